@@ -12,7 +12,7 @@ cd $R
 # through its ordinary-launch route, option jacobi_persist = 3): the bench lines below quote a counter file only when its launch time is within
 # 5 % of the live one, so they must see the files of THIS build
 ( timeout 1800 python scripts/pmc_all.py $TAG > $O/pmc.log 2>&1; cp gpurun_out/pmc/${TAG}_pmc_*.json $O/ 2>/dev/null; cp gpurun_out/pmc/${TAG}_pmc_*.json $R/profiles/ 2>/dev/null )
-timeout 300 python bench.py < /dev/null > $O/${TAG}_bench_line.json 2> $O/bench.err
+timeout 300 python bench.py --full < /dev/null > $O/${TAG}_bench_line.json 2> $O/bench.err
 timeout 300 python scripts/bench_other.py cqrrpt --steps 3 < /dev/null > $O/${TAG}_c3_cqrrpt_line.json 2> $O/c3.err
 timeout 300 python scripts/bench_other.py cqrrpt --steps 3 --opt saso_mode=0 < /dev/null > $O/${TAG}_c3_cqrrpt_affine_saso_line.json 2>> $O/c3.err
 timeout 300 python scripts/bench_other.py bqrrp64 --steps 3 < /dev/null > $O/${TAG}_bqrrp_f64_16k_line.json 2> $O/b64.err
@@ -20,7 +20,7 @@ timeout 300 python scripts/bench_other.py bqrrp_full --steps 2 < /dev/null > $O/
 timeout 300 python scripts/bench_other.py bqrrp_full --steps 1 --triple default < /dev/null > $O/${TAG}_c4_bqrrp_f32_65536_default_triple_line.json 2>> $O/c4.err
 timeout 300 python scripts/bench_other.py abrik --steps 2 < /dev/null > $O/${TAG}_c5_abrik_line.json 2> $O/c5.err
 timeout 400 python scripts/bench_other.py rsvd_p2 --steps 2 < /dev/null > $O/${TAG}_c2_p2_planted_line.json 2> $O/c2p2.err
-timeout 300 python bench.py --m 25000 --steps 8 --warmup 3 --no-cpu-baseline < /dev/null > $O/${TAG}_rank_of_8_line.json 2> $O/r8.err
+timeout 300 python bench.py --full --m 25000 --steps 8 --warmup 3 --no-cpu-baseline < /dev/null > $O/${TAG}_rank_of_8_line.json 2> $O/r8.err
 cd /tmp && export TMPDIR=/tmp
 prof() {   # name, command...
     local name=$1; shift
@@ -29,12 +29,12 @@ prof() {   # name, command...
     if [ -n "$f" ]; then cp "$f" $O/${TAG}_${name}_kernel_stats.csv; fi
     rm -rf $O/prof_$name
 }
-prof bench python $R/bench.py --no-cpu-baseline
+prof bench python $R/bench.py --full --no-cpu-baseline
 prof c3_cqrrpt python $R/scripts/bench_other.py cqrrpt --steps 3
-prof rank_of_8 python $R/bench.py --m 25000 --steps 5 --warmup 3 --no-cpu-baseline
+prof rank_of_8 python $R/bench.py --full --m 25000 --steps 5 --warmup 3 --no-cpu-baseline
 prof c4_bqrrp_f32_65536 python $R/scripts/bq_prof.py 65536 2048 f32
 # kernel timeline of one step of the 1/8 row shard (start, duration, gap before each kernel)
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/tl -- python $R/bench.py --m 25000 --steps 6 --warmup 3 --no-cpu-baseline > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/tl -- python $R/bench.py --full --m 25000 --steps 6 --warmup 3 --no-cpu-baseline > /dev/null 2>&1
 python $R/scripts/timeline.py $O/tl 5 > $O/${TAG}_rank_of_8_timeline.txt 2>&1; rm -rf $O/tl
 # the DVFS map behind the clock holders and the look-ahead A/B of BQRRP
 timeout 300 python $R/scripts/dvfs_probe.py > /dev/null 2> $O/${TAG}_dvfs_probe.txt

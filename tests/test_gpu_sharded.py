@@ -102,10 +102,10 @@ def test_rowsharded_stabilisers_power_scheme_and_replicated_qrcp(world, m, n, k,
 
 
 def test_bench_multi_rank_code_path_on_one_gpu():
-    """bench.py --gpus 2 end to end (row sharding, barrier + max-over-ranks timing, JSON line) with two ranks sharing the GPU and
-    gloo as the process group; the driver's real runs differ only in the transport (RCCL)."""
+    """bench.py --gpus 2 --full end to end (row sharding, barrier + max-over-ranks timing, JSON line with the roofline leg) with two ranks
+    sharing the GPU and gloo as the process group; the driver's real runs differ only in the transport (RCCL)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     env = dict(os.environ)
     env["RLHIP_BENCH_BACKEND"] = "gloo"
     env["RLHIP_BENCH_SHAPE"] = "16384,2048,64"
