@@ -312,7 +312,8 @@ int rlhip_gemqrt_f32(rlhip_ctx* ctx, char side, char trans, int64_t m, int64_t n
                      int64_t ldv, const float* T, int64_t ldt, float* C, int64_t ldc);
 /* The left / transposed apply of ONE compact-WY block (k reflectors, nb >= k) in two calls, cut where the first k rows of C -- BQRRP's block
  * row R12 (rl_bqrrp.hh:547) -- are final: head computes W2 = T^T V^T C (k x n, ld k, the caller's buffer) and updates rows 0..k-1 of C;
- * tail updates rows k..m-1 (C2 -= V2 W2).  head + tail == rlhip_gemqrt_*('L', 'T', ..., nb = k) bit for bit. */
+ * tail updates rows k..m-1 (C2 -= V2 W2).  head + tail == rlhip_gemqrt_*('L', 'T', ..., nb = k) bit for bit under rlhip_avoid_persistent(ctx, 1),
+ * to rounding otherwise (the tail never takes the persistent stream-K GEMM, gemqrt may). */
 int rlhip_gemqrt_head_f64(rlhip_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* V, int64_t ldv, const double* T, int64_t ldt, double* C, int64_t ldc, double* W2);
 int rlhip_gemqrt_head_f32(rlhip_ctx* ctx, int64_t m, int64_t n, int64_t k, const float* V, int64_t ldv, const float* T, int64_t ldt, float* C, int64_t ldc, float* W2);
 int rlhip_gemqrt_tail_f64(rlhip_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* V, int64_t ldv, const double* W2, double* C, int64_t ldc);

@@ -29,7 +29,8 @@ namespace {
 constexpr int LB = 32;
 
 // Sign-modified LU step (dlaorhr_col_getrfnp semantics) on the diagonal block [j0, j0+jb) and its block row:
-//   for i: D(i) = -sign(a_ii) (1 if a_ii == 0); a_ii -= D(i); column below /= a_ii; trailing -= col * row
+//   for i: D(i) = -sign(a_ii) with the sign bit read as LAPACK's SIGN(ONE, a_ii) does (+0.0 -> D = -1, -0.0 -> D = +1); a_ii -= D(i);
+//   column below /= a_ii; trailing -= col * row
 // Every workgroup re-factors the jb x jb block in LDS; workgroup 0 writes it back (+ D); every workgroup then
 // computes its slice of U12 = L11^-1 A12 (one column per thread).
 template <typename T>
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void lunp_panel_kernel(int64_t n, int64_t j0, 
     for (int k = 0; k < jb; ++k) {
         if (tid == 0) {
             T a = sA[k][k];
-            T dd = (a == T(0)) ? T(1) : ((a > T(0)) ? T(-1) : T(1));
+            const T dd = signbit(a) ? T(1) : T(-1);
             sD[k] = dd;
             sA[k][k] = a - dd;
         }
@@ -130,7 +131,9 @@ __global__ void tau_from_t_kernel(int64_t k, int64_t nb, const T* __restrict__ T
     if (i < k) tau[i] = Tm[(i % nb) + i * ldt];
 }
 
-// M = striu(G) + diag(1/tau); tau == 0 (H = I) -> a huge diagonal so that the column of T vanishes
+// M = striu(G) + diag(1/tau).  tau(i) == 0 (H_i = I) is the limit 1/tau(i) -> inf, in which row and column i of T = M^-1 vanish and the
+// rest of T is the inverse of M without row and column i: that row and column of M become the unit vector here (the solve keeps index i
+// apart, no inf on the diagonal) and larft_zero_kernel clears the 1 it leaves on T's diagonal -- dlarft's exact zero row and column
 template <typename T>
 __global__ void larft_m_kernel(int64_t k, T* __restrict__ G, int64_t ldg, const T* __restrict__ tau) {
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -138,8 +141,14 @@ __global__ void larft_m_kernel(int64_t k, T* __restrict__ G, int64_t ldg, const 
     int64_t i = idx % k, j = idx / k;
     T v = G[i + j * ldg];
     if (i > j) v = 0;
-    else if (i == j) v = (tau[i] != T(0)) ? T(1) / tau[i] : T(1e300);
+    else if (i == j) v = (tau[i] != T(0)) ? T(1) / tau[i] : T(1);
+    else if (tau[i] == T(0) || tau[j] == T(0)) v = 0;
     G[i + j * ldg] = v;
+}
+template <typename T>
+__global__ void larft_zero_kernel(int64_t k, T* __restrict__ Tm, int64_t ldt, const T* __restrict__ tau) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < k && tau[i] == T(0)) Tm[i + i * ldt] = T(0);
 }
 
 // flag |= any(|x[i]| > thr), i < n                                                  rl_bqrrp.hh:373-379
@@ -274,7 +283,9 @@ int gemqrt_lt(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, int64_t nb, const T
 //   head:  W2 = T^T (V1^T C1 + V2^T C2),  C1 -= V1 W2     -- after it the block row C1 (BQRRP's R12, rl_bqrrp.hh:547) does not change any more
 //   tail:  C2 -= V2 W2                                     -- the big product; nothing on the path to the NEXT panel's pivots reads C2
 // BQRRP's look-ahead (rl_bqrrp.hh, detail::bqrrp_factor) runs the sketch down-date and the next QRCP of the sketch beside the tail.
-// W2 is the caller's k x n buffer (ld k).  Same kernels, same order of operations as gemqrt_lt with nb >= k: bitwise the same C.
+// W2 is the caller's k x n buffer (ld k).  Same order of operations as gemqrt_lt with nb >= k, and bitwise the same C while no product of
+// this context may take the persistent stream-K GEMM (rlhip_avoid_persistent): the tail always runs C2 -= V2 W2 on the tiled kernel, where
+// gemqrt_lt hands that product to the persistent kernel once it passes the work gate (gemm_sk.hip) -- the same C to rounding then.
 template <typename T>
 int gemqrt_lt_head(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, const T* V, int64_t ldv, const T* Tm, int64_t ldt, T* C, int64_t ldc, T* W2) {
     if (m < 0) return -3;
@@ -359,6 +370,11 @@ int larft_gram(rlhip_ctx* c, int64_t m, int64_t k, const T* V, int64_t ldv, cons
     RLHIP_LAUNCH_CHECK();
     rc = laset<T>(c, 2, k, k, T(0), T(1), Tm, ldt);                       // T = I * M^-1
     if (!rc) rc = trsm_right_upper<T>(c, 0, k, k, T(1), G, k, Tm, ldt);
+    if (!rc) {
+        hipLaunchKernelGGL(larft_zero_kernel<T>, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, k, Tm, ldt, tau);
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) rc = RLHIP_ERR_HIP(le);
+    }
     rlhip_ws_release(c, mark);
     return rc;
 }

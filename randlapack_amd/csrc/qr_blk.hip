@@ -320,7 +320,8 @@ __global__ __launch_bounds__(NT) void qr_blk_kernel(QbArgs<T> g) {
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The same ownership for the sign-modified LU WITHOUT pivoting of Householder reconstruction (lapack::orhr_col -> dlaorhr_col_getrfnp,
-// rl_bqrrp.hh:480 / rl_cqrrt.hh): for i: D(i) = -sign(a_ii), a_ii -= D(i), column below /= a_ii, trailing -= column * row.
+// rl_bqrrp.hh:480 / rl_cqrrt.hh): for i: D(i) = -sign(a_ii) (LAPACK's SIGN: -1 for +0.0, +1 for -0.0), a_ii -= D(i), column below /= a_ii,
+// trailing -= column * row.
 // No pivot search, so a column step needs NO reduction at all -- the thread that holds the diagonal row broadcasts it through LDS -- and
 // a block application is  U_kc = L_kk^-1 C(block rows),  C(below) -= L_k U_kc  with the 8 x 8 pieces handed over by the eight threads
 // that hold the block's rows.  2048 x 2048 fp32 took 64 panels x (panel kernel + trsm + GEMM) = 5.5 ms of launches before.
@@ -420,7 +421,7 @@ __global__ __launch_bounds__(NT) void lunp_blk_kernel(LbArgs<T> g) {
                 const int r = tid + NT * q;
                 if (r == j) {
                     const T a = c[q][cc];
-                    const T dd = (a == T(0)) ? T(1) : ((a > T(0)) ? T(-1) : T(1));
+                    const T dd = signbit(a) ? T(1) : T(-1);
                     c[q][cc] = a - dd;
                     s_d[cc] = dd;
 #pragma unroll
@@ -502,7 +503,7 @@ template int geqrf_blk<double>(rlhip_ctx*, int64_t, int64_t, double*, int64_t, d
 template int geqrf_blk<float>(rlhip_ctx*, int64_t, int64_t, float*, int64_t, float*);
 
 // Sign-modified LU without pivoting of the n x n matrix A (what lapack::orhr_col runs on the top block of Q): L (unit lower) and U in
-// place, D(i) = -sign of the i-th pivot before its modification.  Returns 1 when done here, 0 when the problem does not fit the kernel.
+// place, D(i) = -sign of the i-th pivot before its modification (sign bit: +0.0 gives D = -1, as in LAPACK).  Returns 1 when done here, 0 when the problem does not fit the kernel.
 template <typename T>
 int lunp_blk(rlhip_ctx* c, int64_t n, T* A, int64_t lda, T* D) {
     constexpr int NT = 512, RPT = 4;
