@@ -940,8 +940,11 @@ static hipError_t qr_kernel_lds_limit(rlhip_ctx* c, const void* kern) {
 }
 
 template <typename T>
+static int qrcp_guarded(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* jpvt_dev, T* tau_dev, int64_t steps, int hq_formula);
+
+template <typename T>
 int geqp3(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* jpvt_dev, T* tau_dev) {
-    return qr_core<T>(c, 1, m, n, A, lda, jpvt_dev, tau_dev);
+    return qrcp_guarded<T>(c, m, n, A, lda, jpvt_dev, tau_dev, -1, 0);
 }
 
 // Pivoted Householder QR restricted to the first `steps` columns, with the norm down-date in HQRRP's form: the device
@@ -949,14 +952,14 @@ int geqp3(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* jpvt_d
 // whole permutation (1-based) that the column swaps of those steps produce.
 template <typename T>
 int qrp_partial(rlhip_ctx* c, int64_t m, int64_t n, int64_t steps, T* A, int64_t lda, int64_t* jpvt_dev, T* tau_dev) {
-    return qr_core<T>(c, 1, m, n, A, lda, jpvt_dev, tau_dev, steps, 1);
+    return qrcp_guarded<T>(c, m, n, A, lda, jpvt_dev, tau_dev, steps, 1);
 }
 // The first `steps` steps of geqp3 itself (LAPACK's norm down-date form): on exit rows 0 .. steps-1 of R are final for ALL columns, the trailing
 // (m - steps) x (n - steps) block carries every reflector so far and jpvt the permutation so far -- geqp3 of that block, its pivots applied to
 // the columns of the finished rows and composed into jpvt, completes the factorization (CQRRPT's split QRCP, rl_cqrrpt.hh).
 template <typename T>
 int geqp3_steps(rlhip_ctx* c, int64_t m, int64_t n, int64_t steps, T* A, int64_t lda, int64_t* jpvt_dev, T* tau_dev) {
-    return qr_core<T>(c, 1, m, n, A, lda, jpvt_dev, tau_dev, steps, 0);
+    return qrcp_guarded<T>(c, m, n, A, lda, jpvt_dev, tau_dev, steps, 0);
 }
 template int geqp3_steps<double>(rlhip_ctx*, int64_t, int64_t, int64_t, double*, int64_t, int64_t*, double*);
 template int geqp3_steps<float>(rlhip_ctx*, int64_t, int64_t, int64_t, float*, int64_t, int64_t*, float*);
@@ -972,7 +975,9 @@ template int qrp_partial<float>(rlhip_ctx*, int64_t, int64_t, int64_t, float*, i
 // result stays on the device), factors s A with s the power of two that brings it into [1, 2) when it lies outside the safe window --
 // exact: the reflectors and tau do not depend on the scale -- and gives R its scale back.  No host read; inside the window (always, on
 // this path's sketches) the two rescale launches find s = 1 and write nothing.  What is NOT protected: a column more than half the
-// exponent range below the matrix's largest entry loses its norm to underflow.
+// exponent range below the matrix's largest entry loses its norm to underflow.  The pivoted routes (geqp3, geqp3_steps, qrp_partial) run
+// behind the same guard (qrcp_guarded below): s is a power of two, so every partial norm, every comparison of the pivot search and every
+// tau are those of the unscaled matrix and the pivots do not change; R and, after a partial factorization, the trailing block get 1 / s.
 // w[0] = max |a_ij| as a bit pattern (non-negative IEEE values order like unsigned integers)
 template <typename T>
 __global__ __launch_bounds__(256) void geqrf_absmax_kernel(int64_t m, int64_t n, const T* __restrict__ A, int64_t lda, unsigned long long* __restrict__ w) {
@@ -1008,15 +1013,17 @@ __device__ __forceinline__ double geqrf_scale_of(const unsigned long long* w) {
     (void)frexp(mx, &ex);
     return ldexp(1.0, 1 - ex);
 }
-// A *= s (back = 0: the whole matrix) or A(i <= j) /= s (back = 1: the R part of the result)
+// A *= s (back = 0: the whole matrix) or A(i <= j) /= s (back = 1: the R part of the result) -- and A(i >= tail, j >= tail) /= s, the trailing block
+// a partial factorization leaves (tail = min(m, n) selects nothing more)
 template <typename T>
-__global__ __launch_bounds__(256) void geqrf_rescale_kernel(int64_t m, int64_t n, T* __restrict__ A, int64_t lda, const unsigned long long* __restrict__ w, int back) {
+__global__ __launch_bounds__(256) void geqrf_rescale_kernel(int64_t m, int64_t n, T* __restrict__ A, int64_t lda, const unsigned long long* __restrict__ w, int back,
+                                                            int64_t tail) {
     const double s = geqrf_scale_of<T>(w);
     if (s == 1.0) return;
     const double f = back ? 1.0 / s : s;               // (a power of two: exact both ways)
     for (int64_t j = blockIdx.y; j < n; j += gridDim.y)
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256)
-            if (!back || i <= j) A[i + j * lda] = (T)((double)A[i + j * lda] * f);
+            if (!back || i <= j || (i >= tail && j >= tail)) A[i + j * lda] = (T)((double)A[i + j * lda] * f);
 }
 
 template <typename T>
@@ -1036,13 +1043,45 @@ int geqrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev) {
     if (bx > 64) bx = 64;
     if (by > 1024 / bx) by = 1024 / bx;
     const dim3 blocks((unsigned)bx, (unsigned)(by < 1 ? 1 : by));
+    const int64_t kmin = m < n ? m : n;
     hipError_t e = hipMemsetAsync(w, 0, sizeof(unsigned long long), c->stream);
     if (e != hipSuccess) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(e); }
     hipLaunchKernelGGL(geqrf_absmax_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w);
-    hipLaunchKernelGGL(geqrf_rescale_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w, 0);
+    hipLaunchKernelGGL(geqrf_rescale_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w, 0, kmin);
     int rc = geqrf_core<T>(c, m, n, A, lda, tau_dev);
     if (!rc) {
-        hipLaunchKernelGGL(geqrf_rescale_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w, 1);
+        hipLaunchKernelGGL(geqrf_rescale_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w, 1, kmin);
+        e = hipGetLastError();
+        if (e != hipSuccess) rc = RLHIP_ERR_HIP(e);
+    }
+    rlhip_ws_release(c, mark);
+    return rc;
+}
+
+// the pivoted routes behind geqrf's exponent-range guard: tau and the reflectors are scale-free; R and the trailing block of a partial
+// factorization (rows and columns >= steps: matrix data, not reflectors) get the scale back.  (qr_core's unpivoted route runs behind geqrf's own.)
+template <typename T>
+static int qrcp_guarded(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* jpvt_dev, T* tau_dev, int64_t steps, int hq_formula) {
+    if (m < 0) return -2;
+    if (n < 0) return -3;
+    if (lda < (m > 1 ? m : 1)) return -5;
+    if (m == 0 || n == 0) return 0;
+    const int64_t kmin = m < n ? m : n;
+    const int64_t tail = (steps >= 0 && steps < kmin) ? steps : kmin;
+    size_t mark = rlhip_ws_mark(c);
+    unsigned long long* w = ws_alloc<unsigned long long>(c, 4);
+    if (!w) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    int64_t bx = (m + 1023) / 1024, by = n;               // (the launch shape of geqrf's guard)
+    if (bx > 64) bx = 64;
+    if (by > 1024 / bx) by = 1024 / bx;
+    const dim3 blocks((unsigned)bx, (unsigned)(by < 1 ? 1 : by));
+    hipError_t e = hipMemsetAsync(w, 0, sizeof(unsigned long long), c->stream);
+    if (e != hipSuccess) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(e); }
+    hipLaunchKernelGGL(geqrf_absmax_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w);
+    hipLaunchKernelGGL(geqrf_rescale_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w, 0, tail);
+    int rc = qr_core<T>(c, 1, m, n, A, lda, jpvt_dev, tau_dev, steps, hq_formula);
+    if (!rc) {
+        hipLaunchKernelGGL(geqrf_rescale_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w, 1, tail);
         e = hipGetLastError();
         if (e != hipSuccess) rc = RLHIP_ERR_HIP(e);
     }
