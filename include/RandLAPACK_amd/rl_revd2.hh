@@ -60,6 +60,18 @@ struct ExplicitSymLinOp {
         blas::gemm(layout, Op::NoTrans, Op::NoTrans, dim, n, dim, alpha, full, dim, B, ldb, beta, C, ldc, q);
     }
 
+    /// rp_cholesky's device view of the operator (rl_rpchol.hh): the diagonal (dim entries, DEVICE) and the columns idx_dev[0:nidx) of
+    /// the symmetrised copy (dim x nidx, ldo) -- the reference reads both through its host functor A_stateless(i, j)
+    void diag(T* d_dev) {
+        materialise();
+        if (dim > 0) lapack::lacpy(MatrixType::General, 1, dim, full, dim + 1, d_dev, 1, q);      // a 1 x dim matrix with stride dim + 1
+    }
+    void columns(int64_t nidx, const int64_t* idx_dev, T* out, int64_t ldo) {
+        materialise();
+        if constexpr (sizeof(T) == 8) blas::check(rlhip_gather_cols_f64(q.ctx(), dim, nidx, idx_dev, (const double*)full, dim, (double*)out, ldo), "gather_cols");
+        else blas::check(rlhip_gather_cols_f32(q.ctx(), dim, nidx, idx_dev, (const float*)full, dim, (float*)out, ldo), "gather_cols");
+    }
+
 private:
     void materialise() {
         if (full || dim == 0) return;

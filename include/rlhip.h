@@ -391,6 +391,67 @@ int rlhip_csr_densify_cols_f64(rlhip_ctx* ctx, int64_t m, const int64_t* rowptrT
 int rlhip_csr_densify_cols_f32(rlhip_ctx* ctx, int64_t m, const int64_t* rowptrT, const int64_t* colidxT, const float* valsT,
                                int64_t c0, int64_t b, float* out, int64_t ldo);
 
+/* ---- squared-exponential (RBF) kernel matrices and randomly pivoted Cholesky (rpchol.hip; RandLAPACK/misc/rl_pdkernels.hh,
+ *      RandLAPACK/comps/rl_rpchol.hh).  X is rows_x x n column-major (ldx), one column per data point; h = bandwidth > 0.
+ *
+ * rlhip_sqexp_columns_*: out(i, l) = exp(-sum_r (X(r,i) - X(r,idx[l]))^2 / (2 h^2)), plus reg where i == idx[l], for all n points i and
+ *   the nidx device indices idx_dev (repeats allowed): squared_exp_kernel (rl_pdkernels.hh:102) as compute_columns evaluates it
+ *   (rl_rpchol.hh:19-31).  Differences, not the norm expansion: the entries i == idx[l] are exactly 1 + reg.  out: n x nidx (ldo).
+ * rlhip_sqexp_submatrix_*: squared_exp_kernel_submatrix (rl_pdkernels.hh:133-148): Ksub (rows_ksub x cols_ksub, ldk) =
+ *   exp(-(|x_i|^2 + |x_j|^2 - 2 x_i^T x_j) / (2 h^2)), i = ro_ksub + row, j = co_ksub + col; MFMA GEMM + one epilogue kernel.
+ *   sq_colnorms_x: device |X(:,j)|^2 for all cols_x points, or NULL (computed into scratch); rlhip_sq_colnorms_* fills it.
+ * rlhip_rbf_apply_*: linops::RBFKernelMatrix::operator() (rl_pdkernels.hh:255-283): C (dim x n) = alpha * K * B + beta * C, plus
+ *   alpha * regs_host[min(i, num_ops - 1)] * B(:, i) in column i when eval_includes_reg (num_ops == 1 or n == num_ops).  K is formed in
+ *   full row blocks by rlhip_sqexp_submatrix (not the reference's symmetric arrowhead) in the context's scratch arena: at most
+ *   max(2^26, dim) entries of K at a time (512 MiB in fp64), plus dim squared norms. */
+int rlhip_sqexp_columns_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t n, const double* X, int64_t ldx, int64_t nidx, const int64_t* idx_dev,
+                            double bandwidth, double reg, double* out, int64_t ldo);
+int rlhip_sqexp_columns_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t n, const float* X, int64_t ldx, int64_t nidx, const int64_t* idx_dev,
+                            float bandwidth, float reg, float* out, int64_t ldo);
+int rlhip_sq_colnorms_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t cols_x, const double* X, int64_t ldx, double* sq_colnorms_x);
+int rlhip_sq_colnorms_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t cols_x, const float* X, int64_t ldx, float* sq_colnorms_x);
+int rlhip_sqexp_submatrix_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t cols_x, const double* X, int64_t ldx, const double* sq_colnorms_x,
+                              int64_t rows_ksub, int64_t cols_ksub, double* Ksub, int64_t ldk, int64_t ro_ksub, int64_t co_ksub, double bandwidth);
+int rlhip_sqexp_submatrix_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t cols_x, const float* X, int64_t ldx, const float* sq_colnorms_x,
+                              int64_t rows_ksub, int64_t cols_ksub, float* Ksub, int64_t ldk, int64_t ro_ksub, int64_t co_ksub, float bandwidth);
+int rlhip_rbf_apply_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t dim, const double* X, int64_t ldx, double bandwidth, const double* regs_host,
+                        int64_t num_ops, int eval_includes_reg, int64_t n, double alpha, const double* B, int64_t ldb, double beta, double* C,
+                        int64_t ldc);
+int rlhip_rbf_apply_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t dim, const float* X, int64_t ldx, float bandwidth, const float* regs_host,
+                        int64_t num_ops, int eval_includes_reg, int64_t n, float alpha, const float* B, int64_t ldb, float beta, float* C,
+                        int64_t ldc);
+/* rlhip_sample_indices_iid_*: RandBLAS::weights_to_cdf + sample_indices_iid as rp_cholesky calls them (rl_rpchol.hh:64, 131, 141-143).
+ * RandBLAS is absent, so the stream is this library's own:
+ *   weights   w_i = max(d_i, 0) (d: n DEVICE weights); all sums in double for both precisions, in this fixed order:
+ *             chunk c = [256c, 256c + 256); loc_i = sequential inclusive sum of w inside i's chunk from 0; S_c = loc of its last element;
+ *             off_0 = 0, off_{c+1} = off_c + S_c sequentially; prefix_i = off_c + loc_i; total = off_{nchunks}.  Bitwise reproducible.
+ *   status    2 if some d_i < -eps(T) or d_i is NaN, else 1 if total < sqrt(n) * eps(T), else 0 (what downdate_d_and_cdf derives from
+ *             RandBLAS's errors, rl_rpchol.hh:47-72).  status != 0: nothing is drawn and next_ctr = ctr.
+ *   draw j    Philox4x32-10 block ctr + j/2 with key; its words 2(j%2), 2(j%2)+1 give w64 = lo | hi << 32, u = ((w64 >> 11) + 0.5) 2^-53;
+ *             sample = the first i with prefix_i > u * total (upper bound), clamped to the last index with w > 0 (so an index of zero
+ *             weight is never drawn).  next_ctr = ctr + ceil(k/2).
+ *   unique    0: the k draws in draw order; 1: sorted and de-duplicated in LDS by one workgroup (k <= 4096), *count = distinct values.
+ * out_dev (may be NULL: scratch) receives the samples on the device, out_host (may be NULL) the same k slots on the host; *count and
+ * *status come back through the same, single, host read. */
+int rlhip_sample_indices_iid_f64(rlhip_ctx* ctx, int64_t n, const double* d, int64_t k, int unique, const uint32_t ctr[4], const uint32_t key[2],
+                                 uint32_t next_ctr[4], int64_t* out_dev, int64_t* out_host, int64_t* count, int* status);
+int rlhip_sample_indices_iid_f32(rlhip_ctx* ctx, int64_t n, const float* d, int64_t k, int unique, const uint32_t ctr[4], const uint32_t key[2],
+                                 uint32_t next_ctr[4], int64_t* out_dev, int64_t* out_host, int64_t* count, int* status);
+/* rlhip_rpchol_panel_finish_*: the trsm of rl_rpchol.hh:174 and the downdate of :47-62 for the n x cols panel F (ldf): F <- F U^-1 (U: the
+ * upper triangle of a cols x cols Cholesky factor, ldu), then d_i <- d_i - sum_j F(i,j)^2 (j in order) and d_i <- 0 for i in sidx_dev[0:cols]
+ * (sorted ascending).  cols <= 64: one fused kernel (per-row substitution in registers, U in LDS; the panel is read once and written once);
+ * wider panels: rlhip_trsm, then a downdate kernel.  Asynchronous. */
+int rlhip_rpchol_panel_finish_f64(rlhip_ctx* ctx, int64_t n, int64_t cols, const double* U, int64_t ldu, double* F, int64_t ldf, double* d,
+                                  const int64_t* sidx_dev);
+int rlhip_rpchol_panel_finish_f32(rlhip_ctx* ctx, int64_t n, int64_t cols, const float* U, int64_t ldu, float* F, int64_t ldf, float* d,
+                                  const int64_t* sidx_dev);
+/* row / column gathers with device indices: out(r, c) = A(idx[r], c) (cnt x ncols; _rpchol_impl::pack_selected_rows, rl_rpchol.hh:34-44)
+ * and out(:, c) = A(:, idx[c]) (m x cnt, cnt <= 65535). */
+int rlhip_gather_rows_f64(rlhip_ctx* ctx, int64_t cnt, const int64_t* idx_dev, int64_t ncols, const double* A, int64_t lda, double* out, int64_t ldo);
+int rlhip_gather_rows_f32(rlhip_ctx* ctx, int64_t cnt, const int64_t* idx_dev, int64_t ncols, const float* A, int64_t lda, float* out, int64_t ldo);
+int rlhip_gather_cols_f64(rlhip_ctx* ctx, int64_t m, int64_t cnt, const int64_t* idx_dev, const double* A, int64_t lda, double* out, int64_t ldo);
+int rlhip_gather_cols_f32(rlhip_ctx* ctx, int64_t m, int64_t cnt, const int64_t* idx_dev, const float* A, int64_t lda, float* out, int64_t ldo);
+
 /* ---- row-block sharding across the GPUs of a node (new design; the reference has no
  *      distributed code).  One process per GPU.  Sum all-reduces run on the context's stream through RCCL
  *      (bound at run time), or through a host-installed hook.  With no communicator every call is a no-op,

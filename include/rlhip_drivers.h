@@ -203,6 +203,29 @@ int rlhip_drv_revd2_f64(rlhip_ctx* ctx, char uplo, int64_t m, const double* A, i
 int rlhip_drv_syrf_f64(rlhip_ctx* ctx, char uplo, int64_t m, const double* A, int64_t k, int64_t syps_passes, int64_t passes_per_stab,
                        int orth_kind, double* Q, uint32_t state[6]);
 
+/* rp_cholesky (comps/rl_rpchol.hh:114-187; include/RandLAPACK_amd/rl_rpchol.hh) on a squared-exponential kernel matrix (RBF): the n points are
+ * the columns of X (rows_x x n, ldx, DEVICE), K(i,j) = exp(-|x_i - x_j|^2 / (2 bandwidth^2)) + reg [i == j].  *k: in = target rank, out =
+ * achieved rank.  S_host (k entries) receives the pivots in the order chosen, F (n x k, ldf, DEVICE, caller-allocated) the factor with
+ * K ~ F F^T.  status[0] = w_status (downdate_d_and_cdf's 0 / 1 / 2 after the last block), status[1] = c_status (potrf's info of the block
+ * that broke down, 0 if none).  A diagonal that is no valid weight vector (e.g. all zero) returns 0 with *k = 0 and status[0] = 1 or 2;
+ * the C++ rp_cholesky throws there, as the reference's weights_to_cdf does.  b in [1, 4096]. */
+int rlhip_drv_rpchol_rbf_f64(rlhip_ctx* ctx, const double* X, int64_t ldx, int64_t rows_x, int64_t n, double bandwidth, double reg, int64_t* k,
+                             int64_t b, int64_t* S_host, double* F, int64_t ldf, uint32_t state[6], int status[2]);
+int rlhip_drv_rpchol_rbf_f32(rlhip_ctx* ctx, const float* X, int64_t ldx, int64_t rows_x, int64_t n, float bandwidth, float reg, int64_t* k,
+                             int64_t b, int64_t* S_host, float* F, int64_t ldf, uint32_t state[6], int status[2]);
+/* the same on a full symmetric PSD matrix A (n x n, lda, DEVICE; its upper triangle is symmetrised into a scratch copy, linops::ExplicitSymLinOp),
+ * which is what the reference's own tests feed it (test/comps/test_rpchol.cc) */
+int rlhip_drv_rpchol_dense_f64(rlhip_ctx* ctx, int64_t n, const double* A, int64_t lda, int64_t* k, int64_t b, int64_t* S_host, double* F,
+                               int64_t ldf, uint32_t state[6], int status[2]);
+int rlhip_drv_rpchol_dense_f32(rlhip_ctx* ctx, int64_t n, const float* A, int64_t lda, int64_t* k, int64_t b, int64_t* S_host, float* F,
+                               int64_t ldf, uint32_t state[6], int status[2]);
+/* rpchol_pc_data (comps/rl_preconditioners.hh:348-361) on the RBF matrix above: V (n x k, ld n, DEVICE) <- left singular vectors of the RPCholesky
+ * factor, eigvals (k, DEVICE) <- its squared singular values, so K ~ V diag(eigvals) V^T.  *k: achieved rank.  -100 if the diagonal fails. */
+int rlhip_drv_rpchol_pc_data_rbf_f64(rlhip_ctx* ctx, const double* X, int64_t ldx, int64_t rows_x, int64_t n, double bandwidth, double reg,
+                                     int64_t* k, int64_t b, double* V, double* eigvals, uint32_t state[6]);
+int rlhip_drv_rpchol_pc_data_rbf_f32(rlhip_ctx* ctx, const float* X, int64_t ldx, int64_t rows_x, int64_t n, float bandwidth, float reg,
+                                     int64_t* k, int64_t b, float* V, float* eigvals, uint32_t state[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,24 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):
     for _name, _args in _blas3(_T).items():
         SIGNATURES[f"rlhip_{_name}_{_suf}"] = (c_int, _args)
 
+i64p = C.POINTER(c_i64)
+intp = C.POINTER(c_int)
+for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # squared-exponential kernels and randomly pivoted Cholesky (rpchol.hip, rl_rpchol.hh)
+    SIGNATURES.update({
+        f"rlhip_sqexp_columns_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, _T, _T, c_vp, c_i64]),
+        f"rlhip_sq_colnorms_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
+        f"rlhip_sqexp_submatrix_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, _T]),
+        f"rlhip_rbf_apply_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, _T, C.POINTER(_T), c_i64, c_int, c_i64, _T, c_vp, c_i64, _T, c_vp,
+                                            c_i64]),
+        f"rlhip_sample_indices_iid_{_suf}": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, u32p, u32p, u32p, c_vp, i64p, i64p, intp]),
+        f"rlhip_rpchol_panel_finish_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+        f"rlhip_gather_rows_{_suf}": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64]),
+        f"rlhip_gather_cols_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64]),
+        f"rlhip_drv_rpchol_rbf_{_suf}": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, _T, _T, i64p, c_i64, i64p, c_vp, c_i64, u32p, intp]),
+        f"rlhip_drv_rpchol_dense_{_suf}": (c_int, [c_vp, c_i64, c_vp, c_i64, i64p, c_i64, i64p, c_vp, c_i64, u32p, intp]),
+        f"rlhip_drv_rpchol_pc_data_rbf_{_suf}": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, _T, _T, i64p, c_i64, c_vp, c_vp, u32p]),
+    })
+
 _lib = None
 
 

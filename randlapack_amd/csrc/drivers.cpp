@@ -720,3 +720,75 @@ int rlhip_drv_syrf_f64(rlhip_ctx* ctx, char uplo, int64_t m, const double* A, in
 }
 
 }  // extern "C"
+
+// ---- randomly pivoted Cholesky (include/RandLAPACK_amd/rl_rpchol.hh) on an RBF kernel matrix or an explicit PSD matrix
+namespace {
+template <typename T, typename KOP>
+int drv_rpchol(KOP& A, int64_t n, int64_t* k, int64_t b, int64_t* S_host, T* F, int64_t ldf, uint32_t state[6], int status[2]) {
+    State st = load_state(state);
+    const auto r = RandLAPACK::_rpchol_impl::run(n, A, *k, S_host, F, ldf, b, st);
+    store_state(st, state);
+    status[0] = r.w_status;
+    status[1] = r.c_status;
+    return 0;
+}
+template <typename T>
+int drv_rpchol_rbf(rlhip_ctx* ctx, const T* X, int64_t ldx, int64_t rows_x, int64_t n, T bandwidth, T reg, int64_t* k, int64_t b, int64_t* S_host,
+                   T* F, int64_t ldf, uint32_t state[6], int status[2]) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        std::vector<T> regs{reg};
+        lo::RBFKernelMatrix<T> A(n, X, rows_x, bandwidth, regs, q, ldx);
+        A.set_eval_includes_reg(true);
+        return drv_rpchol<T>(A, n, k, b, S_host, F, ldf, state, status);
+    });
+}
+template <typename T>
+int drv_rpchol_dense(rlhip_ctx* ctx, int64_t n, const T* Ad, int64_t lda, int64_t* k, int64_t b, int64_t* S_host, T* F, int64_t ldf,
+                     uint32_t state[6], int status[2]) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        lo::ExplicitSymLinOp<T> A(n, RandLAPACK::Uplo::Upper, Ad, lda, RandLAPACK::Layout::ColMajor, q);
+        return drv_rpchol<T>(A, n, k, b, S_host, F, ldf, state, status);
+    });
+}
+template <typename T>
+int drv_rpchol_pc_data_rbf(rlhip_ctx* ctx, const T* X, int64_t ldx, int64_t rows_x, int64_t n, T bandwidth, T reg, int64_t* k, int64_t b,
+                           T* V, T* eigvals, uint32_t state[6]) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        std::vector<T> regs{reg};
+        lo::RBFKernelMatrix<T> A(n, X, rows_x, bandwidth, regs, q, ldx);
+        A.set_eval_includes_reg(true);
+        State st = load_state(state);
+        st = RandLAPACK::rpchol_pc_data(n, A, *k, b, V, eigvals, st);
+        store_state(st, state);
+        return 0;
+    });
+}
+}  // namespace
+
+int rlhip_drv_rpchol_rbf_f64(rlhip_ctx* ctx, const double* X, int64_t ldx, int64_t rows_x, int64_t n, double bandwidth, double reg, int64_t* k,
+                             int64_t b, int64_t* S_host, double* F, int64_t ldf, uint32_t state[6], int status[2]) {
+    return drv_rpchol_rbf<double>(ctx, X, ldx, rows_x, n, bandwidth, reg, k, b, S_host, F, ldf, state, status);
+}
+int rlhip_drv_rpchol_rbf_f32(rlhip_ctx* ctx, const float* X, int64_t ldx, int64_t rows_x, int64_t n, float bandwidth, float reg, int64_t* k,
+                             int64_t b, int64_t* S_host, float* F, int64_t ldf, uint32_t state[6], int status[2]) {
+    return drv_rpchol_rbf<float>(ctx, X, ldx, rows_x, n, bandwidth, reg, k, b, S_host, F, ldf, state, status);
+}
+int rlhip_drv_rpchol_dense_f64(rlhip_ctx* ctx, int64_t n, const double* A, int64_t lda, int64_t* k, int64_t b, int64_t* S_host, double* F,
+                               int64_t ldf, uint32_t state[6], int status[2]) {
+    return drv_rpchol_dense<double>(ctx, n, A, lda, k, b, S_host, F, ldf, state, status);
+}
+int rlhip_drv_rpchol_dense_f32(rlhip_ctx* ctx, int64_t n, const float* A, int64_t lda, int64_t* k, int64_t b, int64_t* S_host, float* F,
+                               int64_t ldf, uint32_t state[6], int status[2]) {
+    return drv_rpchol_dense<float>(ctx, n, A, lda, k, b, S_host, F, ldf, state, status);
+}
+int rlhip_drv_rpchol_pc_data_rbf_f64(rlhip_ctx* ctx, const double* X, int64_t ldx, int64_t rows_x, int64_t n, double bandwidth, double reg,
+                                     int64_t* k, int64_t b, double* V, double* eigvals, uint32_t state[6]) {
+    return drv_rpchol_pc_data_rbf<double>(ctx, X, ldx, rows_x, n, bandwidth, reg, k, b, V, eigvals, state);
+}
+int rlhip_drv_rpchol_pc_data_rbf_f32(rlhip_ctx* ctx, const float* X, int64_t ldx, int64_t rows_x, int64_t n, float bandwidth, float reg,
+                                     int64_t* k, int64_t b, float* V, float* eigvals, uint32_t state[6]) {
+    return drv_rpchol_pc_data_rbf<float>(ctx, X, ldx, rows_x, n, bandwidth, reg, k, b, V, eigvals, state);
+}

@@ -722,3 +722,135 @@ def drv_cqrrpt_gpu(ctx: Context, A_host, d_factor=1.25, nnz=4, eps=None, ctr=(0,
     if timing:
         out["times_us"] = [int(t) for t in times]
     return out
+
+
+# ---- squared-exponential kernel matrices and randomly pivoted Cholesky (rpchol.hip; include/RandLAPACK_amd/rl_rpchol.hh, rl_pdkernels.hh).
+#      X is a column-major tensor (n, rows_x): column j of the rows_x x n matrix (one data point) is X[j].  fp64 or fp32 by X's dtype.
+def _suf(t):
+    torch = _torch()
+    if t.dtype == torch.float64:
+        return "f64", C.c_double
+    if t.dtype == torch.float32:
+        return "f32", C.c_float
+    raise TypeError(f"unsupported dtype {t.dtype}")
+
+
+def _ld(t):
+    """leading dimension of a column-major tensor (cols, ld-strided rows)"""
+    return int(t.stride(0)) if t.dim() == 2 else int(t.numel())
+
+
+def sqexp_columns(ctx: Context, X, rows_x, n, idx, bandwidth, reg=0.0, out=None):
+    """out(i, l) = exp(-|x_i - x_idx[l]|^2 / (2 h^2)) (+ reg where i == idx[l]); idx: int64 device tensor.  Returns out (nidx, n) column-major."""
+    torch = _torch()
+    suf, _ = _suf(X)
+    nidx = int(idx.numel())
+    if out is None:
+        out = torch.empty((nidx, n), dtype=X.dtype, device=X.device)
+    rc = getattr(ctx.lib, f"rlhip_sqexp_columns_{suf}")(ctx.h, rows_x, n, X.data_ptr(), _ld(X), nidx, idx.data_ptr(), bandwidth, reg,
+                                                       out.data_ptr(), _ld(out) if nidx > 1 else max(n, 1))
+    _lib.check(rc, "sqexp_columns")
+    return out
+
+
+def sqexp_submatrix(ctx: Context, X, rows_x, cols_x, rows_k, cols_k, ro, co, bandwidth, sq_colnorms=None):
+    """squared_exp_kernel_submatrix: Ksub (cols_k, rows_k) column-major"""
+    torch = _torch()
+    suf, _ = _suf(X)
+    K = torch.empty((cols_k, rows_k), dtype=X.dtype, device=X.device)
+    rc = getattr(ctx.lib, f"rlhip_sqexp_submatrix_{suf}")(ctx.h, rows_x, cols_x, X.data_ptr(), _ld(X),
+                                                         None if sq_colnorms is None else sq_colnorms.data_ptr(), rows_k, cols_k, K.data_ptr(),
+                                                         max(rows_k, 1), ro, co, bandwidth)
+    _lib.check(rc, "sqexp_submatrix")
+    return K
+
+
+def sq_colnorms(ctx: Context, X, rows_x, cols_x):
+    torch = _torch()
+    suf, _ = _suf(X)
+    nr = torch.empty(cols_x, dtype=X.dtype, device=X.device)
+    _lib.check(getattr(ctx.lib, f"rlhip_sq_colnorms_{suf}")(ctx.h, rows_x, cols_x, X.data_ptr(), _ld(X), nr.data_ptr()), "sq_colnorms")
+    return nr
+
+
+def rbf_apply(ctx: Context, X, rows_x, dim, bandwidth, B, n, alpha=1.0, beta=0.0, C_=None, regs=(), eval_includes_reg=False):
+    """linops::RBFKernelMatrix::operator(): C = alpha (K [+ regs]) B + beta C; B, C column-major (n, dim)"""
+    torch = _torch()
+    suf, T = _suf(X)
+    if C_ is None:
+        C_ = torch.zeros((n, dim), dtype=X.dtype, device=X.device)
+    rg = (T * max(len(regs), 1))(*(list(regs) or [0.0]))
+    rc = getattr(ctx.lib, f"rlhip_rbf_apply_{suf}")(ctx.h, rows_x, dim, X.data_ptr(), _ld(X), bandwidth, rg, max(len(regs), 1),
+                                                   1 if eval_includes_reg else 0, n, alpha, B.data_ptr(), _ld(B), beta, C_.data_ptr(), _ld(C_))
+    _lib.check(rc, "rbf_apply")
+    return C_
+
+
+def sample_indices_iid(ctx: Context, d, k, unique=False, ctr=(0, 0, 0, 0), key=(0, 0)):
+    """the library's weighted iid sampler (include/rlhip.h rlhip_sample_indices_iid_*) on the device weights d.
+    Returns dict(S (numpy int64: k draws, or the sorted distinct ones), count, status, next_ctr, S_dev)."""
+    torch = _torch()
+    suf, _ = _suf(d)
+    out_dev = torch.empty(max(k, 1), dtype=torch.int64, device=d.device)
+    out_host = np.zeros(max(k, 1), dtype=np.int64)
+    c4 = (C.c_uint32 * 4)(*[int(v) & 0xFFFFFFFF for v in ctr])
+    k2 = (C.c_uint32 * 2)(*[int(v) & 0xFFFFFFFF for v in key])
+    nxt = (C.c_uint32 * 4)()
+    cnt, status = C.c_int64(0), C.c_int(0)
+    rc = getattr(ctx.lib, f"rlhip_sample_indices_iid_{suf}")(ctx.h, int(d.numel()), d.data_ptr(), k, 1 if unique else 0, c4, k2, nxt,
+                                                            out_dev.data_ptr(), out_host.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cnt),
+                                                            C.byref(status))
+    _lib.check(rc, "sample_indices_iid")
+    m = int(cnt.value)
+    return dict(S=out_host[:m].copy(), count=m, status=int(status.value), next_ctr=tuple(int(x) for x in nxt), S_dev=out_dev[:m])
+
+
+def _rpchol_out(ctx, st, kk, S, F, status):
+    kf = int(kk.value)
+    return dict(F=F, S=S[:kf].copy(), k=kf, status=int(status[0]), c_status=int(status[1]), next_ctr=tuple(int(x) for x in st[:4]))
+
+
+def drv_rpchol_rbf(ctx: Context, X, rows_x, n, bandwidth, k, b, reg=0.0, ctr=(0, 0, 0, 0), key=(0, 0)):
+    """rp_cholesky on the RBF kernel matrix of the points X (column-major (n, rows_x)).  Returns dict(F (k_target, n) column-major -- only the
+    first k columns are the factor --, S, k, status (w_status), c_status, next_ctr)."""
+    torch = _torch()
+    suf, _ = _suf(X)
+    F = torch.zeros((k, n), dtype=X.dtype, device=X.device)
+    S = np.full(max(k, 1), -1, dtype=np.int64)
+    kk = C.c_int64(k)
+    st = _state_arr(ctr, key)
+    status = (C.c_int * 2)()
+    rc = getattr(ctx.lib, f"rlhip_drv_rpchol_rbf_{suf}")(ctx.h, X.data_ptr(), _ld(X), rows_x, n, bandwidth, reg, C.byref(kk), b,
+                                                        S.ctypes.data_as(C.POINTER(C.c_int64)), F.data_ptr(), n, st, status)
+    _drv_check(ctx, rc, "rpchol_rbf")
+    return _rpchol_out(ctx, st, kk, S, F, status)
+
+
+def drv_rpchol_dense(ctx: Context, A, n, k, b, ctr=(0, 0, 0, 0), key=(0, 0)):
+    """rp_cholesky on the symmetric PSD matrix A (column-major (n, n) tensor).  Same dict as drv_rpchol_rbf."""
+    torch = _torch()
+    suf, _ = _suf(A)
+    F = torch.zeros((k, n), dtype=A.dtype, device=A.device)
+    S = np.full(max(k, 1), -1, dtype=np.int64)
+    kk = C.c_int64(k)
+    st = _state_arr(ctr, key)
+    status = (C.c_int * 2)()
+    rc = getattr(ctx.lib, f"rlhip_drv_rpchol_dense_{suf}")(ctx.h, n, A.data_ptr(), _ld(A), C.byref(kk), b, S.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                          F.data_ptr(), n, st, status)
+    _drv_check(ctx, rc, "rpchol_dense")
+    return _rpchol_out(ctx, st, kk, S, F, status)
+
+
+def rpchol_pc_data(ctx: Context, X, rows_x, n, bandwidth, k, b, reg=0.0, ctr=(0, 0, 0, 0), key=(0, 0)):
+    """rpchol_pc_data on the RBF kernel matrix: dict(V (k, n) column-major, eigvals (k), k, next_ctr) with K ~ V diag(eigvals) V^T"""
+    torch = _torch()
+    suf, _ = _suf(X)
+    V = torch.zeros((k, n), dtype=X.dtype, device=X.device)
+    ev = torch.zeros(k, dtype=X.dtype, device=X.device)
+    kk = C.c_int64(k)
+    st = _state_arr(ctr, key)
+    rc = getattr(ctx.lib, f"rlhip_drv_rpchol_pc_data_rbf_{suf}")(ctx.h, X.data_ptr(), _ld(X), rows_x, n, bandwidth, reg, C.byref(kk), b,
+                                                                V.data_ptr(), ev.data_ptr(), st)
+    _drv_check(ctx, rc, "rpchol_pc_data")
+    kf = int(kk.value)
+    return dict(V=V[:kf], eigvals=ev[:kf], k=kf, next_ctr=tuple(int(x) for x in st[:4]))
