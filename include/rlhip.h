@@ -196,8 +196,18 @@ int rlhip_laset_f64(rlhip_ctx* ctx, char uplo, int64_t m, int64_t n, double offd
 int rlhip_laset_f32(rlhip_ctx* ctx, char uplo, int64_t m, int64_t n, float offdiag, float diag, float* A,
                     int64_t lda);
 /* thin SVD of a tall m x n matrix (m >= n), replacing lapack::gesdd(Job::SomeVec) at rl_rsvd.hh:146:
- * on exit A holds U (m x n), S[n] descending, VT (n x n, ld ldvt).  One-sided Jacobi, entirely on device.
- * returns the number of sweeps used in *sweeps_host (may be NULL); info > 0 = not converged. */
+ * on exit A holds U (m x n), S[n] descending, VT (n x n, ld ldvt; NULL: singular values and left vectors only).  One-sided Jacobi,
+ * entirely on device.  Returns the number of sweeps used in *sweeps_host (may be NULL); info > 0 = not converged after 60 sweeps.
+ * Argument codes, checked before anything is enqueued: -2 m < 0 or m < n, -3 n < 0, -5 lda < max(1, m), -8 ldvt < max(1, n) with VT != NULL;
+ * n == 0 returns 0 and writes nothing.  Rows beyond m of A and beyond n of VT are not touched.
+ * Scaled inputs: the call measures max |a_ij| and, outside (1e-30, 1e30) in fp64 / (1e-10, 1e10) in fp32, runs on A times the power of
+ * two that brings it into [1, 2); S gets the scale back exactly, U and VT do not depend on it.  So the SVD of 2^e A is that of A with
+ * S times 2^e for every e that keeps A's entries normal numbers -- no sum of squares overflows or vanishes.  (A column more than
+ * half the exponent range below the largest entry still loses its norm.)  fp32 problems, a single column included, run in fp64.
+ * Rank deficiency (rank r < n, zero and repeated columns, the zero matrix): info == 0 and everything finite; S_j <= c n eps sigma_1 for
+ * j >= r; U S VT reproduces A and VT is orthogonal as for full rank; the leading r columns of U are orthonormal.  A column of U that
+ * belongs to S_j == 0 exactly is ZERO, one that belongs to a rounding-level S_j has norm 1 but need not be orthogonal to the others:
+ * this is where the library departs from LAPACK, whose trailing columns of U are orthonormal too. */
 int rlhip_gesvdj_f64(rlhip_ctx* ctx, int64_t m, int64_t n, double* A, int64_t lda, double* S, double* VT,
                      int64_t ldvt, int* sweeps_host);
 int rlhip_gesvdj_f32(rlhip_ctx* ctx, int64_t m, int64_t n, float* A, int64_t lda, float* S, float* VT,
@@ -208,7 +218,11 @@ int rlhip_add_diag_f64(rlhip_ctx* ctx, int64_t n, double alpha, double* A, int64
 int rlhip_add_diag_f32(rlhip_ctx* ctx, int64_t n, float alpha, float* A, int64_t lda);
 /* lapack::gesdd(Job::SomeVec) contract for a tall matrix (m >= n): A (destroyed) = U diag(S) VT with
  * U m x n (ldu), VT n x n (ldvt), S descending.  Cholesky-QR2 preconditioning + Jacobi on R^T; falls back
- * to rlhip_gesvdj on A when the Cholesky steps cannot be trusted.  (rl_rsvd.hh:146) */
+ * to rlhip_gesvdj on A when the Cholesky steps cannot be trusted.  (rl_rsvd.hh:146)
+ * Argument codes in LAPACK's positions, checked before anything is enqueued: -2 m < 0 or m < n, -3 n < 0, -5 lda < max(1, m),
+ * -8 ldu < max(1, m), -10 ldvt < max(1, n); n == 0 returns 0 and writes nothing.  Rows beyond m of A and U and beyond n of VT are not
+ * touched (A may be a block of a larger matrix, as ABRIK passes it).  Scaled and rank-deficient inputs: as rlhip_gesvdj above, on every
+ * route -- a rank-deficient input takes the Jacobi-on-A route, its U has the same zero / non-orthogonal trailing columns. */
 int rlhip_gesdd_f64(rlhip_ctx* ctx, int64_t m, int64_t n, double* A, int64_t lda, double* S, double* U, int64_t ldu,
                     double* VT, int64_t ldvt, int* sweeps_host);
 int rlhip_gesdd_f32(rlhip_ctx* ctx, int64_t m, int64_t n, float* A, int64_t lda, float* S, float* U, int64_t ldu,
@@ -485,7 +499,13 @@ int rlhip_allreduce_sum_host_f64(rlhip_ctx* ctx, double* x_host, int64_t n);   /
  * 12 block iterations of BQRRP whose sketch down-date and next QRCP ran on the side queue (the look-ahead of rl_bqrrp.hh; noted by the C++
  * layer through rlhip_path_note), 13 CQRRPT calls that took the split order (rl_cqrrpt.hh), 14 sparse-sign sketches applied by the LDS-DMA kernel
  * (sketch.hip::saso_apply_dma_kernel), 15 persistent Jacobi launches whose workers sat on one XCD and handed their blocks over through its L2
- * (jacobi.hip; the other launches use the uncached hand-over: same bits, slower).  -1 for an unknown index.  Tests use it to
+ * (jacobi.hip; the other launches use the uncached hand-over: same bits, slower).
+ * The route a device SVD took (svd.hip::gesdd_tall, one count per call on the branch taken; 10 is its Gram route): 16 Cholesky-QR twice,
+ * 17 one pass (the second factorization skipped), 18 V recovered from R Ux instead of accumulated (beside 16 or 17), 19 Jacobi on A after
+ * the first factorization failed or its diagonal ratio reached the limit, 20 Jacobi on A after the second factorization failed and the
+ * first pass was undone.  The sweep driver of a one-sided Jacobi (jacobi.hip::gesvdj, beside 6): 21 LDS-resident blocks of 16 columns x 256
+ * rows, 22 of 16 x 512 rows, 23 of 32 columns x 256 rows, 24 one launch per round (more than 512 rows), 25 an fp32 problem run in fp64
+ * (counted beside the driver it then takes).  26 .. 31 are free.  -1 for an unknown index.  Tests use it to
  * assert that the kernel / route under test is the one that ran. */
 int64_t rlhip_path_count(rlhip_ctx* ctx, int which);
 /* the host layers above this ABI (include/RandLAPACK_amd/) report their own route decisions into the same counters */

@@ -1040,13 +1040,8 @@ template int jacobi_enqueue_rt<double>(rlhip_ctx*, int, const double*, int64_t, 
 template int jacobi_enqueue_rt<float>(rlhip_ctx*, int, const float*, int64_t, int, float, const int*, int*, const float**);
 
 template <typename T>
-int gesvdj(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T* VT, int64_t ldvt,
-           int* sweeps_host) {
-    if (m < 0) return -2;
-    if (n64 < 0) return -3;
-    if (m < n64) return -2;  // tall only (the path's factor is n x k with n >= k)
-    if (lda < (m > 1 ? m : 1)) return -5;
-    if (VT != nullptr && ldvt < (n64 > 1 ? n64 : 1)) return -8;   // VT == nullptr: singular values and left vectors only
+int gesvdj_core(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T* VT, int64_t ldvt,
+                int* sweeps_host) {
     if (sweeps_host) *sweeps_host = 0;
     if (n64 == 0) return 0;
     const int n = (int)n64;
@@ -1055,7 +1050,9 @@ int gesvdj(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T* VT,
         // fp32 problems run the fp64 kernels on a widened copy.  Short factors (the k x k matrix of an fp32 RSVD / ABRIK tail) then get the
         // LDS-resident block Jacobi (3.5 ms at n = 256 against 25 ms for 255 per-round launches x ~11 sweeps), and tall ones lose the
         // drift of thousands of fp32 rotations (measured at 3000 x 256: ||V^T V - I|| = 7e3 eps32 in fp32 arithmetic, 5 eps32 widened).
-        if (n > 1) {
+        // A single column goes the same way: its norm is then summed in fp64.
+        {
+            c->path_count[25]++;
             size_t mk = rlhip_ws_mark(c);
             double* Ad = ws_alloc<double>(c, (size_t)m * n);
             double* Sd = ws_alloc<double>(c, (size_t)n);
@@ -1063,7 +1060,7 @@ int gesvdj(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T* VT,
             if (!Ad || !Sd || (VT != nullptr && !VTd)) { rlhip_ws_release(c, mk); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
             const unsigned gA = (unsigned)((m * n + 255) / 256), gV = (unsigned)(((int64_t)n * n + 255) / 256);
             hipLaunchKernelGGL((convert_kernel<float, double>), dim3(gA), dim3(256), 0, c->stream, m, (int64_t)n, A, lda, Ad, m);
-            int info = gesvdj<double>(c, m, n64, Ad, m, Sd, VTd, (int64_t)n, sweeps_host);
+            int info = gesvdj_core<double>(c, m, n64, Ad, m, Sd, VTd, (int64_t)n, sweeps_host);
             if (info >= 0) {
                 hipLaunchKernelGGL((convert_kernel<double, float>), dim3(gA), dim3(256), 0, c->stream, m, (int64_t)n, Ad, m, A, lda);
                 hipLaunchKernelGGL((convert_kernel<double, float>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (int64_t)n, (int64_t)1, Sd, (int64_t)n, S, (int64_t)n);
@@ -1102,12 +1099,15 @@ int gesvdj(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T* VT,
             }
         }
         if (done || sweep >= max_sweeps) rc = 0;
+        else c->path_count[m > JM ? 22 : (jb_sel == 32 || n <= 32) ? 23 : 21]++;
+        if (done || sweep >= max_sweeps) rc = 0;
         else if (m > JM) rc = block_jacobi_sweeps<T, 16, 2 * JM>(c, (int)m, n, A, lda, V, tol, d_nrot, max_sweeps, &sweep);   // 257 .. 512 rows: 32 x 512 panel = 128 KiB
         else if (jb_sel == 32 || n <= 32) rc = block_jacobi_sweeps<T, 32, JM>(c, (int)m, n, A, lda, V, tol, d_nrot, max_sweeps, &sweep);
         else rc = block_jacobi_sweeps<T, 16, JM>(c, (int)m, n, A, lda, V, tol, d_nrot, max_sweeps, &sweep);
         if (rc) { rlhip_ws_release(c, mark); return rc; }
         if (sweep >= max_sweeps) info = 1;
     } else if (n > 1) {
+        c->path_count[24]++;
         for (; sweep < max_sweeps; ++sweep) {
             hipLaunchKernelGGL(zero_u32_kernel, dim3(1), dim3(1), 0, c->stream, d_nrot);
             for (int round = 0; round < N - 1; ++round) {
@@ -1133,6 +1133,29 @@ int gesvdj(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T* VT,
     return rc ? rc : info;
 }
 
+// the public entry: LAPACK's argument order for the codes, then the exponent-range guard (qrcp.hip: svd_guard_begin) around the sweeps
+template <typename T>
+int gesvdj(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* VT, int64_t ldvt, int* sweeps_host) {
+    if (m < 0) return -2;
+    if (n < 0) return -3;
+    if (m < n) return -2;  // tall only (the path's factor is n x k with n >= k)
+    if (lda < (m > 1 ? m : 1)) return -5;
+    if (VT != nullptr && ldvt < (n > 1 ? n : 1)) return -8;   // VT == nullptr: singular values and left vectors only
+    if (sweeps_host) *sweeps_host = 0;
+    if (n == 0) return 0;
+    size_t mark = rlhip_ws_mark(c);
+    unsigned long long* w = ws_alloc<unsigned long long>(c, 4);
+    if (!w) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    int rc = svd_guard_begin<T>(c, m, n, A, lda, w);
+    int info = 0;
+    if (!rc) info = gesvdj_core<T>(c, m, n, A, lda, S, VT, ldvt, sweeps_host);
+    if (!rc && info >= 0) rc = svd_guard_end<T>(c, n, S, w);
+    rlhip_ws_release(c, mark);
+    return rc ? rc : info;
+}
+
+template int gesvdj_core<double>(rlhip_ctx*, int64_t, int64_t, double*, int64_t, double*, double*, int64_t, int*);
+template int gesvdj_core<float>(rlhip_ctx*, int64_t, int64_t, float*, int64_t, float*, float*, int64_t, int*);
 template int gesvdj<double>(rlhip_ctx*, int64_t, int64_t, double*, int64_t, double*, double*, int64_t, int*);
 template int gesvdj<float>(rlhip_ctx*, int64_t, int64_t, float*, int64_t, float*, float*, int64_t, int*);
 

@@ -1003,15 +1003,17 @@ __global__ __launch_bounds__(256) void geqrf_absmax_kernel(int64_t m, int64_t n,
         if (b) atomicMax(w, b);
     }
 }
-// the scale this matrix needs (1 inside the safe window, and for zero / non-finite matrices)
-template <typename T>
-__device__ __forceinline__ double geqrf_scale_of(const unsigned long long* w) {
+// the scale this matrix needs (1 inside the safe window (lo, hi), and for zero / non-finite matrices)
+__device__ __forceinline__ double range_scale_of(const unsigned long long* w, const double lo, const double hi) {
     const double mx = __longlong_as_double((long long)w[0]);
-    const double hi = (sizeof(T) == 8) ? 1e149 : 2.8e14, lo = (sizeof(T) == 8) ? 1e-149 : 7e-15;
     if (!(mx > 0.0) || !(mx < 1.7e308) || (mx < hi && mx > lo)) return 1.0;
     int ex = 0;
     (void)frexp(mx, &ex);
     return ldexp(1.0, 1 - ex);
+}
+template <typename T>
+__device__ __forceinline__ double geqrf_scale_of(const unsigned long long* w) {
+    return range_scale_of(w, (sizeof(T) == 8) ? 1e-149 : 7e-15, (sizeof(T) == 8) ? 1e149 : 2.8e14);
 }
 // A *= s (back = 0: the whole matrix) or A(i <= j) /= s (back = 1: the R part of the result) -- and A(i >= tail, j >= tail) /= s, the trailing block
 // a partial factorization leaves (tail = min(m, n) selects nothing more)
@@ -1025,6 +1027,42 @@ __global__ __launch_bounds__(256) void geqrf_rescale_kernel(int64_t m, int64_t n
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256)
             if (!back || i <= j || (i >= tail && j >= tail)) A[i + j * lda] = (T)((double)A[i + j * lda] * f);
 }
+
+// ---- the same guard for the SVDs (jacobi.hip, svd.hip).  Their window is narrower than geqrf's: the Gram route sweeps A^T A, whose squared
+// column norms are sigma^4 and whose rotation test multiplies two of them, and an fp32 gesdd forms A^T A in fp32.  With max |a_ij| inside
+// (1e-30, 1e30) in fp64 / (1e-10, 1e10) in fp32 and sigma_1 <= sqrt(m n) max |a_ij| every one of those products stays normal.
+template <typename T>
+__global__ __launch_bounds__(256) void svd_rescale_kernel(int64_t m, int64_t n, T* __restrict__ A, int64_t lda, const unsigned long long* __restrict__ w, int back) {
+    const double s = range_scale_of(w, (sizeof(T) == 8) ? 1e-30 : 1e-10, (sizeof(T) == 8) ? 1e30 : 1e10);
+    if (s == 1.0) return;
+    const double f = back ? 1.0 / s : s;               // (a power of two: exact both ways)
+    for (int64_t j = blockIdx.y; j < n; j += gridDim.y)
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) A[i + j * lda] = (T)((double)A[i + j * lda] * f);
+}
+// A <- s A with s = 1 inside the window, else the power of two that brings max |a_ij| into [1, 2); w (4 device words) keeps max |a_ij| for svd_guard_end
+template <typename T>
+int svd_guard_begin(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, unsigned long long* w) {
+    int64_t bx = (m + 1023) / 1024, by = n;               // (the launch shape of geqrf's guard)
+    if (bx > 64) bx = 64;
+    if (by > 1024 / bx) by = 1024 / bx;
+    const dim3 blocks((unsigned)bx, (unsigned)(by < 1 ? 1 : by));
+    RLHIP_CHECK(hipMemsetAsync(w, 0, sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(geqrf_absmax_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, (const T*)A, lda, w);
+    hipLaunchKernelGGL(svd_rescale_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w, 0);
+    RLHIP_LAUNCH_CHECK();
+    return 0;
+}
+// S <- S / s: the singular values get the scale back (U and VT do not depend on it)
+template <typename T>
+int svd_guard_end(rlhip_ctx* c, int64_t n, T* S, const unsigned long long* w) {
+    hipLaunchKernelGGL(svd_rescale_kernel<T>, dim3((unsigned)((n + 1023) / 1024 > 64 ? 64 : (n + 1023) / 1024), 1), dim3(256), 0, c->stream, n, (int64_t)1, S, n, w, 1);
+    RLHIP_LAUNCH_CHECK();
+    return 0;
+}
+template int svd_guard_begin<double>(rlhip_ctx*, int64_t, int64_t, double*, int64_t, unsigned long long*);
+template int svd_guard_begin<float>(rlhip_ctx*, int64_t, int64_t, float*, int64_t, unsigned long long*);
+template int svd_guard_end<double>(rlhip_ctx*, int64_t, double*, const unsigned long long*);
+template int svd_guard_end<float>(rlhip_ctx*, int64_t, float*, const unsigned long long*);
 
 template <typename T>
 int geqrf_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev);

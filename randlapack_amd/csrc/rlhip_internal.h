@@ -56,6 +56,7 @@
 
 // Execution context: one HIP stream + a growable device scratch arena + a small
 // pinned host mailbox for info codes / scalars coming back from the device.
+constexpr int RLHIP_NPATH = 32;          // slots of rlhip_path_count (indices: include/rlhip.h)
 struct rlhip_ctx {
     int device = 0;
     int num_cu = 256;            // compute units of THIS context's device (persistent kernels size their grids with it)
@@ -109,7 +110,7 @@ struct rlhip_ctx {
     // diagnostics: how often each specialised kernel path was taken (rlhip_path_count; tests assert the path under test ran)
     //   0 stream-K f64 GEMM, 1 stream-K f32 GEMM, 2 fused trsm block kernel, 3 substitution trsm sub-block, 4 fused out-of-place trsm
     //   (rlhip_trsm_gather), 5 sketch-preconditioned Cholesky-QR panel inside geqrf -- the list in include/rlhip.h is the contract
-    int64_t path_count[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t path_count[RLHIP_NPATH] = {};
 };
 
 // every host wait of the library goes through here: the epoch lets deferred read-backs know that an earlier wait already covered them
@@ -191,6 +192,16 @@ template <typename T>
 int gesvdj(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* VT, int64_t ldvt,
            int* sweeps_host);
 
+
+// gesvdj without the argument checks and the exponent-range guard (the caller has done both): what gesdd_tall runs on its own factors
+template <typename T>
+int gesvdj_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* VT, int64_t ldvt, int* sweeps_host);
+// exponent-range guard of the SVDs (qrcp.hip, beside geqrf's): begin scales A by a power of two when max |a_ij| lies outside the safe
+// window and leaves the measurement in w (4 device words); end gives the n singular values their scale back.  No host read.
+template <typename T>
+int svd_guard_begin(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, unsigned long long* w);
+template <typename T>
+int svd_guard_end(rlhip_ctx* c, int64_t n, T* S, const unsigned long long* w);
 
 // A[i,i] += alpha
 template <typename T>

@@ -233,14 +233,12 @@ int gesdd_tall_gram(rlhip_ctx* c, int64_t m, int64_t n, const T* A, int64_t lda,
     }
 }
 
+// the routes behind gesdd_tall's argument checks and exponent-range guard.  Path counters (include/rlhip.h), one per call on the branch
+// taken: 10 Gram route; 16 Cholesky-QR twice; 17 one pass; 18 V recovered instead of accumulated (beside 16 or 17); 19 Jacobi on A after
+// the first factorization failed or its diagonal ratio reached the limit; 20 Jacobi on A after the second one failed and pass 1 was undone.
 template <typename T>
-int gesdd_tall(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* U, int64_t ldu, T* VT, int64_t ldvt,
-               int* sweeps_host) {
-    if (m < 0) return -2;
-    if (n < 0) return -3;
-    if (m < n) return -2;
-    if (sweeps_host) *sweeps_host = 0;
-    if (n == 0) return 0;
+static int gesdd_tall_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* U, int64_t ldu, T* VT, int64_t ldvt,
+                           int* sweeps_host) {
     {
         const int grc = gesdd_tall_gram<T>(c, m, n, A, lda, S, U, ldu, VT, ldvt, sweeps_host);
         if (grc <= 0) return grc;
@@ -269,6 +267,7 @@ int gesdd_tall(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* U
         const double lim = (sizeof(T) == 8) ? 1e7 : 1e3;
         if (!(ratio < lim)) fallback = true;
     }
+    if (fallback) c->path_count[19]++;
     bool one_pass = false;
     if (!fallback) {
         rc = trsm_right_upper<T>(c, NonUnit, m, n, T(1), R1, n, A, lda);
@@ -301,12 +300,13 @@ int gesdd_tall(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* U
             rc = trmm_right_upper<T>(c, NonUnit, m, n, T(1), R1, n, A, lda);
             if (rc) { rlhip_ws_release(c, mark); return rc; }
             fallback = true;
+            c->path_count[20]++;
         }
     }
     if (fallback) {
         // Jacobi on A directly: A -> U_A, then copy out
         int sw = 0;
-        int jinfo = gesvdj<T>(c, m, n, A, lda, S, VT, ldvt, &sw);
+        int jinfo = gesvdj_core<T>(c, m, n, A, lda, S, VT, ldvt, &sw);
         if (sweeps_host) *sweeps_host = sw;
         if (jinfo < 0) { rlhip_ws_release(c, mark); return jinfo; }
         rc = lacpy<T>(c, 2, m, n, A, lda, U, ldu);
@@ -335,7 +335,9 @@ int gesdd_tall(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* U
         if (rc) { rlhip_ws_release(c, mark); return rc; }
         recover_v = ((double)nr * (double)ni < ((sizeof(T) == 8) ? 1e3 : 30.0));
     }
-    int jinfo = gesvdj<T>(c, n, n, X, n, S, recover_v ? (T*)nullptr : VTx, n, &sw);   // X = Ux S VTx
+    c->path_count[one_pass ? 17 : 16]++;
+    if (recover_v) c->path_count[18]++;
+    int jinfo = gesvdj_core<T>(c, n, n, X, n, S, recover_v ? (T*)nullptr : VTx, n, &sw);   // X = Ux S VTx
     if (sweeps_host) *sweeps_host = sw;
     if (jinfo < 0) { rlhip_ws_release(c, mark); return jinfo; }
     if (recover_v) {
@@ -354,6 +356,31 @@ int gesdd_tall(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* U
     if (!rc) rc = transpose<T>(c, n, n, X, n, VT, ldvt, 0);
     rlhip_ws_release(c, mark);
     return rc ? rc : jinfo;
+}
+
+// the public entry: LAPACK's argument positions of gesdd(jobz, m, n, A, lda, S, U, ldu, VT, ldvt) for the codes -- nothing is enqueued before
+// they pass -- then the exponent-range guard (qrcp.hip: svd_guard_begin): A is scaled by a power of two when max |a_ij| lies outside the
+// window, every route below then sees entries of order 1, and S gets the scale back exactly; U and VT do not depend on it.
+template <typename T>
+int gesdd_tall(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* U, int64_t ldu, T* VT, int64_t ldvt,
+               int* sweeps_host) {
+    if (m < 0) return -2;
+    if (n < 0) return -3;
+    if (m < n) return -2;
+    if (lda < (m > 1 ? m : 1)) return -5;
+    if (ldu < (m > 1 ? m : 1)) return -8;
+    if (ldvt < (n > 1 ? n : 1)) return -10;
+    if (sweeps_host) *sweeps_host = 0;
+    if (n == 0) return 0;
+    size_t mark = rlhip_ws_mark(c);
+    unsigned long long* w = ws_alloc<unsigned long long>(c, 4);
+    if (!w) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    int rc = svd_guard_begin<T>(c, m, n, A, lda, w);
+    int info = 0;
+    if (!rc) info = gesdd_tall_core<T>(c, m, n, A, lda, S, U, ldu, VT, ldvt, sweeps_host);
+    if (!rc && info >= 0) rc = svd_guard_end<T>(c, n, S, w);
+    rlhip_ws_release(c, mark);
+    return rc ? rc : info;
 }
 
 template int transpose<double>(rlhip_ctx*, int64_t, int64_t, const double*, int64_t, double*, int64_t, int);
