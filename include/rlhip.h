@@ -505,8 +505,13 @@ int rlhip_allreduce_sum_host_f64(rlhip_ctx* ctx, double* x_host, int64_t n);   /
  * the first factorization failed or its diagonal ratio reached the limit, 20 Jacobi on A after the second factorization failed and the
  * first pass was undone.  The sweep driver of a one-sided Jacobi (jacobi.hip::gesvdj, beside 6): 21 LDS-resident blocks of 16 columns x 256
  * rows, 22 of 16 x 512 rows, 23 of 32 columns x 256 rows, 24 one launch per round (more than 512 rows), 25 an fp32 problem run in fp64
- * (counted beside the driver it then takes).  26 .. 31 are free.  -1 for an unknown index.  Tests use it to
- * assert that the kernel / route under test is the one that ran. */
+ * (counted beside the driver it then takes).  The routes of a product that is not the persistent kernel's (gemm.hip::gemm_impl, counted on
+ * the host where the launch is enqueued; 0 and 1 are the persistent ones): 26 a launch of the tiled kernel (gemm_kernel), 27 a tiled launch
+ * that went split-K (slabs + splitk_reduce_kernel; counted beside 26), 28 the small-product kernel (gemm_small_kernel), 29 the narrow-panel
+ * kernel (gemm_tn_skinny_kernel), 30 scale-only calls (k == 0 or alpha == 0: C = beta C, also counted for beta == 1, which launches nothing),
+ * 31 a contraction cut in two or more calls by gemm_impl itself (the k-remainder peel, the fp32 chunks of 16384 and their Gram twin; the
+ * pieces count their own routes), 32 a product whose last m % 128 rows were peeled off a persistent launch and given to another route.
+ * -1 for an unknown index.  Tests use it to assert that the kernel / route under test is the one that ran. */
 int64_t rlhip_path_count(rlhip_ctx* ctx, int which);
 /* the host layers above this ABI (include/RandLAPACK_amd/) report their own route decisions into the same counters */
 int rlhip_path_note(rlhip_ctx* ctx, int which, int64_t delta);

@@ -460,11 +460,12 @@ __global__ __launch_bounds__(256) void gemm_tn_skinny_kernel(int m, int n, int64
 }
 
 template <typename T>
-__global__ void scale_kernel(int64_t M, int64_t N, T beta, T* __restrict__ C, int64_t ldc) {
+__global__ void scale_kernel(int64_t M, int64_t N, T beta, T* __restrict__ C, int64_t ldc, int tri) {
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t total = M * N;
     for (; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
         int64_t i = idx % M, j = idx / M;
+        if (tri && i > j) continue;                                   // syrk with k == 0 or alpha == 0: the strictly lower triangle is not touched either
         C[i + j * ldc] = (beta == T(0)) ? T(0) : beta * C[i + j * ldc];
     }
 }
@@ -629,8 +630,10 @@ int gemm_dispatch(rlhip_ctx* c, GemmArgs<T> g, int tri) {
         default: rc = launch_cfg<T, A_KC, B_KC, 256, 16, BK, 64, 16, 2, false>(c, g, vec, splitk); break;
     }
     if (rc) { rlhip_ws_release(c, mark); return rc; }
+    c->path_count[26]++;
 
     if (splitk > 1) {
+        c->path_count[27]++;
         int64_t total = M * N;
         int blocks = (int)((4 * total + 255) / 256);                 // four lanes per entry
         if (blocks > 8192) blocks = 8192;
@@ -697,6 +700,7 @@ static int gemm_tn_skinny(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, T alpha
     }
     rlhip_ws_release(c, mark);
     if (le != hipSuccess) return RLHIP_ERR_HIP(le);
+    c->path_count[29]++;
     return 1;
 }
 
@@ -709,11 +713,12 @@ int gemm_impl(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_
     if (k < 0) return -5;
     if (m == 0 || n == 0) return 0;
     if (k == 0 || alpha == T(0)) {
+        c->path_count[30]++;                                          // (counted with beta == 1 too, where nothing is launched)
         if (beta == T(1)) return 0;
         int64_t total = m * n;
         int blocks = (int)((total + 255) / 256);
         if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(scale_kernel<T>, dim3(blocks), dim3(256), 0, c->stream, m, n, beta, C, ldc);
+        hipLaunchKernelGGL(scale_kernel<T>, dim3(blocks), dim3(256), 0, c->stream, m, n, beta, C, ldc, tri);
         RLHIP_LAUNCH_CHECK();
         return 0;
     }
@@ -730,6 +735,7 @@ int gemm_impl(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_
     constexpr int64_t SKK = (sizeof(T) == 8) ? 16 : 32;      // K-tile of the persistent kernel (128 bytes per row)
     if (!transB && k % SKK != 0 && k >= 1024 && n % 256 == 0 && !ssqA_dev && (tri ? (m == n) : (m >= 128))) {
         const int64_t k_main = (k / SKK) * SKK;
+        c->path_count[31]++;
         int rc = gemm_impl<T>(c, transA, transB, m, n, k_main, alpha, A, lda, B, ldb, beta, C, ldc, tri, nullptr, nullptr);
         if (rc) return rc;
         const T* A2 = transA ? (A + k_main) : (A + k_main * lda);
@@ -741,6 +747,7 @@ int gemm_impl(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_
     if (sizeof(T) == 4 && !tri && !transB && k > 16384 && k % SKK == 0 && m >= 128 && n % 256 == 0 && !ssqA_dev) {
         {
             const int64_t KC = 16384;
+            c->path_count[31]++;
             for (int64_t k0 = 0; k0 < k; k0 += KC) {
                 const int64_t kc = (k - k0 < KC) ? (k - k0) : KC;
                 const T* Ac = transA ? (A + k0) : (A + k0 * lda);
@@ -755,6 +762,7 @@ int gemm_impl(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_
     // contraction (its single fp32 chain per entry), the whole Gram matrix went to the tiled kernel: 3.6 ms for 1.5 ms of MFMA work
     if (sizeof(T) == 4 && tri && !transB && m == n && n % 256 == 0 && k > 16384 && k % SKK == 0) {
         const int64_t KC = 16384;
+        c->path_count[31]++;
         for (int64_t k0 = 0; k0 < k; k0 += KC) {
             const int64_t kc = (k - k0 < KC) ? (k - k0) : KC;
             const T* Ac = transA ? (A + k0) : (A + k0 * lda);
@@ -780,6 +788,7 @@ int gemm_impl(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_
         if (rc == 1) {
             if (ssqA_dev && ssq_done) *ssq_done = (m_main == m) ? 2 : 1;   // 1: covers op(A)'s first (m / 128) * 128 rows, the caller adds the peeled block; 2: all of it
             if (m_main == m) return 0;
+            c->path_count[32]++;
             const T* A2 = transA ? (A + m_main * lda) : (A + m_main);
             return gemm_impl<T>(c, transA, transB, m - m_main, n, k, alpha, A2, lda, B, ldb, beta, C + m_main, ldc, 0,
                                 nullptr, nullptr);
@@ -791,6 +800,7 @@ int gemm_impl(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_
             hipLaunchKernelGGL(gemm_small_kernel<T>, dim3((unsigned)((m + 31) / 32), (unsigned)((n + 31) / 32)), dim3(256), 0, c->stream, (int)m, (int)n, (int)k, alpha, A,
                                transA ? lda : (int64_t)1, transA ? (int64_t)1 : lda, B, transB ? ldb : (int64_t)1, transB ? (int64_t)1 : ldb, beta, C, ldc);
             RLHIP_LAUNCH_CHECK();
+            c->path_count[28]++;
             return 0;
         }
     }
