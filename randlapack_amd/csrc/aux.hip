@@ -142,8 +142,8 @@ int lange_fro(rlhip_ctx* c, int64_t m, int64_t n, const T* A, int64_t lda, T* re
     // of the 20000 x 256 factor B^T of the RSVD tail)
     if ((int64_t)grid.x * grid.y > 2048) grid.y = (unsigned)(2048 / grid.x < 1 ? 1 : 2048 / grid.x);
     int np = (int)(grid.x * grid.y);
-    size_t mark = rlhip_ws_mark(c);
-    double* partial = ws_alloc<double>(c, np);
+    ws_scope ws(c);
+    double* partial = ws.alloc<double>(np);
     if (!partial) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     hipLaunchKernelGGL(ssq_partial_kernel<T>, grid, dim3(256), 0, c->stream, m, n, A, lda, partial);
     RLHIP_LAUNCH_CHECK();
@@ -164,18 +164,16 @@ int lange_fro(rlhip_ctx* c, int64_t m, int64_t n, const T* A, int64_t lda, T* re
         RLHIP_CHECK(rlhip_stream_sync(c));
         double mx;
         memcpy(&mx, c->h_mail + 1, sizeof(double));
-        if (mx != mx || mx > 1.7e308) { rlhip_ws_release(c, mark); *result_host = (T)mx; return 0; }     // NaN / inf entries: that is the norm
-        if (mx == 0.0) { rlhip_ws_release(c, mark); *result_host = T(0); return 0; }
+        if (mx != mx || mx > 1.7e308) { *result_host = (T)mx; return 0; }     // NaN / inf entries: that is the norm
+        if (mx == 0.0) { *result_host = T(0); return 0; }
         hipLaunchKernelGGL(ssq_scaled_partial_kernel<T>, grid, dim3(256), 0, c->stream, m, n, A, lda, mx, partial);
         hipLaunchKernelGGL(ssq_final_kernel, dim3(1), dim3(256), 0, c->stream, np, partial, d_out);
         RLHIP_LAUNCH_CHECK();
         RLHIP_CHECK(hipMemcpyAsync(c->h_mail, d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
-        rlhip_ws_release(c, mark);
         *result_host = (T)(mx * sqrt(*(double*)c->h_mail));
         return 0;
     }
-    rlhip_ws_release(c, mark);
     *result_host = (T)sqrt(ssq);
     return 0;
 }

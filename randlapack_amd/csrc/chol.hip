@@ -297,32 +297,33 @@ int potrf_upper(rlhip_ctx* c, int64_t n, T* A, int64_t lda, int* info_host) {
         //                         RIGHT-side solve of the transposed slab on the blocked trsm of tri.hip, between two transposes),
         //   trailing update     : A22 -= U12^T U12 with K = 256 on the MFMA tri-tile GEMM.
         constexpr int64_t BS = 256;
-        const size_t mark = rlhip_ws_mark(c);
-        T* UT = ws_alloc<T>(c, (size_t)BS * BS);                 // U11^T of the current step (chol_rowsolve_kernel)
-        if (!UT) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
-        RLHIP_FUNC_LDS(c, potrf_small_kernel<T>, 150 * 1024);
-        hipLaunchKernelGGL(zero_int_kernel, dim3(1), dim3(1), 0, c->stream, d_info);
         int rc = 0;
-        for (int64_t j0 = 0; j0 < n && !rc; j0 += BS) {
-            const int64_t jb = (n - j0 < BS) ? (n - j0) : BS;
-            const int64_t rest = n - j0 - jb;
-            T* A11 = A + j0 + j0 * lda;
-            const size_t smem = (size_t)(32 * 33 + 64 + (size_t)(jb + 16) * PS_LD) * sizeof(T);
-            hipLaunchKernelGGL(potrf_small_kernel<T>, dim3(1), dim3(1024), smem, c->stream, (int)jb, A11, lda, d_info, (int)j0 + 1);
-            RLHIP_LAUNCH_CHECK();
-            if (rest <= 0) break;
-            T* A12 = A + j0 + (j0 + jb) * lda;
-            T* A22 = A + (j0 + jb) + (j0 + jb) * lda;
-            rc = transpose<T>(c, jb, jb, A11, lda, UT, jb, 0);
-            if (!rc) {
-                hipLaunchKernelGGL(chol_rowsolve_kernel<T>, dim3((unsigned)((rest + 3) / 4)), dim3(256), 0, c->stream, (int)jb, rest, (const T*)UT, A12, lda,
-                                   (const int*)d_info);
-                const hipError_t le = hipGetLastError();
-                if (le != hipSuccess) rc = RLHIP_ERR_HIP(le);        // (the arena mark is released below on every path)
+        {
+            ws_scope ws(c);
+            T* UT = ws.alloc<T>((size_t)BS * BS);                 // U11^T of the current step (chol_rowsolve_kernel)
+            if (!UT) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
+            RLHIP_FUNC_LDS(c, potrf_small_kernel<T>, 150 * 1024);
+            hipLaunchKernelGGL(zero_int_kernel, dim3(1), dim3(1), 0, c->stream, d_info);
+            for (int64_t j0 = 0; j0 < n && !rc; j0 += BS) {
+                const int64_t jb = (n - j0 < BS) ? (n - j0) : BS;
+                const int64_t rest = n - j0 - jb;
+                T* A11 = A + j0 + j0 * lda;
+                const size_t smem = (size_t)(32 * 33 + 64 + (size_t)(jb + 16) * PS_LD) * sizeof(T);
+                hipLaunchKernelGGL(potrf_small_kernel<T>, dim3(1), dim3(1024), smem, c->stream, (int)jb, A11, lda, d_info, (int)j0 + 1);
+                RLHIP_LAUNCH_CHECK();
+                if (rest <= 0) break;
+                T* A12 = A + j0 + (j0 + jb) * lda;
+                T* A22 = A + (j0 + jb) + (j0 + jb) * lda;
+                rc = transpose<T>(c, jb, jb, A11, lda, UT, jb, 0);
+                if (!rc) {
+                    hipLaunchKernelGGL(chol_rowsolve_kernel<T>, dim3((unsigned)((rest + 3) / 4)), dim3(256), 0, c->stream, (int)jb, rest, (const T*)UT, A12, lda,
+                                       (const int*)d_info);
+                    const hipError_t le = hipGetLastError();
+                    if (le != hipSuccess) rc = RLHIP_ERR_HIP(le);
+                }
+                if (!rc) rc = gemm_impl<T>(c, 1, 0, rest, rest, jb, T(-1), A12, lda, A12, lda, T(1), A22, lda, 1);
             }
-            if (!rc) rc = gemm_impl<T>(c, 1, 0, rest, rest, jb, T(-1), A12, lda, A12, lda, T(1), A22, lda, 1);
         }
-        rlhip_ws_release(c, mark);
         if (rc) return rc;
         RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 8, d_info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));

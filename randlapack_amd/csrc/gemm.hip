@@ -604,10 +604,10 @@ int gemm_dispatch(rlhip_ctx* c, GemmArgs<T> g, int tri) {
     g.kchunk = kchunk;
     g.tri = tri;
 
-    size_t mark = rlhip_ws_mark(c);
+    ws_scope ws(c);
     T alpha = g.alpha, beta = g.beta;
     if (splitk > 1) {
-        g.slab = ws_alloc<T>(c, (size_t)splitk * M * N);
+        g.slab = ws.alloc<T>((size_t)splitk * M * N);
         if (!g.slab) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     } else {
         g.slab = nullptr;
@@ -629,7 +629,7 @@ int gemm_dispatch(rlhip_ctx* c, GemmArgs<T> g, int tri) {
         case 3: rc = launch_cfg<T, A_KC, B_KC, 256, 32, BK, 64, 32, 2, false>(c, g, vec, splitk); break;
         default: rc = launch_cfg<T, A_KC, B_KC, 256, 16, BK, 64, 16, 2, false>(c, g, vec, splitk); break;
     }
-    if (rc) { rlhip_ws_release(c, mark); return rc; }
+    if (rc) return rc;
     c->path_count[26]++;
 
     if (splitk > 1) {
@@ -641,7 +641,6 @@ int gemm_dispatch(rlhip_ctx* c, GemmArgs<T> g, int tri) {
                            g.slab, alpha, beta, g.C, g.ldc, tri, (int)bm);
         RLHIP_LAUNCH_CHECK();
     }
-    rlhip_ws_release(c, mark);
     return 0;
 }
 
@@ -676,9 +675,9 @@ static int gemm_tn_skinny(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, T alpha
     int64_t G = 2 * (int64_t)c->num_cu;
     if (G > nslab) G = nslab;
     { const int64_t per = (nslab + G - 1) / G; G = (nslab + per - 1) / per; }
-    size_t mark = rlhip_ws_mark(c);
-    T* slab = ws_alloc<T>(c, (size_t)G * m * n);
-    if (!slab) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* slab = ws.alloc<T>((size_t)G * m * n);
+    if (!slab) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     hipError_t le = hipSuccess;
 #define RLHIP_TN_LAUNCH(NA, NB_, SM)                                                                                                  \
     do {                                                                                                                              \
@@ -698,7 +697,6 @@ static int gemm_tn_skinny(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, T alpha
         hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3(blocks), dim3(256), 0, c->stream, m, n, (int)G, (const T*)slab, alpha, beta, C, ldc, tri, 0);
         le = hipGetLastError();
     }
-    rlhip_ws_release(c, mark);
     if (le != hipSuccess) return RLHIP_ERR_HIP(le);
     c->path_count[29]++;
     return 1;

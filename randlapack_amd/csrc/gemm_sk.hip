@@ -624,13 +624,13 @@ int gemm_streamk(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int
     // transposed product: groups of 8 walk their K range 16 tiles apart (see `rot` in the kernel).  Interleaved A/B at C2, best of 4 / median,
     // ms: groups of 2 in phase (round 3) 31.64 / 33.1;  8 in phase 32.1;  8 staggered by 16: 30.87 / 31.6;  4 by 8: 30.85 / 31.6;  8 by 64: 32.2
     g.stag = (transA && g.gs > 1) ? (tune[3] >= 0 ? tune[3] : 16) : 0;
-    size_t mark = rlhip_ws_mark(c);
-    g.slab = ws_alloc<T>(c, (size_t)2 * P * SLAB_ELEMS);
+    ws_scope ws(c);
+    g.slab = ws.alloc<T>((size_t)2 * P * SLAB_ELEMS);
     if (!g.slab) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
-    g.ssq_part = ssqA_dev ? ws_alloc<double>(c, (size_t)P) : nullptr;
+    g.ssq_part = ssqA_dev ? ws.alloc<double>((size_t)P) : nullptr;
     static int want_clk = -1;
     if (want_clk < 0) { const char* e = getenv("RLHIP_SK_CLOCK"); want_clk = e ? atoi(e) : 0; }
-    g.clk = want_clk ? ws_alloc<unsigned long long>(c, 4) : nullptr;
+    g.clk = want_clk ? ws.alloc<unsigned long long>(4) : nullptr;
     constexpr int smem = NSTAGE * STAGE;
     // 32-bit byte offsets for the DMA pieces when the 256 rows a stage takes from either operand span < 4 GiB (ld < 2 M doubles / 4 M floats)
     const int64_t span = (int64_t)sizeof(T) * (256 * (lda > ldb ? lda : ldb) + 512);
@@ -665,7 +665,6 @@ int gemm_streamk(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int
             fprintf(stderr, "[sk clock] %s m %lld n %lld k %lld: %.1f us at %.0f MHz\n", transA ? "TN" : "NN", (long long)m, (long long)n, (long long)k,
                     (double)(h[3] - h[1]) / 100.0, (double)(h[2] - h[0]) / ((double)(h[3] - h[1]) / 100.0));
     }
-    rlhip_ws_release(c, mark);
     c->path_count[sizeof(T) == 8 ? 0 : 1]++;
     return 1;
 }

@@ -199,8 +199,8 @@ int orhr_col(rlhip_ctx* c, int64_t m, int64_t n, int64_t nb, T* A, int64_t lda, 
     hipLaunchKernelGGL(tfac_init_kernel<T>, dim3((unsigned)((nb * n + 255) / 256)), dim3(256), 0, c->stream, n, nb, A, lda, D,
                        Tm, ldt);
     RLHIP_LAUNCH_CHECK();
-    size_t mark = rlhip_ws_mark(c);
-    T* Lt = ws_alloc<T>(c, (size_t)nb * nb);
+    ws_scope ws(c);
+    T* Lt = ws.alloc<T>((size_t)nb * nb);
     if (!Lt) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     for (int64_t jb0 = 0; jb0 < n; jb0 += nb) {
         const int64_t jnb = (n - jb0 < nb) ? (n - jb0) : nb;
@@ -208,9 +208,8 @@ int orhr_col(rlhip_ctx* c, int64_t m, int64_t n, int64_t nb, T* A, int64_t lda, 
                            A + jb0 + jb0 * lda, lda, Lt, 1);   // Lt = V1^T (unit upper)
         RLHIP_LAUNCH_CHECK();
         int rc = trsm_right_upper<T>(c, 1, jnb, jnb, T(1), Lt, jnb, Tm + jb0 * ldt, ldt);
-        if (rc) { rlhip_ws_release(c, mark); return rc; }
+        if (rc) return rc;
     }
-    rlhip_ws_release(c, mark);
     return 0;
 }
 
@@ -252,11 +251,11 @@ int gemqrt_lt(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, int64_t nb, const T
     if (nb < 1) return -6;
     if (k == 0 || n == 0 || m == 0) return 0;
     if (nb > k) nb = k;
-    size_t mark = rlhip_ws_mark(c);
-    T* V1 = ws_alloc<T>(c, (size_t)nb * nb);
-    T* W = ws_alloc<T>(c, (size_t)nb * n);
-    T* W2 = ws_alloc<T>(c, (size_t)nb * n);
-    if (!V1 || !W || !W2) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* V1 = ws.alloc<T>((size_t)nb * nb);
+    T* W = ws.alloc<T>((size_t)nb * n);
+    T* W2 = ws.alloc<T>((size_t)nb * n);
+    if (!V1 || !W || !W2) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     int rc = 0;
     for (int64_t i = 0; i < k && !rc; i += nb) {
         const int64_t ib = (k - i < nb) ? (k - i) : nb;
@@ -275,7 +274,6 @@ int gemqrt_lt(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, int64_t nb, const T
         if (!rc) rc = gemm<T>(c, 0, 0, ib, n, ib, T(-1), V1, ib, W2, ib, T(1), Ci, ldc);
         if (!rc && mr > 0) rc = gemm<T>(c, 0, 0, mr, n, ib, T(-1), Vi + ib, ldv, W2, ib, T(1), Ci + ib, ldc);
     }
-    rlhip_ws_release(c, mark);
     return rc;
 }
 
@@ -292,10 +290,10 @@ int gemqrt_lt_head(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, const T* V, in
     if (n < 0) return -4;
     if (k < 0 || k > m) return -5;
     if (k == 0 || n == 0 || m == 0) return 0;
-    size_t mark = rlhip_ws_mark(c);
-    T* V1 = ws_alloc<T>(c, (size_t)k * k);
-    T* W = ws_alloc<T>(c, (size_t)k * n);
-    if (!V1 || !W) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* V1 = ws.alloc<T>((size_t)k * k);
+    T* W = ws.alloc<T>((size_t)k * n);
+    if (!V1 || !W) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     const int64_t mr = m - k;
     hipLaunchKernelGGL(unit_lower_copy_kernel<T>, dim3((unsigned)((k * k + 255) / 256)), dim3(256), 0, c->stream, k, V, ldv, V1, 0);
     int rc = 0;
@@ -307,7 +305,6 @@ int gemqrt_lt_head(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, const T* V, in
     if (!rc && mr > 0) rc = gemm<T>(c, 1, 0, k, n, mr, T(1), V + k, ldv, C + k, ldc, T(1), W, k);
     if (!rc) rc = gemm<T>(c, 1, 0, k, n, k, T(1), Tm, ldt, W, k, T(0), W2, k);
     if (!rc) rc = gemm<T>(c, 0, 0, k, n, k, T(-1), V1, k, W2, k, T(1), C, ldc);
-    rlhip_ws_release(c, mark);
     return rc;
 }
 template <typename T>
@@ -334,11 +331,11 @@ int gemqrt_rn(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, const T* V, int64_t
     if (n < 0) return -4;
     if (k < 0 || k > n) return -5;
     if (k == 0 || n == 0 || m == 0) return 0;
-    size_t mark = rlhip_ws_mark(c);
-    T* V1 = ws_alloc<T>(c, (size_t)k * k);
-    T* W = ws_alloc<T>(c, (size_t)m * k);
-    T* W2 = ws_alloc<T>(c, (size_t)m * k);
-    if (!V1 || !W || !W2) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* V1 = ws.alloc<T>((size_t)k * k);
+    T* W = ws.alloc<T>((size_t)m * k);
+    T* W2 = ws.alloc<T>((size_t)m * k);
+    if (!V1 || !W || !W2) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     hipLaunchKernelGGL(unit_lower_copy_kernel<T>, dim3((unsigned)((k * k + 255) / 256)), dim3(256), 0, c->stream, k, V, ldv, V1, 0);
     RLHIP_LAUNCH_CHECK();
     const int64_t nr = n - k;
@@ -347,7 +344,6 @@ int gemqrt_rn(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, const T* V, int64_t
     if (!rc) rc = gemm<T>(c, 0, 0, m, k, k, T(1), W, m, Tm, ldt, T(0), W2, m);                              // W2 = W T
     if (!rc) rc = gemm<T>(c, 0, 1, m, k, k, T(-1), W2, m, V1, k, T(1), C, ldc);                             // C1 -= W2 V1^T
     if (!rc && nr > 0) rc = gemm<T>(c, 0, 1, m, nr, k, T(-1), W2, m, V + k, ldv, T(1), C + k * ldc, ldc);   // C2 -= W2 V2^T
-    rlhip_ws_release(c, mark);
     return rc;
 }
 template int gemqrt_rn<double>(rlhip_ctx*, int64_t, int64_t, int64_t, const double*, int64_t, const double*, int64_t, double*, int64_t);
@@ -357,15 +353,15 @@ template int gemqrt_rn<float>(rlhip_ctx*, int64_t, int64_t, int64_t, const float
 template <typename T>
 int larft_gram(rlhip_ctx* c, int64_t m, int64_t k, const T* V, int64_t ldv, const T* tau, T* Tm, int64_t ldt) {
     if (k <= 0) return 0;
-    size_t mark = rlhip_ws_mark(c);
-    T* V1 = ws_alloc<T>(c, (size_t)k * k);
-    T* G = ws_alloc<T>(c, (size_t)k * k);
-    if (!V1 || !G) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* V1 = ws.alloc<T>((size_t)k * k);
+    T* G = ws.alloc<T>((size_t)k * k);
+    if (!V1 || !G) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     hipLaunchKernelGGL(unit_lower_copy_kernel<T>, dim3((unsigned)((k * k + 255) / 256)), dim3(256), 0, c->stream, k, V, ldv, V1, 0);
     RLHIP_LAUNCH_CHECK();
     int rc = gemm<T>(c, 1, 0, k, k, k, T(1), V1, k, V1, k, T(0), G, k);
     if (!rc && m > k) rc = gemm<T>(c, 1, 0, k, k, m - k, T(1), V + k, ldv, V + k, ldv, T(1), G, k);
-    if (rc) { rlhip_ws_release(c, mark); return rc; }
+    if (rc) return rc;
     hipLaunchKernelGGL(larft_m_kernel<T>, dim3((unsigned)((k * k + 255) / 256)), dim3(256), 0, c->stream, k, G, k, tau);
     RLHIP_LAUNCH_CHECK();
     rc = laset<T>(c, 2, k, k, T(0), T(1), Tm, ldt);                       // T = I * M^-1
@@ -375,7 +371,6 @@ int larft_gram(rlhip_ctx* c, int64_t m, int64_t k, const T* V, int64_t ldv, cons
         const hipError_t le = hipGetLastError();
         if (le != hipSuccess) rc = RLHIP_ERR_HIP(le);
     }
-    rlhip_ws_release(c, mark);
     return rc;
 }
 
@@ -564,7 +559,7 @@ template <typename T> int geqrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_
 
 // A (m x n, tall) <- its orthonormal factor by Cholesky-QR twice, R2 (n x n, ld n) <- the upper-triangular R with A_in = Q R2; for an
 // ill-conditioned panel once more behind a sparse-sketch preconditioner (below).  *good = false: A holds its input (up to rounding, or bit
-// for bit after the preconditioned attempt) and the caller takes the Householder route.  The caller owns the arena mark.
+// for bit after the preconditioned attempt) and the caller takes the Householder route.  Allocates inside the caller's ws_scope.
 template <typename T>
 static int cholqr_orthonormal(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* R2, bool* good_out) {
     *good_out = false;
@@ -624,20 +619,19 @@ static int cholqr_orthonormal(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t 
 template <typename T>
 int geqrf_cholqr(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau, int* done) {
     *done = 0;
-    size_t mark = rlhip_ws_mark(c);
-    T* R2 = ws_alloc<T>(c, (size_t)n * n);
-    T* Tm = ws_alloc<T>(c, (size_t)n * n);
-    T* D = ws_alloc<T>(c, (size_t)n);
-    if (!R2 || !Tm || !D) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* R2 = ws.alloc<T>((size_t)n * n);
+    T* Tm = ws.alloc<T>((size_t)n * n);
+    T* D = ws.alloc<T>((size_t)n);
+    if (!R2 || !Tm || !D) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     bool good = false;
     int rc = cholqr_orthonormal<T>(c, m, n, A, lda, R2, &good);
-    if (rc) { rlhip_ws_release(c, mark); return rc; }
-    if (!good) { rlhip_ws_release(c, mark); return 0; }                              // let Householder do it
+    if (rc) return rc;
+    if (!good) return 0;                                                             // let Householder do it
     rc = orhr_col<T>(c, m, n, n, A, lda, Tm, n, D);                                  // V below the diagonal, T, sign vector D
     if (!rc) rc = row_sign<T>(c, n, R2, n, D);                                      // R <- D R
     if (!rc) rc = tau_from_t<T>(c, n, n, Tm, n, tau);
     if (!rc) rc = lacpy<T>(c, 0, n, n, R2, n, A, lda);                              // upper triangle incl. diagonal
-    rlhip_ws_release(c, mark);
     if (!rc) *done = 1;
     return rc;
 }
@@ -667,14 +661,14 @@ int geqrf_q(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* R, int64_t
     if (ldr < (n > 1 ? n : 1)) return -7;
     if (n == 0 || m == 0) { *done = 1; return 0; }
     if (!(m >= 2 * n && n >= 8 && (size_t)m * n >= 16384)) return 0;                 // (the shapes the BLAS-3 geqrf serves)
-    size_t mark = rlhip_ws_mark(c);
-    T* R2 = ws_alloc<T>(c, (size_t)n * n);
-    T* Qt = ws_alloc<T>(c, (size_t)n * n);
-    T* D = ws_alloc<T>(c, (size_t)n);
-    if (!R2 || !Qt || !D) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* R2 = ws.alloc<T>((size_t)n * n);
+    T* Qt = ws.alloc<T>((size_t)n * n);
+    T* D = ws.alloc<T>((size_t)n);
+    if (!R2 || !Qt || !D) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     bool good = false;
     int rc = cholqr_orthonormal<T>(c, m, n, A, lda, R2, &good);
-    if (rc || !good) { rlhip_ws_release(c, mark); return rc; }
+    if (rc || !good) return rc;
     rc = lacpy<T>(c, 2, n, n, A, lda, Qt, n);
     if (!rc) rc = lunp_top<T>(c, n, Qt, n, D);                                      // only D is wanted: the sign pattern of the top block's LU
     if (!rc) rc = row_sign<T>(c, n, R2, n, D);                                      // R <- D R
@@ -685,7 +679,6 @@ int geqrf_q(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* R, int64_t
     }
     if (!rc) rc = laset<T>(c, 2, n, n, T(0), T(0), R, ldr);
     if (!rc) rc = lacpy<T>(c, 0, n, n, R2, n, R, ldr);
-    rlhip_ws_release(c, mark);
     if (!rc) *done = 1;
     return rc;
 }

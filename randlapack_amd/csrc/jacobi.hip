@@ -815,8 +815,8 @@ __global__ void gram_offdiag_kernel(int n, const T* __restrict__ G, T tol, unsig
 template <typename T>
 int jacobi_verify_converged(rlhip_ctx* c, int m, int n, const T* A, int64_t lda, T tol, unsigned* d_nrot, bool* ok) {
     *ok = false;
-    size_t gm = rlhip_ws_mark(c);
-    T* G = ws_alloc<T>(c, (size_t)n * n);
+    ws_scope ws(c);
+    T* G = ws.alloc<T>((size_t)n * n);
     unsigned* flag = d_nrot + 1;
     if (G) {
         int grc = gemm<T>(c, 1, 0, n, n, m, T(1), A, lda, A, lda, T(0), G, n);
@@ -831,7 +831,6 @@ int jacobi_verify_converged(rlhip_ctx* c, int m, int n, const T* A, int64_t lda,
             *ok = (*((unsigned*)(c->h_mail + 16) + 1) == 0u);
         }
     }
-    rlhip_ws_release(c, gm);
     return 0;
 }
 
@@ -904,18 +903,18 @@ int persistent_jacobi_sweeps(rlhip_ctx* c, int m, int n, T* A, int64_t lda, T to
     const size_t xwords = (size_t)NBk * JB * m, words = xwords + (size_t)NBk + 8 * (size_t)NW + 1 + (size_t)NW;
     const int hold = jp_hold(c).mode;
     unsigned long long* buf = (unsigned long long*)rlhip_xchg_buffer(c, words * sizeof(unsigned long long));
-    size_t mark = rlhip_ws_mark(c);
-    int* out = ws_alloc<int>(c, 32);
-    if (!buf || !out) { rlhip_ws_release(c, mark); return 1; }
+    ws_scope ws(c);
+    int* out = ws.alloc<int>(32);
+    if (!buf || !out) return 1;
     int sweep = *sweeps_out;
     while (sweep < max_sweeps) {
         JpArgs<T> g;
         g.n = n; g.sweep0 = sweep; g.max_sweeps = max_sweeps; g.A = A; g.lda = lda; g.tol = tol; g.out = out; g.trans_upper = 0; g.skip = nullptr; g.norm_ratio_lim = 0.f;
         const int lrc = jp_launch<T>(c, g, buf, m, NBk);
-        if (lrc) { rlhip_ws_release(c, mark); return lrc; }
+        if (lrc) return lrc;
         hipError_t e2 = hipMemcpyAsync(c->h_mail + 16, out, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
         if (e2 == hipSuccess) e2 = rlhip_stream_sync(c);
-        if (e2 != hipSuccess) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(e2); }
+        if (e2 != hipSuccess) return RLHIP_ERR_HIP(e2);
         const int status = *(int*)(c->h_mail + 16), done_sweeps = *((int*)(c->h_mail + 16) + 1), any_lost = *((int*)(c->h_mail + 16) + 2);
         {
             static int want_clk = -1;
@@ -924,9 +923,9 @@ int persistent_jacobi_sweeps(rlhip_ctx* c, int m, int n, T* A, int64_t lda, T to
             if (want_clk && tk[1]) fprintf(stderr, "[jacobi clock] %d sweeps, %.1f us at %.0f MHz (hold %d, same-XCD hand-over %d)\n", done_sweeps - sweep, (double)tk[1] / 100.0, (double)tk[0] / ((double)tk[1] / 100.0), hold, *((const int*)(c->h_mail + 16) + 3));
         }
         if (*((const int*)(c->h_mail + 16) + 3) == 1) c->path_count[15]++;     // the workers shared one XCD and handed their blocks over through its L2
-        if ((status != 1 && status != 2 && status != 3) || any_lost) { rlhip_ws_release(c, mark); *sweeps_out = sweep; return 1; }   // -7, a lost word anywhere, or nothing written: A untouched by this launch
+        if ((status != 1 && status != 2 && status != 3) || any_lost) { *sweeps_out = sweep; return 1; }   // -7, a lost word anywhere, or nothing written: A untouched by this launch
         int rc = rlhip::lacpy<T>(c, 2, m, n, reinterpret_cast<const T*>(buf), m, A, lda);
-        if (rc) { rlhip_ws_release(c, mark); return rc < 0 ? rc : 1; }
+        if (rc) return rc < 0 ? rc : 1;
         sweep = done_sweeps;
         if (status == 1) { *done = true; break; }
         if (status == 2) {
@@ -937,7 +936,6 @@ int persistent_jacobi_sweeps(rlhip_ctx* c, int m, int n, T* A, int64_t lda, T to
         }
         break;                                         // sweep limit
     }
-    rlhip_ws_release(c, mark);
     *sweeps_out = sweep;
     return 0;
 }
@@ -1053,11 +1051,11 @@ int gesvdj_core(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T
         // A single column goes the same way: its norm is then summed in fp64.
         {
             c->path_count[25]++;
-            size_t mk = rlhip_ws_mark(c);
-            double* Ad = ws_alloc<double>(c, (size_t)m * n);
-            double* Sd = ws_alloc<double>(c, (size_t)n);
-            double* VTd = (VT != nullptr) ? ws_alloc<double>(c, (size_t)n * n) : nullptr;
-            if (!Ad || !Sd || (VT != nullptr && !VTd)) { rlhip_ws_release(c, mk); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+            ws_scope ws(c);
+            double* Ad = ws.alloc<double>((size_t)m * n);
+            double* Sd = ws.alloc<double>((size_t)n);
+            double* VTd = (VT != nullptr) ? ws.alloc<double>((size_t)n * n) : nullptr;
+            if (!Ad || !Sd || (VT != nullptr && !VTd)) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
             const unsigned gA = (unsigned)((m * n + 255) / 256), gV = (unsigned)(((int64_t)n * n + 255) / 256);
             hipLaunchKernelGGL((convert_kernel<float, double>), dim3(gA), dim3(256), 0, c->stream, m, (int64_t)n, A, lda, Ad, m);
             int info = gesvdj_core<double>(c, m, n64, Ad, m, Sd, VTd, (int64_t)n, sweeps_host);
@@ -1068,19 +1066,18 @@ int gesvdj_core(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T
                     hipLaunchKernelGGL((convert_kernel<double, float>), dim3(gV), dim3(256), 0, c->stream, (int64_t)n, (int64_t)n, VTd, (int64_t)n, VT, ldvt);
                 RLHIP_LAUNCH_CHECK();
             }
-            rlhip_ws_release(c, mk);
             return info;
         }
     }
-    size_t mark = rlhip_ws_mark(c);
-    T* V = (VT != nullptr) ? ws_alloc<T>(c, (size_t)n * n) : nullptr;
-    T* W = ws_alloc<T>(c, (size_t)m * n);
-    T* Sraw = ws_alloc<T>(c, (size_t)n);
-    int* rank = ws_alloc<int>(c, (size_t)n);
-    if ((VT != nullptr && !V) || !W || !Sraw || !rank) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* V = (VT != nullptr) ? ws.alloc<T>((size_t)n * n) : nullptr;
+    T* W = ws.alloc<T>((size_t)m * n);
+    T* Sraw = ws.alloc<T>((size_t)n);
+    int* rank = ws.alloc<int>((size_t)n);
+    if ((VT != nullptr && !V) || !W || !Sraw || !rank) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     unsigned* d_nrot = (unsigned*)(c->d_mail + 16);
     int rc = V ? laset<T>(c, 2, n, n, T(0), T(1), V, n) : 0;
-    if (rc) { rlhip_ws_release(c, mark); return rc; }
+    if (rc) return rc;
     const T tol = std::sqrt((T)m) * std::numeric_limits<T>::epsilon();
     const int max_sweeps = 60;
     int sweep = 0;
@@ -1094,7 +1091,7 @@ int gesvdj_core(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T
             // singular values / left vectors only and at most 256 rows: all sweeps in one resident launch (see jacobi_persist_kernel)
             if (persist && V == nullptr && m <= JM && jb_sel == 16 && n > 32) {
                 const int prc = persistent_jacobi_sweeps<T>(c, (int)m, n, A, lda, tol, d_nrot, max_sweeps, &sweep, &done);
-                if (prc < 0) { rlhip_ws_release(c, mark); return prc; }
+                if (prc < 0) return prc;
                 if (prc == 0) c->path_count[6]++;
             }
         }
@@ -1104,7 +1101,7 @@ int gesvdj_core(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T
         else if (m > JM) rc = block_jacobi_sweeps<T, 16, 2 * JM>(c, (int)m, n, A, lda, V, tol, d_nrot, max_sweeps, &sweep);   // 257 .. 512 rows: 32 x 512 panel = 128 KiB
         else if (jb_sel == 32 || n <= 32) rc = block_jacobi_sweeps<T, 32, JM>(c, (int)m, n, A, lda, V, tol, d_nrot, max_sweeps, &sweep);
         else rc = block_jacobi_sweeps<T, 16, JM>(c, (int)m, n, A, lda, V, tol, d_nrot, max_sweeps, &sweep);
-        if (rc) { rlhip_ws_release(c, mark); return rc; }
+        if (rc) return rc;
         if (sweep >= max_sweeps) info = 1;
     } else if (n > 1) {
         c->path_count[24]++;
@@ -1129,7 +1126,6 @@ int gesvdj_core(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T
                        W, m, S, VT, ldvt);
     RLHIP_LAUNCH_CHECK();
     rc = lacpy<T>(c, 2, m, n, W, m, A, lda);
-    rlhip_ws_release(c, mark);
     return rc ? rc : info;
 }
 
@@ -1143,14 +1139,13 @@ int gesvdj(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* VT, i
     if (VT != nullptr && ldvt < (n > 1 ? n : 1)) return -8;   // VT == nullptr: singular values and left vectors only
     if (sweeps_host) *sweeps_host = 0;
     if (n == 0) return 0;
-    size_t mark = rlhip_ws_mark(c);
-    unsigned long long* w = ws_alloc<unsigned long long>(c, 4);
-    if (!w) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    unsigned long long* w = ws.alloc<unsigned long long>(4);
+    if (!w) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     int rc = svd_guard_begin<T>(c, m, n, A, lda, w);
     int info = 0;
     if (!rc) info = gesvdj_core<T>(c, m, n, A, lda, S, VT, ldvt, sweeps_host);
     if (!rc && info >= 0) rc = svd_guard_end<T>(c, n, S, w);
-    rlhip_ws_release(c, mark);
     return rc ? rc : info;
 }
 

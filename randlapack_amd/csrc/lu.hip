@@ -734,13 +734,13 @@ int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_d
     if (mn == 0) return 0;
     const int num_cu = c->num_cu;
     RLHIP_FUNC_LDS(c, getrf_panel_kernel<T>, 128 * 1024);
-    size_t mark = rlhip_ws_mark(c);
+    ws_scope ws(c);
     const int64_t Gmax = num_cu;
     LuArgs<T> g;
     g.m = m; g.n = n; g.A = A; g.lda = lda; g.ipiv = ipiv_dev;
-    g.cand_val = ws_alloc<T>(c, 2 * Gmax); g.cand_row = ws_alloc<int64_t>(c, 2 * Gmax);
-    g.cand_data = ws_alloc<T>(c, (size_t)2 * Gmax * PB); g.diag_data = ws_alloc<T>(c, 2 * PB + 64);
-    g.bar = ws_alloc<unsigned>(c, 4); g.info = (int*)ws_alloc<int>(c, 4);
+    g.cand_val = ws.alloc<T>(2 * Gmax); g.cand_row = ws.alloc<int64_t>(2 * Gmax);
+    g.cand_data = ws.alloc<T>((size_t)2 * Gmax * PB); g.diag_data = ws.alloc<T>(2 * PB + 64);
+    g.bar = ws.alloc<unsigned>(4); g.info = (int*)ws.alloc<int>(4);
     const bool use_tag = m < ((int64_t)1 << 31);
     constexpr size_t TW = sizeof(T) / 4;
     // (the general register kernel may run more workgroups than CUs: the word buffer is sized -- and cleared -- for the largest grid of this call)
@@ -751,10 +751,10 @@ int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_d
     // tags: (panel index + 1) * 64 + column.  The word buffer is cleared at the start of every call and belongs to this call's workspace, so
     // a tag is unique where it can be seen and never equals the cleared pattern (m < 2^31 keeps 2 * j0 + 64 inside 32 bits)
     if (use_tag) {
-        if (!g.tw) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+        if (!g.tw) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
         RLHIP_CHECK(hipMemsetAsync(g.tw, 0, tw_words * sizeof(unsigned long long), c->stream));
     }
-    if (!g.cand_val || !g.cand_row || !g.cand_data || !g.diag_data || !g.bar || !g.info) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    if (!g.cand_val || !g.cand_row || !g.cand_data || !g.diag_data || !g.bar || !g.info) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     // Two-level blocking: the 32-column panel steps then update only the columns of their own
     // OUTER block; everything to the right of it gets the block's interchanges, one block forward substitution and ONE rank-nbo GEMM
     // when the block is finished.  Pays for very tall matrices only (numbers below); round 1 measured it slower everywhere because the
@@ -775,7 +775,7 @@ int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_d
         int64_t rpw = (rows + Gmax - 1) / Gmax;
         if (rpw < 256) rpw = 256;   // fewer, fatter workgroups: the per-column rendezvous and winner search shrink with G
         const int64_t rpw_max = (96 * 1024) / (PB * (int64_t)sizeof(T));
-        if (rpw > rpw_max && !(use_tag && rows >= 1024)) { rlhip_ws_release(c, mark); return -2; }   // LDS variant only: > num_cu * 384 rows (fp64)
+        if (rpw > rpw_max && !(use_tag && rows >= 1024)) return -2;   // LDS variant only: > num_cu * 384 rows (fp64)
         int64_t G = (rows + rpw - 1) / rpw;
         g.j0 = j0; g.pb = pb; g.rpw = rpw;
         // (the tagged-word kernels never touch the barrier counter: only the first panel of a call needs the launch, for `info`)
@@ -794,8 +794,8 @@ int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_d
         if (G_reg > reg_cap[c->device & 63] && G_reg > 64) {
             // taller than the resident kernels can hold (fp64: 262144 rows, fp32: 262144): column-at-a-time launches on the L2-resident panel
             const int nparts = (int)((rows / 2048 < 1) ? 1 : (rows / 2048 > 1024 ? 1024 : rows / 2048));
-            T* pval = ws_alloc<T>(c, 1024); int64_t* prow = ws_alloc<int64_t>(c, 1024);
-            if (!pval || !prow) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+            T* pval = ws.alloc<T>(1024); int64_t* prow = ws.alloc<int64_t>(1024);
+            if (!pval || !prow) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
             for (int64_t j = j0; j < j0 + pb; ++j) {
                 hipLaunchKernelGGL(getf2_colmax_kernel<T>, dim3((unsigned)nparts), dim3(256), 0, c->stream, m, j, A, lda, pval, prow);
                 hipLaunchKernelGGL(getf2_pivot_kernel<T>, dim3(1), dim3(256), 0, c->stream, m, j0, pb, j, nparts, A, lda, pval, prow, ipiv_dev, g.info);
@@ -839,7 +839,7 @@ int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_d
             if (mrest > 0) {
                 int rc = gemm_impl<T>(c, 0, 0, mrest, rest, pb, T(-1), A + (j0 + pb) + j0 * lda, lda, A + j0 + (j0 + pb) * lda, lda, T(1),
                                       A + (j0 + pb) + (j0 + pb) * lda, lda, 0);
-                if (rc) { rlhip_ws_release(c, mark); return rc; }
+                if (rc) return rc;
             }
         }
     }
@@ -862,7 +862,7 @@ int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_d
             if (below > 0) {
                 int rc = gemm_impl<T>(c, 0, 0, below, right, sb, T(-1), A + (s0 + sb) + s0 * lda, lda, A + s0 + Cin * lda, lda, T(1),
                                       A + (s0 + sb) + Cin * lda, lda, 0);
-                if (rc) { rlhip_ws_release(c, mark); return rc; }
+                if (rc) return rc;
             }
         }
         RLHIP_LAUNCH_CHECK();
@@ -870,7 +870,7 @@ int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_d
         if (mrest > 0) {
             int rc = gemm_impl<T>(c, 0, 0, mrest, right, Jend - J0, T(-1), A + Jend + J0 * lda, lda, A + J0 + Cin * lda, lda, T(1),
                                   A + Jend + Cin * lda, lda, 0);
-            if (rc) { rlhip_ws_release(c, mark); return rc; }
+            if (rc) return rc;
         }
     }
     }
@@ -888,9 +888,8 @@ int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_d
         RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 56, g.info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
         *info_host = *(int*)(c->h_mail + 56);
-        if (*info_host < 0) { rlhip_ws_release(c, mark); return -9; }   // the flag-less exchange timed out (bounded so that a lost word cannot hang the device)
+        if (*info_host < 0) return -9;   // the flag-less exchange timed out (bounded so that a lost word cannot hang the device)
     }
-    rlhip_ws_release(c, mark);
     return 0;
 }
 

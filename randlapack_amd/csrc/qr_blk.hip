@@ -464,18 +464,18 @@ int geqrf_blk(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev)
     if (n > m || n < 1 || m > (int64_t)NT * RPT) return 0;
     const int64_t G = (n + 7) / 8;
     if (G > c->num_cu) return 0;                           // one chunk per workgroup, one workgroup per CU: all of them are resident
-    size_t mark = rlhip_ws_mark(c);
+    ws_scope ws(c);
     QbArgs<T> g;
     g.m = m; g.n = n; g.A = A; g.lda = lda; g.tau = tau_dev;
-    g.Tx = ws_alloc<T>(c, (size_t)G * 64);
-    g.flag = ws_alloc<unsigned>(c, (size_t)G + 4);
-    if (!g.Tx || !g.flag) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    g.Tx = ws.alloc<T>((size_t)G * 64);
+    g.flag = ws.alloc<unsigned>((size_t)G + 4);
+    if (!g.Tx || !g.flag) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     {
         const hipError_t me = hipMemsetAsync(g.flag, 0, (size_t)G * sizeof(unsigned), c->stream);
-        if (me != hipSuccess) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(me); }
+        if (me != hipSuccess) return RLHIP_ERR_HIP(me);
     }
 #ifdef RLHIP_QB_PROF
-    g.prof = (unsigned long long*)ws_alloc<double>(c, 4);
+    g.prof = (unsigned long long*)ws.alloc<double>(4);
     RLHIP_CHECK(hipMemsetAsync(g.prof, 0, 4 * sizeof(double), c->stream));
 #endif
     // every workgroup waits for flags raised by others: the grid must be co-resident (cooperative launch: checked against the device's
@@ -483,7 +483,6 @@ int geqrf_blk(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev)
     void* kargs[] = {(void*)&g};
     if (hipLaunchCooperativeKernel((const void*)qr_blk_kernel<T, NT, RPT, IW>, dim3((unsigned)G), dim3(NT), kargs, 0, c->stream) != hipSuccess) {
         (void)hipGetLastError();                           // the grid cannot be made resident here (shared or partitioned device): the caller's other routes
-        rlhip_ws_release(c, mark);
         return 0;
     }
 #ifdef RLHIP_QB_PROF
@@ -495,7 +494,6 @@ int geqrf_blk(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev)
                 pf[0] / 100.0 / G, pf[1] / 100.0 / G, pf[2] / 100.0 / G);
     }
 #endif
-    rlhip_ws_release(c, mark);
     c->path_count[8]++;
     return 1;
 }
@@ -510,22 +508,20 @@ int lunp_blk(rlhip_ctx* c, int64_t n, T* A, int64_t lda, T* D) {
     if (n < 1 || n > (int64_t)NT * RPT) return 0;
     const int64_t G = (n + 7) / 8;
     if (G > c->num_cu) return 0;
-    size_t mark = rlhip_ws_mark(c);
+    ws_scope ws(c);
     LbArgs<T> g;
     g.n = n; g.A = A; g.lda = lda; g.D = D;
-    g.flag = ws_alloc<unsigned>(c, (size_t)G + 4);
-    if (!g.flag) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    g.flag = ws.alloc<unsigned>((size_t)G + 4);
+    if (!g.flag) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     {
         const hipError_t me = hipMemsetAsync(g.flag, 0, (size_t)G * sizeof(unsigned), c->stream);
-        if (me != hipSuccess) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(me); }
+        if (me != hipSuccess) return RLHIP_ERR_HIP(me);
     }
     void* kargs[] = {(void*)&g};
     if (hipLaunchCooperativeKernel((const void*)lunp_blk_kernel<T, NT, RPT>, dim3((unsigned)G), dim3(NT), kargs, 0, c->stream) != hipSuccess) {
         (void)hipGetLastError();
-        rlhip_ws_release(c, mark);
         return 0;
     }
-    rlhip_ws_release(c, mark);
     c->path_count[9]++;
     return 1;
 }

@@ -1073,9 +1073,9 @@ int geqrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev) {
     if (n < 0) return -3;
     if (lda < (m > 1 ? m : 1)) return -5;
     if (m == 0 || n == 0) return 0;
-    size_t mark = rlhip_ws_mark(c);
-    unsigned long long* w = ws_alloc<unsigned long long>(c, 4);
-    if (!w) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    unsigned long long* w = ws.alloc<unsigned long long>(4);
+    if (!w) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     // a thread walks rows of a column: coalesced, no index divisions, eight loads in flight; at most 1024 workgroups (one atomic each)
     int64_t bx = (m + 1023) / 1024, by = n;
     if (bx > 64) bx = 64;
@@ -1083,7 +1083,7 @@ int geqrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev) {
     const dim3 blocks((unsigned)bx, (unsigned)(by < 1 ? 1 : by));
     const int64_t kmin = m < n ? m : n;
     hipError_t e = hipMemsetAsync(w, 0, sizeof(unsigned long long), c->stream);
-    if (e != hipSuccess) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(e); }
+    if (e != hipSuccess) return RLHIP_ERR_HIP(e);
     hipLaunchKernelGGL(geqrf_absmax_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w);
     hipLaunchKernelGGL(geqrf_rescale_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w, 0, kmin);
     int rc = geqrf_core<T>(c, m, n, A, lda, tau_dev);
@@ -1092,7 +1092,6 @@ int geqrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev) {
         e = hipGetLastError();
         if (e != hipSuccess) rc = RLHIP_ERR_HIP(e);
     }
-    rlhip_ws_release(c, mark);
     return rc;
 }
 
@@ -1106,15 +1105,15 @@ static int qrcp_guarded(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, i
     if (m == 0 || n == 0) return 0;
     const int64_t kmin = m < n ? m : n;
     const int64_t tail = (steps >= 0 && steps < kmin) ? steps : kmin;
-    size_t mark = rlhip_ws_mark(c);
-    unsigned long long* w = ws_alloc<unsigned long long>(c, 4);
-    if (!w) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    unsigned long long* w = ws.alloc<unsigned long long>(4);
+    if (!w) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     int64_t bx = (m + 1023) / 1024, by = n;               // (the launch shape of geqrf's guard)
     if (bx > 64) bx = 64;
     if (by > 1024 / bx) by = 1024 / bx;
     const dim3 blocks((unsigned)bx, (unsigned)(by < 1 ? 1 : by));
     hipError_t e = hipMemsetAsync(w, 0, sizeof(unsigned long long), c->stream);
-    if (e != hipSuccess) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(e); }
+    if (e != hipSuccess) return RLHIP_ERR_HIP(e);
     hipLaunchKernelGGL(geqrf_absmax_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w);
     hipLaunchKernelGGL(geqrf_rescale_kernel<T>, blocks, dim3(256), 0, c->stream, m, n, A, lda, w, 0, tail);
     int rc = qr_core<T>(c, 1, m, n, A, lda, jpvt_dev, tau_dev, steps, hq_formula);
@@ -1123,7 +1122,6 @@ static int qrcp_guarded(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, i
         e = hipGetLastError();
         if (e != hipSuccess) rc = RLHIP_ERR_HIP(e);
     }
-    rlhip_ws_release(c, mark);
     return rc;
 }
 
@@ -1148,9 +1146,9 @@ int geqrf_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev
         if (rb < 0) return rb;
         if (rb == 1) {
             if (n <= kmax) return 0;
-            size_t markb = rlhip_ws_mark(c);
-            T* Tb = ws_alloc<T>(c, (size_t)NBQ * NBQ);
-            if (!Tb) { rlhip_ws_release(c, markb); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+            ws_scope ws(c);
+            T* Tb = ws.alloc<T>((size_t)NBQ * NBQ);
+            if (!Tb) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
             int rcb = 0;
             for (int64_t j0 = 0; j0 < kmax && !rcb; j0 += NBQ) {
                 const int64_t jb = (kmax - j0 < NBQ) ? (kmax - j0) : NBQ;
@@ -1158,7 +1156,6 @@ int geqrf_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev
                 rcb = larft_gram<T>(c, m - j0, jb, P, lda, tau_dev + j0, Tb, jb);
                 if (!rcb) rcb = gemqrt_lt<T>(c, m - j0, n - kmax, jb, jb, P, lda, Tb, jb, A + j0 + kmax * lda, lda);
             }
-            rlhip_ws_release(c, markb);
             return rcb;
         }
     }
@@ -1168,16 +1165,15 @@ int geqrf_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev
     if (kmax <= pipe_max && (m < 16 * kmax && (10 * m < 19 * kmax || kmax < 600))) {
         int rc0 = qr_core<T>(c, 0, m, kmax, A, lda, nullptr, tau_dev);
         if (rc0 || n <= kmax) return rc0;
-        size_t mark0 = rlhip_ws_mark(c);
-        T* T0 = ws_alloc<T>(c, (size_t)kmax * kmax);
-        if (!T0) { rlhip_ws_release(c, mark0); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+        ws_scope ws(c);
+        T* T0 = ws.alloc<T>((size_t)kmax * kmax);
+        if (!T0) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
         rc0 = larft_gram<T>(c, m, kmax, A, lda, tau_dev, T0, kmax);
         if (!rc0) rc0 = gemqrt_lt<T>(c, m, n - kmax, kmax, kmax, A, lda, T0, kmax, A + kmax * lda, lda);
-        rlhip_ws_release(c, mark0);
         return rc0;
     }
-    size_t mark = rlhip_ws_mark(c);
-    T* Tm = (n > NBQ || n > kmax) ? ws_alloc<T>(c, (size_t)NBQ * NBQ) : nullptr;
+    ws_scope ws(c);
+    T* Tm = (n > NBQ || n > kmax) ? ws.alloc<T>((size_t)NBQ * NBQ) : nullptr;
     int rc = 0;
     for (int64_t j0 = 0; j0 < kmax && !rc; j0 += NBQ) {
         const int64_t jb = (kmax - j0 < NBQ) ? (kmax - j0) : NBQ;
@@ -1193,7 +1189,6 @@ int geqrf_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev
             if (!rc) rc = gemqrt_lt<T>(c, rows, rest, jb, jb, P, lda, Tm, jb, A + j0 + (j0 + jb) * lda, lda);
         }
     }
-    rlhip_ws_release(c, mark);
     return rc;
 }
 
@@ -1228,15 +1223,15 @@ int ungqr(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, const T* tau_de
     if (n < 0 || n > m) return -3;
     if (lda < (m > 1 ? m : 1)) return -6;
     if (n == 0) return 0;
-    size_t mark = rlhip_ws_mark(c);
-    T* Tm = ws_alloc<T>(c, (size_t)n * n);
-    T* V1t = ws_alloc<T>(c, (size_t)n * n);
-    T* Wm = ws_alloc<T>(c, (size_t)n * n);
-    T* Qtop = ws_alloc<T>(c, (size_t)n * n);
-    T* V2 = (m > n) ? ws_alloc<T>(c, (size_t)(m - n) * n) : nullptr;
-    if (!Tm || !V1t || !Wm || !Qtop || (m > n && !V2)) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* Tm = ws.alloc<T>((size_t)n * n);
+    T* V1t = ws.alloc<T>((size_t)n * n);
+    T* Wm = ws.alloc<T>((size_t)n * n);
+    T* Qtop = ws.alloc<T>((size_t)n * n);
+    T* V2 = (m > n) ? ws.alloc<T>((size_t)(m - n) * n) : nullptr;
+    if (!Tm || !V1t || !Wm || !Qtop || (m > n && !V2)) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     int rc = larft_gram<T>(c, m, n, A, lda, tau_dev, Tm, n);
-    if (rc) { rlhip_ws_release(c, mark); return rc; }
+    if (rc) return rc;
     const unsigned nb2 = (unsigned)((n * n + 255) / 256);
     hipLaunchKernelGGL(ungqr_seed_kernel<T>, dim3(nb2), dim3(256), 0, c->stream, n, A, lda, V1t);
     RLHIP_LAUNCH_CHECK();
@@ -1254,7 +1249,6 @@ int ungqr(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, const T* tau_de
     if (!rc)
         RLHIP_CHECK(hipMemcpy2DAsync(A, (size_t)lda * sizeof(T), Qtop, (size_t)n * sizeof(T), (size_t)n * sizeof(T), (size_t)n,
                                      hipMemcpyDeviceToDevice, c->stream));
-    rlhip_ws_release(c, mark);
     return rc;
 }
 
@@ -1282,7 +1276,7 @@ static int qr_core(rlhip_ctx* c, int pivot, int64_t m, int64_t n, T* A, int64_t 
         else lds_bytes = 0;
     }
     if (!pivot && max_steps < 0) {
-        size_t mark2 = rlhip_ws_mark(c);
+        ws_scope ws(c);
         const int64_t kmax = m < n ? m : n;
         QrPipeArgs<T> pa;
         pa.m = m; pa.n = n; pa.A = A; pa.lda = lda; pa.tau = tau_dev; pa.use_lds = use_lds;
@@ -1294,8 +1288,8 @@ static int qr_core(rlhip_ctx* c, int pivot, int64_t m, int64_t n, T* A, int64_t 
             Gp = n < num_cu ? n : num_cu;
             pa.wg_per_col = 1;
         }
-        pa.flag = ws_alloc<unsigned>(c, (size_t)kmax + 4);
-        if (!pa.flag) { rlhip_ws_release(c, mark2); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+        pa.flag = ws.alloc<unsigned>((size_t)kmax + 4);
+        if (!pa.flag) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
         hipLaunchKernelGGL(zero_u32_n, dim3((unsigned)((kmax + 255) / 256)), dim3(256), 0, c->stream, pa.flag, kmax);
         // local column slots under the chunked layout; if the rounding up to whole chunks no longer fits LDS, fall back to chunk = 1
         auto slots = [&](int64_t ch) { return (size_t)((((n + ch - 1) / ch + Gp - 1) / Gp) * ch); };
@@ -1312,9 +1306,8 @@ static int qr_core(rlhip_ctx* c, int pivot, int64_t m, int64_t n, T* A, int64_t 
                                        : (pa.v_in_lds ? (const void*)qr_pipe_kernel<T, false, true> : (const void*)qr_pipe_kernel<T, false, false>);
             hipError_t le = qr_kernel_lds_limit(c, kern);
             if (le == hipSuccess) le = hipLaunchCooperativeKernel(kern, dim3((unsigned)Gp), dim3(256), kargs, (unsigned)dyn2, c->stream);
-            if (le != hipSuccess) { rlhip_ws_release(c, mark2); return RLHIP_ERR_HIP(le); }
+            if (le != hipSuccess) return RLHIP_ERR_HIP(le);
         }
-        rlhip_ws_release(c, mark2);
         return 0;
     }
     if (pivot && use_lds && m < ((int64_t)1 << 31) - 2 && n < ((int64_t)1 << 31) - 2) {
@@ -1331,16 +1324,16 @@ static int qr_core(rlhip_ctx* c, int pivot, int64_t m, int64_t n, T* A, int64_t 
         const size_t dyn = cpw_t * sizeof(int64_t) + (2 * cpw_t + (size_t)m) * sizeof(T) + cpw_t * (size_t)m * sizeof(T);
         if (dyn <= 150 * 1024) {
             RLHIP_FUNC_LDS(c, qrcp_tag_kernel<T>, 150 * 1024);
-            size_t mark = rlhip_ws_mark(c);
+            ws_scope ws(c);
             QrcpTagArgs<T> t;
             t.m = m; t.n = n; t.A = A; t.lda = lda; t.tau = tau_dev;
-            t.Aout = ws_alloc<T>(c, (size_t)m * n); t.ldo = m;
-            t.jpvt = ws_alloc<int64_t>(c, (size_t)n);
+            t.Aout = ws.alloc<T>((size_t)m * n); t.ldo = m;
+            t.jpvt = ws.alloc<int64_t>((size_t)n);
             const size_t words = 2 * qt_words<T>(m, Gt);
             t.tw = (unsigned long long*)rlhip_xchg_buffer(c, words * sizeof(unsigned long long));
-            t.info = (int*)ws_alloc<int>(c, 32);
+            t.info = (int*)ws.alloc<int>(32);
             // (the scratch copy of the output is this path's own need: when it cannot be had, the rendezvous kernel below -- which works in
-            // place -- takes the problem instead of an out-of-memory error; every error exit releases the arena mark)
+            // place -- takes the problem instead of an out-of-memory error)
             const bool have = t.tw && t.info && t.Aout && t.jpvt;
             t.tol3z = std::sqrt(std::numeric_limits<T>::epsilon() / 2);
             t.max_steps = max_steps; t.hq_formula = hq_formula;
@@ -1358,7 +1351,7 @@ static int qr_core(rlhip_ctx* c, int pivot, int64_t m, int64_t n, T* A, int64_t 
                 te = hipMemcpyAsync(c->h_mail + 56, t.info, sizeof(int), hipMemcpyDeviceToHost, c->stream);
                 if (te == hipSuccess) te = rlhip_stream_sync(c);
             }
-            if (te != hipSuccess) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(te); }
+            if (te != hipSuccess) return RLHIP_ERR_HIP(te);
 #ifdef RLHIP_QT_PROF
             {
                 long long pf[6];
@@ -1371,39 +1364,33 @@ static int qr_core(rlhip_ctx* c, int pivot, int64_t m, int64_t n, T* A, int64_t 
                 // the kernel only read A: its results are taken over now (10 MB at 1280 x 1024: microseconds)
                 te = hipMemcpy2DAsync(A, (size_t)lda * sizeof(T), t.Aout, (size_t)m * sizeof(T), (size_t)m * sizeof(T), (size_t)n, hipMemcpyDeviceToDevice, c->stream);
                 if (te == hipSuccess) te = hipMemcpyAsync(jpvt_dev, t.jpvt, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream);
-                rlhip_ws_release(c, mark);
                 return te == hipSuccess ? 0 : RLHIP_ERR_HIP(te);
             }
             // no scratch, no residency, or a published word never arrived (bounded spins).  A and jpvt are untouched: the rendezvous kernel below.
-            rlhip_ws_release(c, mark);
         }
     }
-    size_t mark = rlhip_ws_mark(c);
+    ws_scope ws(c);
     QrcpArgs<T> g;
     g.m = m; g.n = n; g.A = A; g.lda = lda; g.jpvt = jpvt_dev; g.tau = tau_dev;
-    g.cand_val = ws_alloc<T>(c, 2 * G); g.cand_pos = ws_alloc<int64_t>(c, 2 * G); g.cand_tau = ws_alloc<T>(c, 2 * G);
-    g.slot = ws_alloc<T>(c, (size_t)2 * G * m); g.kcol = ws_alloc<T>(c, (size_t)2 * (m + 2));
-    g.bar = ws_alloc<unsigned>(c, 4);
+    g.cand_val = ws.alloc<T>(2 * G); g.cand_pos = ws.alloc<int64_t>(2 * G); g.cand_tau = ws.alloc<T>(2 * G);
+    g.slot = ws.alloc<T>((size_t)2 * G * m); g.kcol = ws.alloc<T>((size_t)2 * (m + 2));
+    g.bar = ws.alloc<unsigned>(4);
     g.tol3z = std::sqrt(std::numeric_limits<T>::epsilon() / 2);   // SQRT(DLAMCH('Epsilon')): LAPACK's eps is the rounding unit
     g.use_lds = use_lds; g.pivot = pivot; g.max_steps = max_steps; g.hq_formula = hq_formula;
-    if (!g.cand_val || !g.cand_pos || !g.cand_tau || !g.slot || !g.kcol || !g.bar) {
-        rlhip_ws_release(c, mark);
-        return RLHIP_ERR_HIP(hipErrorOutOfMemory);
-    }
+    if (!g.cand_val || !g.cand_pos || !g.cand_tau || !g.slot || !g.kcol || !g.bar) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     hipLaunchKernelGGL(zero_u32, dim3(1), dim3(1), 0, c->stream, g.bar);
     const size_t cpw_final = (size_t)((n + G - 1) / G);
     g.v_in_lds = use_lds || ((2 * cpw_final + (size_t)m) * sizeof(T) <= 140 * 1024);
     const size_t dyn = (2 * cpw_final + (g.v_in_lds ? (size_t)m : 0)) * sizeof(T) + (use_lds ? cpw_final * (size_t)m * sizeof(T) : 0);
-    if (dyn > 150 * 1024) { rlhip_ws_release(c, mark); return -2; }   // only the per-column norms left: n / G > ~9000 columns per workgroup
+    if (dyn > 150 * 1024) return -2;   // only the per-column norms left: n / G > ~9000 columns per workgroup
     {   // grid barrier inside: cooperative launch (see qr_pipe_kernel above)
         void* kargs[] = {(void*)&g};
         const void* kern = use_lds ? (const void*)qrcp_kernel<T, true, true>
                                    : (g.v_in_lds ? (const void*)qrcp_kernel<T, false, true> : (const void*)qrcp_kernel<T, false, false>);
         hipError_t le = qr_kernel_lds_limit(c, kern);
         if (le == hipSuccess) le = hipLaunchCooperativeKernel(kern, dim3((unsigned)G), dim3(256), kargs, (unsigned)dyn, c->stream);
-        if (le != hipSuccess) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(le); }
+        if (le != hipSuccess) return RLHIP_ERR_HIP(le);
     }
-    rlhip_ws_release(c, mark);
     return 0;
 }
 

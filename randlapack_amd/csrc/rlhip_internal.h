@@ -65,7 +65,7 @@ struct rlhip_ctx {
     // scratch arena: stack-disciplined bump allocator over a short list of device segments.  Marks are virtual
     // offsets (segment k starts where segment k-1's full size ends); when a request does not fit, a new, larger
     // segment is appended (hipMalloc once); when the stack returns to empty the segments are merged into one so
-    // that steady-state calls never allocate.
+    // that steady-state calls never allocate.  Library code opens and closes a marked region with ws_scope (below), never by hand.
     struct Seg { char* base; size_t size; };
     Seg segs[32];
     int nsegs = 0;
@@ -120,13 +120,27 @@ static inline hipError_t rlhip_stream_sync(rlhip_ctx* c) {
     return e;
 }
 
-// scratch arena helpers (capi.hip)
+// scratch arena helpers (capi.hip).  Library code takes and returns marks through ws_scope only; the bare mark / release pair is for
+// the scratch ABI entry points and rlhip_reserve_workspace in capi.hip.
 void* rlhip_ws_alloc(rlhip_ctx* c, size_t bytes);           // 256-B aligned, never fails softly (nullptr on OOM)
 size_t rlhip_ws_mark(rlhip_ctx* c);
 void rlhip_ws_release(rlhip_ctx* c, size_t mark);
 
 template <typename T>
 static inline T* ws_alloc(rlhip_ctx* c, size_t n) { return (T*)rlhip_ws_alloc(c, n * sizeof(T)); }
+
+// One marked region of the arena: everything allocated after the constructor goes back when the scope ends, on every way out of it
+// (a plain return and the return inside RLHIP_CHECK included).  A region that ends before its function does is a { } block.
+struct ws_scope {
+    rlhip_ctx* const c;
+    const size_t mark;
+    explicit ws_scope(rlhip_ctx* ctx) : c(ctx), mark(rlhip_ws_mark(ctx)) {}
+    ~ws_scope() { rlhip_ws_release(c, mark); }
+    ws_scope(const ws_scope&) = delete;
+    ws_scope& operator=(const ws_scope&) = delete;
+    template <typename T>
+    T* alloc(size_t n) { return ws_alloc<T>(c, n); }   // nullptr when the arena cannot grow
+};
 // device buffer for the tagged-word exchanges between workgroups (QRCP / LU panel kernels); grows, lives with the context.
 // RLHIP_XCHG = 0: ordinary device memory, 1: fine-grained, 2: uncached (default)
 void* rlhip_xchg_buffer(rlhip_ctx* c, size_t bytes);

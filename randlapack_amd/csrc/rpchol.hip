@@ -388,13 +388,13 @@ int sqexp_submatrix(rlhip_ctx* c, int64_t rows_x, int64_t cols_x, const T* X, in
     if (!(bandwidth > T(0))) return -13;
     if (rows_k == 0 || cols_k == 0) return 0;
     if (cols_k > 65535) return -8;
-    const size_t mark = rlhip_ws_mark(c);
+    ws_scope ws(c);
     const T* nr = sq_colnorms_x;
     if (!nr) {
-        T* tmp = ws_alloc<T>(c, (size_t)cols_x);
+        T* tmp = ws.alloc<T>((size_t)cols_x);
         if (!tmp) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
         int rc = sq_colnorms(c, rows_x, cols_x, X, ldx, tmp);
-        if (rc) { rlhip_ws_release(c, mark); return rc; }
+        if (rc) return rc;
         nr = tmp;
     }
     int rc = rlhip::gemm<T>(c, rlhip::Trans, rlhip::NoTrans, rows_k, cols_k, rows_x, T(-2), X + ro * ldx, ldx, X + co * ldx, ldx, T(0), K, ldk);
@@ -405,7 +405,6 @@ int sqexp_submatrix(rlhip_ctx* c, int64_t rows_x, int64_t cols_x, const T* X, in
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = RLHIP_ERR_HIP(e);
     }
-    rlhip_ws_release(c, mark);
     return rc;
 }
 
@@ -430,14 +429,14 @@ int rbf_apply(rlhip_ctx* c, int64_t rows_x, int64_t dim, const T* X, int64_t ldx
     if (ldb < (dim > 1 ? dim : 1)) return -13;
     if (ldc < (dim > 1 ? dim : 1)) return -16;
     if (dim == 0 || n == 0) return 0;
-    const size_t mark = rlhip_ws_mark(c);
+    ws_scope ws(c);
     int rc = 0;
-    T* nr = ws_alloc<T>(c, (size_t)dim);
+    T* nr = ws.alloc<T>((size_t)dim);
     int64_t rb = ((int64_t)1 << 26) / dim;                 // the K block holds at most 2^26 entries (one row when dim > 2^26)
     rb = rb < 1 ? 1 : (rb >= 256 ? (rb / 256) * 256 : rb);
     if (rb > dim) rb = dim;
-    T* Kb = ws_alloc<T>(c, (size_t)(rb * dim));
-    if (!nr || !Kb) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    T* Kb = ws.alloc<T>((size_t)(rb * dim));
+    if (!nr || !Kb) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     rc = sq_colnorms(c, rows_x, dim, X, ldx, nr);
     for (int64_t r0 = 0; rc == 0 && r0 < dim; r0 += rb) {
         const int64_t rows = (dim - r0) < rb ? (dim - r0) : rb;
@@ -454,7 +453,6 @@ int rbf_apply(rlhip_ctx* c, int64_t rows_x, int64_t dim, const T* X, int64_t ldx
             rc = axpby_dev<T>(c, dim, coeff, B + i * ldb, T(1), C + i * ldc);
         }
     }
-    rlhip_ws_release(c, mark);
     return rc;
 }
 
@@ -471,14 +469,14 @@ int sample_indices_iid(rlhip_ctx* c, int64_t n, const T* d, int64_t k, int uniqu
     if (!count) return -11;
     if (!status) return -12;
     const int64_t nchunks = (n + SAMPLE_CHUNK - 1) / SAMPLE_CHUNK;
-    const size_t mark = rlhip_ws_mark(c);
-    double* S = ws_alloc<double>(c, (size_t)nchunks);
-    double* off = ws_alloc<double>(c, (size_t)nchunks + 1);
-    int64_t* lp = ws_alloc<int64_t>(c, (size_t)nchunks);
-    int* bad = ws_alloc<int>(c, (size_t)nchunks);
-    SampleHdr* hdr = ws_alloc<SampleHdr>(c, 1);
-    int64_t* out = out_dev ? out_dev : ws_alloc<int64_t>(c, (size_t)(k > 0 ? k : 1));
-    if (!S || !off || !lp || !bad || !hdr || !out) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    double* S = ws.alloc<double>((size_t)nchunks);
+    double* off = ws.alloc<double>((size_t)nchunks + 1);
+    int64_t* lp = ws.alloc<int64_t>((size_t)nchunks);
+    int* bad = ws.alloc<int>((size_t)nchunks);
+    SampleHdr* hdr = ws.alloc<SampleHdr>(1);
+    int64_t* out = out_dev ? out_dev : ws.alloc<int64_t>((size_t)(k > 0 ? k : 1));
+    if (!S || !off || !lp || !bad || !hdr || !out) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     const double eps = sizeof(T) == 8 ? (double)DBL_EPSILON : (double)FLT_EPSILON;
     hipLaunchKernelGGL(sample_partial_kernel<T>, dim3(grid1(nchunks, 256)), dim3(256), 0, c->stream, n, d, S, lp, bad, nchunks, -eps);
     hipLaunchKernelGGL(sample_scan_kernel, dim3(1), dim3(1024), 0, c->stream, n, nchunks, S, lp, bad, off, std::sqrt((double)n) * eps, hdr);
@@ -499,7 +497,6 @@ int sample_indices_iid(rlhip_ctx* c, int64_t n, const T* d, int64_t k, int uniqu
     if (e == hipSuccess) e = hipMemcpyAsync(c->h_mail + 60, hdr, sizeof(SampleHdr), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && out_host && k > 0) e = hipMemcpyAsync(out_host, out, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = rlhip_stream_sync(c);
-    rlhip_ws_release(c, mark);
     if (e != hipSuccess) return RLHIP_ERR_HIP(e);
     SampleHdr h;
     memcpy(&h, c->h_mail + 60, sizeof(SampleHdr));

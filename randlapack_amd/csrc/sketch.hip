@@ -866,10 +866,10 @@ int saso_build(rlhip_ctx* c, int64_t d, int64_t m, int nnz, int mode, const uint
                                op->src, op->src16);
             RLHIP_LAUNCH_CHECK();
         } else if (op->T > 0) {
-            size_t mark = rlhip_ws_mark(c);
-            int32_t* cnt = ws_alloc<int32_t>(c, nkeys);
-            int32_t* cursor = ws_alloc<int32_t>(c, nkeys);
-            if (!cnt || !cursor) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+            ws_scope ws(c);
+            int32_t* cnt = ws.alloc<int32_t>(nkeys);
+            int32_t* cursor = ws.alloc<int32_t>(nkeys);
+            if (!cnt || !cursor) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
             RLHIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int32_t) * nkeys, c->stream));
             RLHIP_CHECK(hipMemsetAsync(cursor, 0, sizeof(int32_t) * nkeys, c->stream));
             if (nnz <= 8) hipLaunchKernelGGL(saso_ind_gen_kernel<8>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, d, m, nnz, st, op->rows, cnt);
@@ -879,7 +879,6 @@ int saso_build(rlhip_ctx* c, int64_t d, int64_t m, int nnz, int mode, const uint
                                op->ptr, cursor, op->src);
             hipLaunchKernelGGL(saso_ind_sort_kernel, dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, c->stream, (int64_t)nkeys, op->ptr, op->src, op->src16);
             RLHIP_LAUNCH_CHECK();
-            rlhip_ws_release(c, mark);
         }
         inc = (uint64_t)m * (uint64_t)((nnz + 1) / 2);
     }
@@ -966,8 +965,8 @@ int saso_apply_rows(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T*
     const int64_t tpg_d = dma ? (nfb + G - 1) / G : tpg;
     if (dma) G = (nfb + tpg_d - 1) / tpg_d;
     const int64_t Gtot = G + head + tail;
-    size_t mark = rlhip_ws_mark(c);
-    T* partial = ws_alloc<T>(c, (size_t)Gtot * d * n);
+    ws_scope ws(c);
+    T* partial = ws.alloc<T>((size_t)Gtot * d * n);
     if (!partial) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     if (nTb == 0) RLHIP_CHECK(hipMemsetAsync(partial, 0, sizeof(T) * (size_t)(d * n), c->stream));
     // sketch rows per thread and pass: 5 (d <= 1280, the CQRRPT sketches of the benchmark configurations: 40 accumulator registers
@@ -1000,14 +999,13 @@ int saso_apply_rows(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T*
         } else if (op->mode == 1) rc = (CT == 4) ? RLHIP_SASO_LAUNCH(4, 1, partial, G, tpg, tb0, tb1) : (CT == 2) ? RLHIP_SASO_LAUNCH(2, 1, partial, G, tpg, tb0, tb1) : RLHIP_SASO_LAUNCH(1, 1, partial, G, tpg, tb0, tb1);
         else rc = (CT == 4) ? RLHIP_SASO_LAUNCH(4, 0, partial, G, tpg, tb0, tb1) : (CT == 2) ? RLHIP_SASO_LAUNCH(2, 0, partial, G, tpg, tb0, tb1) : RLHIP_SASO_LAUNCH(1, 0, partial, G, tpg, tb0, tb1);
 #undef RLHIP_SASO_LAUNCH
-        if (rc) { rlhip_ws_release(c, mark); return rc; }
+        if (rc) return rc;
     }
     RLHIP_LAUNCH_CHECK();
     const int64_t total = d * n;
     hipLaunchKernelGGL(saso_reduce_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, total, (int)Gtot,
                        partial, alpha, beta, B, d, ldb);
     RLHIP_LAUNCH_CHECK();
-    rlhip_ws_release(c, mark);
     return 0;
 }
 
@@ -1063,9 +1061,9 @@ int col_swap(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, T* A, int64_t lda, c
     if (k > n) return -3;                       // reference throws (rl_util.hh:159-160)
     if (m <= 0 || n <= 0) return 0;
     if (n < 4096 && (size_t)m * (size_t)n * sizeof(T) <= ((size_t)32 << 20)) {
-        const size_t mk = rlhip_ws_mark(c);
-        T* tmp = ws_alloc<T>(c, (size_t)m * n);
-        unsigned* seen = ws_alloc<unsigned>(c, (size_t)n / 32 + 2);
+        ws_scope ws(c);
+        T* tmp = ws.alloc<T>((size_t)m * n);
+        unsigned* seen = ws.alloc<unsigned>((size_t)n / 32 + 2);
         if (tmp && seen) {
             int* bad = (int*)(seen + n / 32 + 1);
             hipError_t he = hipMemsetAsync(seen, 0, ((size_t)n / 32 + 2) * sizeof(unsigned), c->stream);
@@ -1075,16 +1073,14 @@ int col_swap(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, T* A, int64_t lda, c
                 hipLaunchKernelGGL(colperm_store_kernel<T>, grid, dim3(256), 0, c->stream, m, tmp, A, lda, bad);
                 he = hipGetLastError();
             }
-            rlhip_ws_release(c, mk);
             return he == hipSuccess ? 0 : RLHIP_ERR_HIP(he);
-        }
-        rlhip_ws_release(c, mk);                // no scratch: the in-place cycle walk
+        }                                       // no scratch: the in-place cycle walk
     }
-    size_t mark = rlhip_ws_mark(c);
-    int64_t* moves = ws_alloc<int64_t>(c, (size_t)(2 * n + 2));
-    int64_t* nmoves = ws_alloc<int64_t>(c, 1);
-    unsigned char* seen = ws_alloc<unsigned char>(c, (size_t)n);
-    if (!moves || !nmoves || !seen) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    int64_t* moves = ws.alloc<int64_t>((size_t)(2 * n + 2));
+    int64_t* nmoves = ws.alloc<int64_t>(1);
+    unsigned char* seen = ws.alloc<unsigned char>((size_t)n);
+    if (!moves || !nmoves || !seen) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     std::vector<int64_t> h_chunk;
     int64_t* chunk_dev = nullptr;
     if (n >= 4096) {
@@ -1099,7 +1095,7 @@ int col_swap(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, T* A, int64_t lda, c
             if (h_seen[(size_t)i]) continue;
             h_seen[(size_t)i] = 1;
             int64_t s_ = h_idx[(size_t)i] - 1;
-            if (s_ < 0 || s_ >= n) { rlhip_ws_release(c, mark); return -7; }
+            if (s_ < 0 || s_ >= n) return -7;
             if (s_ == i) continue;
             h_moves[(size_t)w++] = -(i + 1);
             int64_t j = i;
@@ -1108,7 +1104,7 @@ int col_swap(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, T* A, int64_t lda, c
                 h_seen[(size_t)s_] = 1;
                 j = s_;
                 s_ = h_idx[(size_t)j] - 1;
-                if (s_ < 0 || s_ >= n || (s_ != i && h_seen[(size_t)s_])) { rlhip_ws_release(c, mark); return -7; }   // not a permutation
+                if (s_ < 0 || s_ >= n || (s_ != i && h_seen[(size_t)s_])) return -7;   // not a permutation
             }
         }
         // chunks of whole cycles for the apply kernel's second grid dimension: ~1024 workgroups in all, at least 64 moves per chunk
@@ -1126,7 +1122,7 @@ int col_swap(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, T* A, int64_t lda, c
         RLHIP_CHECK(hipMemcpyAsync(moves, h_moves.data(), sizeof(int64_t) * (size_t)std::max<int64_t>(w, 1), hipMemcpyHostToDevice, c->stream));
         RLHIP_CHECK(hipMemcpyAsync(nmoves, &h_moves[(size_t)(2 * n + 1)], sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
         if (h_chunk.size() > 2) {
-            chunk_dev = ws_alloc<int64_t>(c, h_chunk.size());
+            chunk_dev = ws.alloc<int64_t>(h_chunk.size());
             if (chunk_dev) RLHIP_CHECK(hipMemcpyAsync(chunk_dev, h_chunk.data(), sizeof(int64_t) * h_chunk.size(), hipMemcpyHostToDevice, c->stream));
         }
         RLHIP_CHECK(rlhip_stream_sync(c));           // the host vectors die at the end of this scope
@@ -1135,19 +1131,17 @@ int col_swap(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, T* A, int64_t lda, c
     hipLaunchKernelGGL(perm_apply_kernel<T>, dim3((unsigned)((m + 255) / 256), (unsigned)(chunk_dev ? h_chunk.size() - 1 : 1)), dim3(256), 0, c->stream, m, A, lda,
                        moves, nmoves, (const int64_t*)chunk_dev);
     RLHIP_LAUNCH_CHECK();
-    rlhip_ws_release(c, mark);
     return 0;
 }
 
 int col_swap_i64(rlhip_ctx* c, int64_t n, int64_t k, int64_t* A, const int64_t* idx_dev) {
     if (k > n) return -3;
     if (k <= 0) return 0;
-    size_t mark = rlhip_ws_mark(c);
-    int64_t* tmp = ws_alloc<int64_t>(c, (size_t)k);
+    ws_scope ws(c);
+    int64_t* tmp = ws.alloc<int64_t>((size_t)k);
     if (!tmp) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     hipLaunchKernelGGL(vec_gather_i64_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, k, A, idx_dev, tmp);
     RLHIP_CHECK(hipMemcpyAsync(A, tmp, sizeof(int64_t) * (size_t)k, hipMemcpyDeviceToDevice, c->stream));
-    rlhip_ws_release(c, mark);
     return 0;
 }
 

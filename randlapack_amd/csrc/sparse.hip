@@ -206,10 +206,10 @@ int csr_spmm(rlhip_ctx* c, int layout_rowmajor, int64_t nrows, int64_t k, int64_
              const T* vals, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {
     if (nrows <= 0 || nc <= 0) return 0;
     if (layout_rowmajor) return csr_spmm_rowmajor<T>(c, nrows, nc, rowptr, colidx, vals, alpha, B, ldb, beta, C, ldc);
-    const size_t mark = rlhip_ws_mark(c);
+    ws_scope ws(c);
     if (nc <= 32) {
-        T* Bt = ws_alloc<T>(c, (size_t)std::max<int64_t>(k, 1) * nc);
-        if (!Bt) { rlhip_ws_release(c, mark); return -3; }
+        T* Bt = ws.alloc<T>((size_t)std::max<int64_t>(k, 1) * nc);
+        if (!Bt) return -3;
         int rc = 0;
         if (k > 0) rc = transpose<T>(c, k, nc, B, ldb, Bt, nc, 0);
         if (!rc) {
@@ -219,18 +219,16 @@ int csr_spmm(rlhip_ctx* c, int layout_rowmajor, int64_t nrows, int64_t k, int64_
             const hipError_t le = hipGetLastError();
             if (le != hipSuccess) rc = RLHIP_ERR_HIP(le);
         }
-        rlhip_ws_release(c, mark);
         return rc;
     }
-    T* Bt = ws_alloc<T>(c, (size_t)std::max<int64_t>(k, 1) * nc);
-    T* Ct = ws_alloc<T>(c, (size_t)nrows * nc);
-    if (!Bt || !Ct) { rlhip_ws_release(c, mark); return -3; }
+    T* Bt = ws.alloc<T>((size_t)std::max<int64_t>(k, 1) * nc);
+    T* Ct = ws.alloc<T>((size_t)nrows * nc);
+    if (!Bt || !Ct) return -3;
     int rc = 0;
     if (k > 0) rc = transpose<T>(c, k, nc, B, ldb, Bt, nc, 0);          // Bt is nc x k column-major == k x nc row-major
     if (!rc && beta != (T)0) rc = transpose<T>(c, nrows, nc, C, ldc, Ct, nc, 0);
     if (!rc) rc = csr_spmm_rowmajor<T>(c, nrows, nc, rowptr, colidx, vals, alpha, Bt, nc, beta, Ct, nc);
     if (!rc) rc = transpose<T>(c, nc, nrows, Ct, nc, C, ldc, 0);
-    rlhip_ws_release(c, mark);
     return rc;
 }
 
@@ -463,12 +461,12 @@ int csr_transpose(rlhip_ctx* c, int64_t m, int64_t k, const int64_t* rowptr, con
     const int64_t nblk = (k + 1023) / 1024;
     int* d_bad = (int*)(c->d_mail + 51);
     unsigned long long* d_maxlen = (unsigned long long*)(c->d_mail + 52);
-    const size_t mark = rlhip_ws_mark(c);
-    int64_t* total = ws_alloc<int64_t>(c, (size_t)k);
-    int64_t* bsum = ws_alloc<int64_t>(c, (size_t)nblk + 1);
-    int64_t* rowid = ws_alloc<int64_t>(c, (size_t)(nnz > 0 ? nnz : 1));
-    int* cursor = ws_alloc<int>(c, (size_t)k);
-    if (!total || !bsum || !rowid || !cursor) { rlhip_ws_release(c, mark); return -3; }
+    ws_scope ws(c);
+    int64_t* total = ws.alloc<int64_t>((size_t)k);
+    int64_t* bsum = ws.alloc<int64_t>((size_t)nblk + 1);
+    int64_t* rowid = ws.alloc<int64_t>((size_t)(nnz > 0 ? nnz : 1));
+    int* cursor = ws.alloc<int>((size_t)k);
+    if (!total || !bsum || !rowid || !cursor) return -3;
     int rc = 0;
     do {
         // ---- column totals, row pointers of the transpose, the longest transposed row (one host read for it and the index check)
@@ -501,7 +499,7 @@ int csr_transpose(rlhip_ctx* c, int64_t m, int64_t k, const int64_t* rowptr, con
         const int64_t per = std::max<int64_t>(64, ((nnz + nb - 1) / nb + 63) / 64 * 64);
         nb = std::max<int64_t>(1, (nnz + per - 1) / per);
         if (per >= ((int64_t)1 << 31)) { rc = -2; break; }
-        int* cnt = ws_alloc<int>(c, (size_t)nb * k);
+        int* cnt = ws.alloc<int>((size_t)nb * k);
         if (!cnt) { rc = -3; break; }
         if (hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)nb * k, c->stream) != hipSuccess) { rc = -1; break; }
         hipLaunchKernelGGL(ct_count_kernel, dim3((unsigned)nb), dim3(256), 0, c->stream, nnz, per, k, colidx, cnt, d_bad);
@@ -509,7 +507,6 @@ int csr_transpose(rlhip_ctx* c, int64_t m, int64_t k, const int64_t* rowptr, con
         hipLaunchKernelGGL(ct_scatter_kernel<T>, dim3((unsigned)nb), dim3(64), 0, c->stream, m, nnz, per, k, rowptr, colidx, vals, rowptrT, cnt, colidxT, valsT, (const int64_t*)rowid);
         if (hipGetLastError() != hipSuccess) rc = -1;
     } while (0);
-    rlhip_ws_release(c, mark);
     return rc;
 }
 

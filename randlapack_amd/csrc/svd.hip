@@ -190,36 +190,35 @@ int gesdd_tall_gram(rlhip_ctx* c, int64_t m, int64_t n, const T* A, int64_t lda,
     else {
         if (c->opt[RLHIP_OPT_GESDD_GRAM] == 0 || n <= 32 || n > 256 || m < n) return 1;
         const int nn = (int)n;
-        size_t mark = rlhip_ws_mark(c);
-        T* G = ws_alloc<T>(c, (size_t)n * n);
-        T* Gf = ws_alloc<T>(c, (size_t)n * n);
-        T* W = ws_alloc<T>(c, (size_t)n * n);
-        T* M1 = ws_alloc<T>(c, (size_t)n * n);
-        T* sig = ws_alloc<T>(c, (size_t)n);
-        int64_t* mb = ws_alloc<int64_t>(c, 8);       // [0..3] the Jacobi launch's 8 ints, [4] defect (double); the launch clears all of it
-        if (!G || !Gf || !W || !M1 || !sig || !mb) { rlhip_ws_release(c, mark); return 1; }
+        ws_scope ws(c);
+        T* G = ws.alloc<T>((size_t)n * n);
+        T* Gf = ws.alloc<T>((size_t)n * n);
+        T* W = ws.alloc<T>((size_t)n * n);
+        T* M1 = ws.alloc<T>((size_t)n * n);
+        T* sig = ws.alloc<T>((size_t)n);
+        int64_t* mb = ws.alloc<int64_t>(8);       // [0..3] the Jacobi launch's 8 ints, [4] defect (double); the launch clears all of it
+        if (!G || !Gf || !W || !M1 || !sig || !mb) return 1;
         int* jout = (int*)mb;
         double* defect = (double*)(mb + 4);
         const unsigned g2 = (unsigned)((n * n + 255) / 256);
         int rc = laset<T>(c, 2, n, n, T(0), T(0), G, n);
         if (!rc) rc = syrk<T>(c, Upper, 1, n, m, T(1), A, lda, T(0), G, n);
-        if (rc) { rlhip_ws_release(c, mark); return rc < 0 ? rc : 1; }
+        if (rc) return rc < 0 ? rc : 1;
         hipLaunchKernelGGL(symmetrize_kernel<T>, dim3(g2), dim3(256), 0, c->stream, nn, G, n, Gf);
         const T* X = nullptr;
         rc = jacobi_enqueue_rt<T>(c, nn, Gf, n, 0, 1e6f, nullptr, jout, &X);     // squared norms of G J's columns = sigma^4: 1e6 <-> cond(A)^2 = 1e3
-        if (rc) { rlhip_ws_release(c, mark); return rc < 0 ? rc : 1; }
+        if (rc) return rc < 0 ? rc : 1;
         hipLaunchKernelGGL(gram_colnorm_kernel<T>, dim3((unsigned)n), dim3(256), 0, c->stream, nn, X, sig);
         hipLaunchKernelGGL(gram_finalize_kernel<T>, dim3((unsigned)n), dim3(256), 0, c->stream, nn, X, sig, W, S, VT, ldvt);
         RLHIP_LAUNCH_CHECK();
         rc = gemm<T>(c, 0, 0, m, n, n, T(1), A, lda, W, n, T(0), U, ldu);                 // U = A W
         if (!rc) rc = gemm<T>(c, 0, 0, n, n, n, T(1), Gf, n, W, n, T(0), M1, n);          // U^T U = W^T (G W)
         if (!rc) rc = gemm<T>(c, 1, 0, n, n, n, T(1), W, n, M1, n, T(0), G, n);
-        if (rc) { rlhip_ws_release(c, mark); return rc < 0 ? rc : 1; }
+        if (rc) return rc < 0 ? rc : 1;
         hipLaunchKernelGGL(identity_defect_kernel<T>, dim3(g2), dim3(256), 0, c->stream, nn, G, defect);            // (defect starts at 0: the Jacobi launch cleared the mailbox)
         RLHIP_LAUNCH_CHECK();
         hipError_t e = hipMemcpyAsync(c->h_mail + 32, mb, 5 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = rlhip_stream_sync(c);
-        rlhip_ws_release(c, mark);
         if (e != hipSuccess) return RLHIP_ERR_HIP(e);
         const int* jo = (const int*)(c->h_mail + 32);
         const double dv = *(const double*)(c->h_mail + 36);
@@ -243,12 +242,12 @@ static int gesdd_tall_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda
         const int grc = gesdd_tall_gram<T>(c, m, n, A, lda, S, U, ldu, VT, ldvt, sweeps_host);
         if (grc <= 0) return grc;
     }
-    size_t mark = rlhip_ws_mark(c);
-    T* R1 = ws_alloc<T>(c, (size_t)n * n);
-    T* R2 = ws_alloc<T>(c, (size_t)n * n);
-    T* X = ws_alloc<T>(c, (size_t)n * n);
-    T* VTx = ws_alloc<T>(c, (size_t)n * n);
-    if (!R1 || !R2 || !X || !VTx) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* R1 = ws.alloc<T>((size_t)n * n);
+    T* R2 = ws.alloc<T>((size_t)n * n);
+    T* X = ws.alloc<T>((size_t)n * n);
+    T* VTx = ws.alloc<T>((size_t)n * n);
+    if (!R1 || !R2 || !X || !VTx) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     int rc = 0, info = 0;
     bool fallback = false;
     double ratio = 0;
@@ -256,7 +255,7 @@ static int gesdd_tall_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda
     rc = laset<T>(c, 2, n, n, T(0), T(0), R1, n);
     if (!rc) rc = syrk<T>(c, Upper, 1, n, m, T(1), A, lda, T(0), R1, n);
     if (!rc) rc = potrf_upper<T>(c, n, R1, n, &info);
-    if (rc) { rlhip_ws_release(c, mark); return rc; }
+    if (rc) return rc;
     if (info) fallback = true;
     if (!fallback) {
         double* d_ratio = (double*)(c->d_mail + 24);
@@ -274,7 +273,7 @@ static int gesdd_tall_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda
         // ---- pass 2
         if (!rc) rc = laset<T>(c, 2, n, n, T(0), T(0), R2, n);
         if (!rc) rc = syrk<T>(c, Upper, 1, n, m, T(1), A, lda, T(0), R2, n);
-        if (rc) { rlhip_ws_release(c, mark); return rc; }
+        if (rc) return rc;
         // The Gram matrix of the first pass's Q says how orthonormal it already is.  A well-conditioned input (cond ~ 2 for the
         // B^T of an RSVD of a Gaussian matrix) leaves max |Q^T Q - I| at a few eps: the second factorization would multiply by a
         // triangle that equals the identity to rounding, so it is skipped (one k x k Cholesky + one m x k triangular solve +
@@ -289,16 +288,16 @@ static int gesdd_tall_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda
         }
         if (one_pass) {
             rc = lacpy<T>(c, 0, n, n, R1, n, R2, n);        // R = R1 (upper triangle; the strictly lower part of R2 is reset below)
-            if (rc) { rlhip_ws_release(c, mark); return rc; }
+            if (rc) return rc;
             info = 0;
         } else {
             rc = potrf_upper<T>(c, n, R2, n, &info);
-            if (rc) { rlhip_ws_release(c, mark); return rc; }
+            if (rc) return rc;
         }
         if (info) {
             // undo pass 1 on A (A = Q1 R1) and take the robust route
             rc = trmm_right_upper<T>(c, NonUnit, m, n, T(1), R1, n, A, lda);
-            if (rc) { rlhip_ws_release(c, mark); return rc; }
+            if (rc) return rc;
             fallback = true;
             c->path_count[20]++;
         }
@@ -308,9 +307,8 @@ static int gesdd_tall_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda
         int sw = 0;
         int jinfo = gesvdj_core<T>(c, m, n, A, lda, S, VT, ldvt, &sw);
         if (sweeps_host) *sweeps_host = sw;
-        if (jinfo < 0) { rlhip_ws_release(c, mark); return jinfo; }
+        if (jinfo < 0) return jinfo;
         rc = lacpy<T>(c, 2, m, n, A, lda, U, ldu);
-        rlhip_ws_release(c, mark);
         return rc ? rc : jinfo;
     }
     if (!one_pass) rc = trsm_right_upper<T>(c, NonUnit, m, n, T(1), R2, n, A, lda);   // A now holds Q (orthonormal)
@@ -319,7 +317,7 @@ static int gesdd_tall_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda
     if (!rc && !one_pass) rc = trmm_right_upper<T>(c, NonUnit, n, n, T(1), R1, n, R2, n);
     if (!rc) rc = laset<T>(c, 2, n, n, T(0), T(0), X, n);
     if (!rc) rc = transpose<T>(c, n, n, R2, n, X, n, 1);               // X = R^T (lower triangular)
-    if (rc) { rlhip_ws_release(c, mark); return rc; }
+    if (rc) return rc;
     int sw = 0;
     // Well-conditioned R (diag ratio < 1e3): the rotations need not be accumulated -- R Ux = Vx S gives Vx = (R Ux) S^-1 to
     // eps * cond(R); that removes the V-panel update (a quarter of every Jacobi launch).  Otherwise accumulate as usual.
@@ -332,14 +330,14 @@ static int gesdd_tall_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda
         if (!rc) rc = trsm_right_upper<T>(c, NonUnit, n, n, T(1), R2, n, VTx, n);
         if (!rc) rc = lange_fro<T>(c, n, n, R2, n, &nr);
         if (!rc) rc = lange_fro<T>(c, n, n, VTx, n, &ni);
-        if (rc) { rlhip_ws_release(c, mark); return rc; }
+        if (rc) return rc;
         recover_v = ((double)nr * (double)ni < ((sizeof(T) == 8) ? 1e3 : 30.0));
     }
     c->path_count[one_pass ? 17 : 16]++;
     if (recover_v) c->path_count[18]++;
     int jinfo = gesvdj_core<T>(c, n, n, X, n, S, recover_v ? (T*)nullptr : VTx, n, &sw);   // X = Ux S VTx
     if (sweeps_host) *sweeps_host = sw;
-    if (jinfo < 0) { rlhip_ws_release(c, mark); return jinfo; }
+    if (jinfo < 0) return jinfo;
     if (recover_v) {
         // VTx (used as scratch for Vx, NOT transposed here) = R * Ux, columns scaled by 1 / sigma;  U_out = Q * Vx
         rc = gemm<T>(c, 0, 0, n, n, n, T(1), R2, n, X, n, T(0), VTx, n);
@@ -354,7 +352,6 @@ static int gesdd_tall_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda
     }
     // VT_out = Ux^T
     if (!rc) rc = transpose<T>(c, n, n, X, n, VT, ldvt, 0);
-    rlhip_ws_release(c, mark);
     return rc ? rc : jinfo;
 }
 
@@ -372,14 +369,13 @@ int gesdd_tall(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* U
     if (ldvt < (n > 1 ? n : 1)) return -10;
     if (sweeps_host) *sweeps_host = 0;
     if (n == 0) return 0;
-    size_t mark = rlhip_ws_mark(c);
-    unsigned long long* w = ws_alloc<unsigned long long>(c, 4);
-    if (!w) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    unsigned long long* w = ws.alloc<unsigned long long>(4);
+    if (!w) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     int rc = svd_guard_begin<T>(c, m, n, A, lda, w);
     int info = 0;
     if (!rc) info = gesdd_tall_core<T>(c, m, n, A, lda, S, U, ldu, VT, ldvt, sweeps_host);
     if (!rc && info >= 0) rc = svd_guard_end<T>(c, n, S, w);
-    rlhip_ws_release(c, mark);
     return rc ? rc : info;
 }
 

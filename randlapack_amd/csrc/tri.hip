@@ -786,21 +786,21 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
     if (lda < (n > 1 ? n : 1)) return -10;
     if (ldb < (m > 1 ? m : 1)) return -12;
     if (m == 0 || n == 0) return 0;
-    size_t mark = rlhip_ws_mark(c);
-    T* Ut = ws_alloc<T>(c, (size_t)SB * SB);
+    ws_scope ws(c);
+    T* Ut = ws.alloc<T>((size_t)SB * SB);
     if (!Ut) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     // blk path (one MFMA launch per 256-block): needs the explicit inverses of the 32 x 32 diagonal blocks, so it is taken per block
     // only where those are well conditioned (kappa_F <= 1e3: error eps * kappa stays at 1e-13); graded triangles -- the R factor of an
     // ill-conditioned sketch in CQRRPT's preconditioning step -- keep the componentwise-stable substitution kernels.
     const int64_t nblk = (n + BW - 1) / BW;
     const bool try_blk = m >= 16 && n >= 128 && nblk <= 32;   // narrow solves (orhr_col, potrf panels: n = 32) are one pack + one substitution launch already
-    T* Upk_all = try_blk ? ws_alloc<T>(c, (size_t)nblk * BW * BW) : nullptr;
-    T* Dinv_all = try_blk ? ws_alloc<T>(c, (size_t)nblk * (BW / 32) * 1024) : nullptr;
-    int* bad_dev = try_blk ? ws_alloc<int>(c, 32) : nullptr;
+    T* Upk_all = try_blk ? ws.alloc<T>((size_t)nblk * BW * BW) : nullptr;
+    T* Dinv_all = try_blk ? ws.alloc<T>((size_t)nblk * (BW / 32) * 1024) : nullptr;
+    int* bad_dev = try_blk ? ws.alloc<int>(32) : nullptr;
     int bad_host[32];
     for (int i = 0; i < 32; ++i) bad_host[i] = 1;
     if (try_blk) {
-        if (!Upk_all || !Dinv_all || !bad_dev) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+        if (!Upk_all || !Dinv_all || !bad_dev) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
         RLHIP_CHECK(hipMemsetAsync(bad_dev, 0, 32 * sizeof(int), c->stream));
         hipLaunchKernelGGL(trsm_blk_pack_kernel<T>, dim3(BW / 32 + 24, (unsigned)nblk), dim3(256), 0, c->stream, n, diag, A, lda, Upk_all, Dinv_all, bad_dev,
                            1.0e6);
@@ -832,12 +832,12 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
         bool any_good = false;
         for (int64_t b = 0; (b + 1) * BW <= n; ++b) any_good |= !bad_host[b];   // (a ragged last block stays on the blk path)
         if (any_good) {
-            Uneg = ws_alloc<T>(c, (size_t)n_pad * n_pad);
-            if (!Uneg) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+            Uneg = ws.alloc<T>((size_t)n_pad * n_pad);
+            if (!Uneg) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
             hipLaunchKernelGGL(trsm_neg_pack_kernel<T>, dim3((unsigned)(n_pad / 32), (unsigned)(n_pad / 32)), dim3(256), 0, c->stream, n, n_pad, A, lda, Uneg);
             RLHIP_LAUNCH_CHECK();
-            fdump = ws_alloc<T>(c, 512 + 64);
-            if (!fdump) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+            fdump = ws.alloc<T>(512 + 64);
+            if (!fdump) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
         }
     }
     for (int64_t j0 = 0; j0 < n; j0 += DB) {
@@ -851,13 +851,13 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
             const int64_t jend = (Je * (int64_t)BW < n) ? Je * (int64_t)BW : n;
             if (j0 > 0) {
                 int rc = gemm_impl<T>(c, 0, 0, m, jend - j0, j0, T(-1), B, ldb, A + j0 * lda, lda, alpha, B + j0 * ldb, ldb, 0);
-                if (rc) { rlhip_ws_release(c, mark); return rc; }
+                if (rc) return rc;
                 a = T(1);
             }
             {
                 const int lrc = tf_launch<T, 0>(c, m, n, n_pad, a, Uneg, Dinv_all, B, ldb, Jb, Je, Jb, fdump, (const T*)nullptr, (int64_t)0, (const int64_t*)nullptr, (int64_t)0,
                                                     (const int*)nullptr, 0);
-                if (lrc) { rlhip_ws_release(c, mark); return lrc; }
+                if (lrc) return lrc;
             }
 #ifdef RLHIP_TF_PROF
             {
@@ -875,7 +875,7 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
         }
         if (j0 > 0) {
             int rc = gemm_impl<T>(c, 0, 0, m, nb, j0, T(-1), B, ldb, A + j0 * lda, lda, alpha, B + j0 * ldb, ldb, 0);
-            if (rc) { rlhip_ws_release(c, mark); return rc; }
+            if (rc) return rc;
             a = T(1);
         }
         if (try_blk && !bad_host[j0 / BW]) {
@@ -892,7 +892,7 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
                     const int64_t jc = j0 + h0;
                     // columns [j0, jc) of this block (the columns left of j0 went in above, with alpha)
                     int rc = gemm_impl<T>(c, 0, 0, m, hb, h0, T(-1), B + j0 * ldb, ldb, A + j0 + jc * lda, lda, a, B + jc * ldb, ldb, 0);
-                    if (rc) { rlhip_ws_release(c, mark); return rc; }
+                    if (rc) return rc;
                     ah = T(1);
                 }
                 if (m >= 65536)       // enough rows to fill the chip with 128-row workgroups: two row tiles per wave halve the U-fragment traffic (four: slower, 108.6 vs 105.5 ms at C3)
@@ -912,7 +912,7 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
             if (s0 > 0) {
                 int rc = gemm_impl<T>(c, 0, 0, m, sbw, s0, T(-1), B + j0 * ldb, ldb, A + j0 + jc * lda, lda, a, B + jc * ldb,
                                       ldb, 0);
-                if (rc) { rlhip_ws_release(c, mark); return rc; }
+                if (rc) return rc;
                 a2 = T(1);
             }
             hipLaunchKernelGGL(pack_upper_rows_kernel<T>, dim3((SB * SB + 255) / 256), dim3(256), 0, c->stream, sbw, SB, diag,
@@ -923,7 +923,6 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
             c->path_count[3]++;
         }
     }
-    rlhip_ws_release(c, mark);
     return 0;
 }
 
@@ -944,56 +943,53 @@ int trsm_right_upper_oop(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, 
     if ((const T*)B == Bsrc) { if (perm_dev) return -14; return trsm_right_upper<T>(c, diag, m, n, alpha, A, lda, B, ldb); }
     const int64_t nblk = (n + BW - 1) / BW;
     bool fused = m >= TF_MIN_ROWS && n >= BW && n % BW == 0 && nblk <= 32 && (4 * ldb + m) < ((int64_t)1 << 28);
-    size_t mark = rlhip_ws_mark(c);
     bool perm_checked = false;
     if (fused) {
-        T* Upk_all = ws_alloc<T>(c, (size_t)nblk * BW * BW);
-        T* Dinv_all = ws_alloc<T>(c, (size_t)nblk * (BW / 32) * 1024);
-        int* bad_dev = ws_alloc<int>(c, 40);
-        unsigned* seen = ws_alloc<unsigned>(c, (size_t)n / 32 + 2);
-        T* Uneg = ws_alloc<T>(c, (size_t)n * n);
-        T* fdump = ws_alloc<T>(c, 512);
-        if (!Upk_all || !Dinv_all || !bad_dev || !seen || !Uneg || !fdump) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
-        auto chk = [&](hipError_t e) { if (e != hipSuccess) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(e); } return 0; };   // every error exit gives the arena mark back
-        if (int rc = chk(hipMemsetAsync(bad_dev, 0, 33 * sizeof(int), c->stream))) return rc;
+        ws_scope ws(c);
+        T* Upk_all = ws.alloc<T>((size_t)nblk * BW * BW);
+        T* Dinv_all = ws.alloc<T>((size_t)nblk * (BW / 32) * 1024);
+        int* bad_dev = ws.alloc<int>(40);
+        unsigned* seen = ws.alloc<unsigned>((size_t)n / 32 + 2);
+        T* Uneg = ws.alloc<T>((size_t)n * n);
+        T* fdump = ws.alloc<T>(512);
+        if (!Upk_all || !Dinv_all || !bad_dev || !seen || !Uneg || !fdump) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
+        RLHIP_CHECK(hipMemsetAsync(bad_dev, 0, 33 * sizeof(int), c->stream));
         hipLaunchKernelGGL(trsm_blk_pack_kernel<T>, dim3(BW / 32 + 24, (unsigned)nblk), dim3(256), 0, c->stream, n, diag, A, lda, Upk_all, Dinv_all, bad_dev,
                            1.0e6);
-        if (int rc = chk(hipGetLastError())) return rc;
+        RLHIP_LAUNCH_CHECK();
         if (perm_dev) {     // the pivot vector is validated on the device; its verdict rides on the guard's read-back (slot 32)
-            if (int rc = chk(hipMemsetAsync(seen, 0, ((size_t)n + 31) / 32 * sizeof(unsigned), c->stream))) return rc;
+            RLHIP_CHECK(hipMemsetAsync(seen, 0, ((size_t)n + 31) / 32 * sizeof(unsigned), c->stream));
             hipLaunchKernelGGL(perm_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, perm_dev, (int64_t)1, seen, bad_dev + 32, n);
-            if (int rc = chk(hipGetLastError())) return rc;
+            RLHIP_LAUNCH_CHECK();
             perm_checked = true;
         }
         // The verdict (33 words: the conditioning guard of every block, the pivot check) travels to the host while the device runs on: the
         // packed triangle and the fused solve are enqueued right behind the read-back, GATED on the same device words (a launch that finds
         // one of them set does nothing), and the host waits for the read-back only -- no idle device during the round trip.
-        if (int rc = chk(hipMemcpyAsync(c->h_mail + 16, bad_dev, 33 * sizeof(int), hipMemcpyDeviceToHost, c->stream))) return rc;
-        if (int rc = chk(hipEventRecord(c->ev_flag, c->stream))) return rc;
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 16, bad_dev, 33 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipEventRecord(c->ev_flag, c->stream));
         hipLaunchKernelGGL(trsm_neg_pack_kernel<T>, dim3((unsigned)(n / 32), (unsigned)(n / 32)), dim3(256), 0, c->stream, n, n, A, lda, Uneg);
-        if (int rc = chk(hipGetLastError())) return rc;
+        RLHIP_LAUNCH_CHECK();
         {
             // (no pivot vector: the identity-column twin of the kernel, when the source's lane offsets fit 32 bits too)
             const bool ident = !perm_dev && (4 * ldsrc + m) < ((int64_t)1 << 28);
             const int lrc = ident ? tf_launch<T, 2>(c, m, n, n, alpha, Uneg, Dinv_all, B, ldb, 0, (int)nblk, 0, fdump, Bsrc, ldsrc, perm_dev, (int64_t)1, (const int*)bad_dev, 33)
                                   : tf_launch<T, 1>(c, m, n, n, alpha, Uneg, Dinv_all, B, ldb, 0, (int)nblk, 0, fdump, Bsrc, ldsrc, perm_dev, (int64_t)1, (const int*)bad_dev, 33);
-            if (lrc) { rlhip_ws_release(c, mark); return lrc; }
+            if (lrc) return lrc;
         }
-        if (int rc = chk(hipEventSynchronize(c->ev_flag))) return rc;
-        if (perm_checked && ((int*)(c->h_mail + 16))[32] != 0) { rlhip_ws_release(c, mark); return -7; }     // jpvt is not a permutation of 1..n (as col_swap reports it)
+        RLHIP_CHECK(hipEventSynchronize(c->ev_flag));
+        if (perm_checked && ((int*)(c->h_mail + 16))[32] != 0) return -7;     // jpvt is not a permutation of 1..n (as col_swap reports it)
         for (int64_t b = 0; b < nblk; ++b) fused = fused && ((int*)(c->h_mail + 16))[b] == 0;
         if (fused) {
             c->path_count[4]++;
-            rlhip_ws_release(c, mark);
             return 0;
         }
     }
-    rlhip_ws_release(c, mark);
     if (perm_dev && !perm_checked) {     // gather-copy route: validate before anything is written
-        size_t mk2 = rlhip_ws_mark(c);
-        unsigned* seen = ws_alloc<unsigned>(c, (size_t)n / 32 + 2);
-        int* bad = ws_alloc<int>(c, 8);
-        if (!seen || !bad) { rlhip_ws_release(c, mk2); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+        ws_scope ws(c);
+        unsigned* seen = ws.alloc<unsigned>((size_t)n / 32 + 2);
+        int* bad = ws.alloc<int>(8);
+        if (!seen || !bad) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
         hipError_t pe = hipMemsetAsync(seen, 0, ((size_t)n + 31) / 32 * sizeof(unsigned), c->stream);
         if (pe == hipSuccess) pe = hipMemsetAsync(bad, 0, sizeof(int), c->stream);
         if (pe == hipSuccess) {
@@ -1002,7 +998,6 @@ int trsm_right_upper_oop(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, 
         }
         if (pe == hipSuccess) pe = hipMemcpyAsync(c->h_mail + 16, bad, sizeof(int), hipMemcpyDeviceToHost, c->stream);
         if (pe == hipSuccess) pe = rlhip_stream_sync(c);
-        rlhip_ws_release(c, mk2);
         if (pe != hipSuccess) return RLHIP_ERR_HIP(pe);
         if (*(int*)(c->h_mail + 16) != 0) return -7;
     }
@@ -1036,14 +1031,14 @@ int trsm_right_upper_oop_range(rlhip_ctx* c, int diag, int64_t m, int64_t nsrc, 
     if ((const T*)B == Bsrc) return -14;
     const int64_t n = col1, nblk = n / BW;
     if (m < TF_MIN_ROWS || nblk > 32 || (4 * ldb + m) >= ((int64_t)1 << 28)) return 1;
-    size_t mark = rlhip_ws_mark(c);
-    T* Upk_all = ws_alloc<T>(c, (size_t)nblk * BW * BW);
-    T* Dinv_all = ws_alloc<T>(c, (size_t)nblk * (BW / 32) * 1024);
-    int* bad_dev = ws_alloc<int>(c, 40);
-    unsigned* seen = ws_alloc<unsigned>(c, (size_t)nsrc / 32 + 2);
-    T* Uneg = ws_alloc<T>(c, (size_t)n * n);
-    T* fdump = ws_alloc<T>(c, 512);
-    if (!Upk_all || !Dinv_all || !bad_dev || !seen || !Uneg || !fdump) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* Upk_all = ws.alloc<T>((size_t)nblk * BW * BW);
+    T* Dinv_all = ws.alloc<T>((size_t)nblk * (BW / 32) * 1024);
+    int* bad_dev = ws.alloc<int>(40);
+    unsigned* seen = ws.alloc<unsigned>((size_t)nsrc / 32 + 2);
+    T* Uneg = ws.alloc<T>((size_t)n * n);
+    T* fdump = ws.alloc<T>(512);
+    if (!Upk_all || !Dinv_all || !bad_dev || !seen || !Uneg || !fdump) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     hipError_t he = hipMemsetAsync(bad_dev, 0, 33 * sizeof(int), c->stream);
     if (he == hipSuccess) {
         hipLaunchKernelGGL(trsm_blk_pack_kernel<T>, dim3(BW / 32 + 24, (unsigned)nblk), dim3(256), 0, c->stream, n, diag, A, lda, Upk_all, Dinv_all, bad_dev, 1.0e6);
@@ -1060,7 +1055,7 @@ int trsm_right_upper_oop_range(rlhip_ctx* c, int diag, int64_t m, int64_t nsrc, 
     //  whole-matrix form above)
     if (he == hipSuccess) he = hipMemcpyAsync(c->h_mail + 16, bad_dev, 33 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (he == hipSuccess) he = hipEventRecord(c->ev_flag, c->stream);
-    if (he != hipSuccess) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(he); }
+    if (he != hipSuccess) return RLHIP_ERR_HIP(he);
     hipLaunchKernelGGL(trsm_neg_pack_kernel<T>, dim3((unsigned)(n / 32), (unsigned)(n / 32)), dim3(256), 0, c->stream, n, n, A, lda, Uneg);
     he = hipGetLastError();
     int lrc = (he == hipSuccess) ? 0 : RLHIP_ERR_HIP(he);
@@ -1074,7 +1069,6 @@ int trsm_right_upper_oop_range(rlhip_ctx* c, int diag, int64_t m, int64_t nsrc, 
         if (!good) lrc = 1;                       // the gated launch did nothing
     }
     if (!lrc) c->path_count[4]++;
-    rlhip_ws_release(c, mark);
     return lrc;
 }
 
@@ -1086,16 +1080,15 @@ int trmm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
     if (lda < (n > 1 ? n : 1)) return -10;
     if (ldb < (m > 1 ? m : 1)) return -12;
     if (m == 0 || n == 0) return 0;
-    size_t mark = rlhip_ws_mark(c);
-    T* W = ws_alloc<T>(c, (size_t)n * n);
-    T* Bc = ws_alloc<T>(c, (size_t)m * n);
-    if (!W || !Bc) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* W = ws.alloc<T>((size_t)n * n);
+    T* Bc = ws.alloc<T>((size_t)m * n);
+    if (!W || !Bc) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     hipLaunchKernelGGL(copy_triu_kernel<T>, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, c->stream, n, diag, A,
                        lda, W);
     RLHIP_LAUNCH_CHECK();
     int rc = lacpy<T>(c, 2, m, n, B, ldb, Bc, m);
     if (!rc) rc = gemm_impl<T>(c, 0, 0, m, n, n, alpha, Bc, m, W, n, T(0), B, ldb, 0);
-    rlhip_ws_release(c, mark);
     return rc;
 }
 
@@ -1108,15 +1101,14 @@ int trmm_left_upper(rlhip_ctx* c, int trans, int diag, int64_t m, int64_t n, T a
     if (lda < (m > 1 ? m : 1)) return -10;
     if (ldb < (m > 1 ? m : 1)) return -12;
     if (m == 0 || n == 0) return 0;
-    size_t mark = rlhip_ws_mark(c);
-    T* W = ws_alloc<T>(c, (size_t)m * m);
-    T* Bc = ws_alloc<T>(c, (size_t)m * n);
-    if (!W || !Bc) { rlhip_ws_release(c, mark); return RLHIP_ERR_HIP(hipErrorOutOfMemory); }
+    ws_scope ws(c);
+    T* W = ws.alloc<T>((size_t)m * m);
+    T* Bc = ws.alloc<T>((size_t)m * n);
+    if (!W || !Bc) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     hipLaunchKernelGGL(copy_triu_kernel<T>, dim3((unsigned)((m * m + 255) / 256)), dim3(256), 0, c->stream, m, diag, A, lda, W);
     RLHIP_LAUNCH_CHECK();
     int rc = lacpy<T>(c, 2, m, n, B, ldb, Bc, m);
     if (!rc) rc = gemm_impl<T>(c, trans ? 1 : 0, 0, m, n, m, alpha, W, m, Bc, m, T(0), B, ldb, 0);
-    rlhip_ws_release(c, mark);
     return rc;
 }
 template int trmm_left_upper<double>(rlhip_ctx*, int, int, int64_t, int64_t, double, const double*, int64_t, double*, int64_t);
@@ -1143,61 +1135,62 @@ int cholqrq(rlhip_ctx* c, int64_t m, int64_t k, T* A, int64_t lda, T* R, int red
     bool local_ok = m >= TF_MIN_ROWS && (4 * lda + m) < ((int64_t)1 << 28);
     if (!reduce_gram && !local_ok) return 1;
     *info_host = 0;
-    size_t mark = rlhip_ws_mark(c);
-    auto fail = [&](int rc) { rlhip_ws_release(c, mark); return rc; };
-    int* words = ws_alloc<int>(c, 40);                            // [0] potrf info, [1 .. nblk] guard verdicts
-    if (!words) { rlhip_ws_release(c, mark); return reduce_gram ? RLHIP_ERR_HIP(hipErrorOutOfMemory) : 1; }
-    T *Upk_all = nullptr, *Dinv_all = nullptr, *Uneg = nullptr, *fdump = nullptr;
-    if (local_ok) {
-        Upk_all = ws_alloc<T>(c, (size_t)nblk * BW * BW);
-        Dinv_all = ws_alloc<T>(c, (size_t)nblk * (BW / 32) * 1024);
-        Uneg = ws_alloc<T>(c, (size_t)k * k);
-        fdump = ws_alloc<T>(c, 512 + 64);
-        if (!Upk_all || !Dinv_all || !Uneg || !fdump) {
-            if (!reduce_gram) return fail(1);
-            local_ok = false;                                     // (rank-local: the substitution route below needs none of them)
-        }
-    }
-    hipError_t e0 = hipMemsetAsync(words, 0, 40 * sizeof(int), c->stream);
-    if (e0 != hipSuccess) return fail(RLHIP_ERR_HIP(e0));
-    int rc = laset<T>(c, 2, k, k, T(0), T(0), R, k);
-    if (!rc && m > 0) rc = syrk<T>(c, Upper, 1, k, m, T(1), A, lda, T(0), R, k);
-    if (!rc && reduce_gram) {
-        if (sizeof(T) == 8 && c->norma_state == 1 && !c->norma_reduced) {
-            // a deferred ||A||_F^2 is waiting (QB: rl_qb.hh:168): its sum over the ranks rides on THIS all-reduce as word k*k of the buffer instead
-            // of taking a scalar collective (and a host round trip) of its own.  (norma_state is set by the product that precedes this call on
-            // EVERY rank -- rank-uniform.)
-            double* G2 = ws_alloc<double>(c, (size_t)k * k + 1);
-            if (!G2) return fail(RLHIP_ERR_HIP(hipErrorOutOfMemory));
-            hipError_t e = hipMemcpyAsync(G2, R, (size_t)k * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(G2 + (size_t)k * k, (double*)(c->d_mail + 40), sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-            if (e != hipSuccess) return fail(RLHIP_ERR_HIP(e));
-            rc = rlhip_allreduce_sum_f64(c, G2, k * k + 1);
-            if (!rc) {
-                e = hipMemcpyAsync(R, G2, (size_t)k * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-                if (e == hipSuccess) e = hipMemcpyAsync(c->h_mail + 41, G2 + (size_t)k * k, sizeof(double), hipMemcpyDeviceToHost, c->stream);
-                if (e != hipSuccess) return fail(RLHIP_ERR_HIP(e));
-                c->norma_reduced = 1;
+    hipError_t e1 = hipSuccess;
+    {
+        ws_scope ws(c);
+        int* words = ws.alloc<int>(40);                            // [0] potrf info, [1 .. nblk] guard verdicts
+        if (!words) return reduce_gram ? RLHIP_ERR_HIP(hipErrorOutOfMemory) : 1;
+        T *Upk_all = nullptr, *Dinv_all = nullptr, *Uneg = nullptr, *fdump = nullptr;
+        if (local_ok) {
+            Upk_all = ws.alloc<T>((size_t)nblk * BW * BW);
+            Dinv_all = ws.alloc<T>((size_t)nblk * (BW / 32) * 1024);
+            Uneg = ws.alloc<T>((size_t)k * k);
+            fdump = ws.alloc<T>(512 + 64);
+            if (!Upk_all || !Dinv_all || !Uneg || !fdump) {
+                if (!reduce_gram) return 1;
+                local_ok = false;                                     // (rank-local: the substitution route below needs none of them)
             }
-        } else {
-            rc = (sizeof(T) == 8) ? rlhip_allreduce_sum_f64(c, (double*)R, k * k) : rlhip_allreduce_sum_f32(c, (float*)R, k * k);
         }
-    }
-    if (!rc) rc = potrf_upper_enqueue<T>(c, k, R, k, words);
-    if (rc) return fail(rc < 0 ? rc : RLHIP_ERR_HIP(hipErrorUnknown));
-    if (local_ok) {
-        hipLaunchKernelGGL(trsm_blk_pack_kernel<T>, dim3(BW / 32 + 24, (unsigned)nblk), dim3(256), 0, c->stream, k, (int)NonUnit, R, k, Upk_all, Dinv_all, words + 1, 1.0e6);
-        hipLaunchKernelGGL(trsm_neg_pack_kernel<T>, dim3((unsigned)(k / 32), (unsigned)(k / 32)), dim3(256), 0, c->stream, k, k, R, k, Uneg);
-        {
-            hipError_t le = hipGetLastError();
-            if (le != hipSuccess) return fail(RLHIP_ERR_HIP(le));
+        hipError_t e0 = hipMemsetAsync(words, 0, 40 * sizeof(int), c->stream);
+        if (e0 != hipSuccess) return RLHIP_ERR_HIP(e0);
+        int rc = laset<T>(c, 2, k, k, T(0), T(0), R, k);
+        if (!rc && m > 0) rc = syrk<T>(c, Upper, 1, k, m, T(1), A, lda, T(0), R, k);
+        if (!rc && reduce_gram) {
+            if (sizeof(T) == 8 && c->norma_state == 1 && !c->norma_reduced) {
+                // a deferred ||A||_F^2 is waiting (QB: rl_qb.hh:168): its sum over the ranks rides on THIS all-reduce as word k*k of the buffer instead
+                // of taking a scalar collective (and a host round trip) of its own.  (norma_state is set by the product that precedes this call on
+                // EVERY rank -- rank-uniform.)
+                double* G2 = ws.alloc<double>((size_t)k * k + 1);
+                if (!G2) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
+                hipError_t e = hipMemcpyAsync(G2, R, (size_t)k * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+                if (e == hipSuccess) e = hipMemcpyAsync(G2 + (size_t)k * k, (double*)(c->d_mail + 40), sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+                if (e != hipSuccess) return RLHIP_ERR_HIP(e);
+                rc = rlhip_allreduce_sum_f64(c, G2, k * k + 1);
+                if (!rc) {
+                    e = hipMemcpyAsync(R, G2, (size_t)k * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+                    if (e == hipSuccess) e = hipMemcpyAsync(c->h_mail + 41, G2 + (size_t)k * k, sizeof(double), hipMemcpyDeviceToHost, c->stream);
+                    if (e != hipSuccess) return RLHIP_ERR_HIP(e);
+                    c->norma_reduced = 1;
+                }
+            } else {
+                rc = (sizeof(T) == 8) ? rlhip_allreduce_sum_f64(c, (double*)R, k * k) : rlhip_allreduce_sum_f32(c, (float*)R, k * k);
+            }
         }
-        rc = tf_launch<T, 0>(c, m, k, k, T(1), Uneg, Dinv_all, A, lda, 0, (int)nblk, 0, fdump, (const T*)nullptr, (int64_t)0, (const int64_t*)nullptr, (int64_t)0, words, 1 + (int)nblk);
-        if (rc) return fail(rc);
+        if (!rc) rc = potrf_upper_enqueue<T>(c, k, R, k, words);
+        if (rc) return rc < 0 ? rc : RLHIP_ERR_HIP(hipErrorUnknown);
+        if (local_ok) {
+            hipLaunchKernelGGL(trsm_blk_pack_kernel<T>, dim3(BW / 32 + 24, (unsigned)nblk), dim3(256), 0, c->stream, k, (int)NonUnit, R, k, Upk_all, Dinv_all, words + 1, 1.0e6);
+            hipLaunchKernelGGL(trsm_neg_pack_kernel<T>, dim3((unsigned)(k / 32), (unsigned)(k / 32)), dim3(256), 0, c->stream, k, k, R, k, Uneg);
+            {
+                hipError_t le = hipGetLastError();
+                if (le != hipSuccess) return RLHIP_ERR_HIP(le);
+            }
+            rc = tf_launch<T, 0>(c, m, k, k, T(1), Uneg, Dinv_all, A, lda, 0, (int)nblk, 0, fdump, (const T*)nullptr, (int64_t)0, (const int64_t*)nullptr, (int64_t)0, words, 1 + (int)nblk);
+            if (rc) return rc;
+        }
+        e1 = hipMemcpyAsync(c->h_mail + 44, words, 40 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+        if (e1 == hipSuccess) e1 = rlhip_stream_sync(c);
     }
-    hipError_t e1 = hipMemcpyAsync(c->h_mail + 44, words, 40 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    if (e1 == hipSuccess) e1 = rlhip_stream_sync(c);
-    rlhip_ws_release(c, mark);
     if (e1 != hipSuccess) return RLHIP_ERR_HIP(e1);
     const int* w = (const int*)(c->h_mail + 44);
     *info_host = w[0];
