@@ -1,16 +1,11 @@
 // HBM-bound helper kernels: norms, copies, fills.  Lanes always run along the contiguous (row)
 // direction of the column-major operands so every wavefront touches whole 512-byte segments.
 #include <cstring>
-#include "rlhip_internal.h"
+#include "rlhip_device.h"
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
+using namespace rlhip_dev;   // wave_sum
 
 // block-level sum, result valid in thread 0
 template <typename T, int NT>

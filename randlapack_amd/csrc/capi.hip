@@ -1,47 +1,8 @@
 // extern "C" surface of librlhip.so (declared in include/rlhip.h) + context / scratch-arena management.
 #include "rlhip_internal.h"
-#include "../../include/rlhip.h"
 #include <cstring>
 #include <cstdlib>
 #include <dlfcn.h>
-
-namespace rlhip {
-struct SasoOp;
-int saso_build(rlhip_ctx* c, int64_t d, int64_t m, int nnz, int mode, const uint32_t ctr[4], const uint32_t key[2],
-               uint32_t next_ctr[4], SasoOp** out);
-int saso_destroy(rlhip_ctx* c, SasoOp* op);
-template <typename T> int saso_dense(rlhip_ctx* c, const SasoOp* op, T* S);
-template <typename T> int saso_apply_rows(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T* A, int64_t lda, int64_t row0, int64_t mloc,
-                                          T beta, T* B, int64_t ldb);
-template <typename T> int saso_apply(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T* A, int64_t lda, T beta,
-                                     T* B, int64_t ldb);
-template <typename T> int saso_apply_csr(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const int64_t* rowptrT, const int64_t* colidxT,
-                                         const T* valsT, T beta, T* B, int64_t ldb, int64_t row0);
-template <typename T> int col_swap(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, T* A, int64_t lda, const int64_t* idx);
-template <typename T> int cholqrq(rlhip_ctx* c, int64_t m, int64_t k, T* A, int64_t lda, T* R, int reduce_gram, int* info_host);
-int col_swap_i64(rlhip_ctx* c, int64_t n, int64_t k, int64_t* A, const int64_t* idx_dev);
-template <typename T> int geqp3(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* jpvt_dev, T* tau_dev);
-template <typename T> int orhr_col(rlhip_ctx*, int64_t, int64_t, int64_t, T*, int64_t, T*, int64_t, T*);
-template <typename T> int geqrf_q(rlhip_ctx*, int64_t, int64_t, T*, int64_t, T*, int64_t, int*);
-template <typename T> int gemqrt_lt(rlhip_ctx*, int64_t, int64_t, int64_t, int64_t, const T*, int64_t, const T*, int64_t, T*, int64_t);
-template <typename T> int gemqrt_lt_head(rlhip_ctx*, int64_t, int64_t, int64_t, const T*, int64_t, const T*, int64_t, T*, int64_t, T*);
-template <typename T> int gemqrt_lt_tail(rlhip_ctx*, int64_t, int64_t, int64_t, const T*, int64_t, const T*, T*, int64_t);
-template <typename T> int larft_gram(rlhip_ctx*, int64_t, int64_t, const T*, int64_t, const T*, T*, int64_t);
-template <typename T> int row_sign(rlhip_ctx*, int64_t, T*, int64_t, const T*);
-template <typename T> int tau_from_t(rlhip_ctx*, int64_t, int64_t, const T*, int64_t, T*);
-template <typename T> int any_abs_gt(rlhip_ctx*, int64_t, const T*, T, int*);
-template <typename T> int getrf(rlhip_ctx*, int64_t, int64_t, T*, int64_t, int64_t*, int*, int pivots_only);
-int luqrcp_piv(rlhip_ctx*, int64_t, int64_t, const int64_t*, int64_t*);
-template <typename T> int geqrf(rlhip_ctx*, int64_t, int64_t, T*, int64_t, T*);
-template <typename T> int vrows_explicit(rlhip_ctx*, int64_t, int64_t, int64_t, const T*, int64_t, T*, int64_t);
-template <typename T> int qrp_partial(rlhip_ctx*, int64_t, int64_t, int64_t, T*, int64_t, int64_t*, T*);
-template <typename T> int geqp3_steps(rlhip_ctx*, int64_t, int64_t, int64_t, T*, int64_t, int64_t*, T*);
-template <typename T> int gemqrt_rn(rlhip_ctx*, int64_t, int64_t, int64_t, const T*, int64_t, const T*, int64_t, T*, int64_t);
-template <typename T> int ungqr(rlhip_ctx*, int64_t, int64_t, T*, int64_t, const T*);
-template <typename T> int laswp(rlhip_ctx*, int64_t, T*, int64_t, int64_t, int64_t, const int64_t*);
-template <typename T> int fill_dense_rows(rlhip_ctx*, int, int64_t, int64_t, int64_t, int64_t, T*, int64_t, const uint32_t*, const uint32_t*, uint32_t*);
-int philox_raw(rlhip_ctx* c, int64_t nblk, uint32_t* out_dev, const uint32_t ctr[4], const uint32_t key[2]);
-}
 
 // ------------------------------------------------------------------ scratch arena
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -142,11 +103,6 @@ void rlhip_ws_release(rlhip_ctx* c, size_t mark) {
     }
 }
 
-namespace rlhip {
-template <typename T>
-int gemm_impl(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda,
-              const T* B, int64_t ldb, T beta, T* C, int64_t ldc, int tri, double* ssqA_dev, int* ssq_done);
-}
 __global__ void rlhip_zero_f64_kernel(double* p) { *p = 0.0; }
 
 extern "C" {

@@ -8,10 +8,12 @@
 // A non-positive (or NaN) pivot stores its 1-based global index in a device flag; later kernels see
 // the flag and leave the matrix untouched, so the caller gets LAPACK's info and a partially factored
 // matrix, as with dpotrf.
-#include "rlhip_internal.h"
+#include "rlhip_device.h"
 #include <cstdlib>
 
 namespace {
+
+using namespace rlhip_dev;   // lane_get
 
 constexpr int NB = 32;
 
@@ -203,11 +205,6 @@ __global__ __launch_bounds__(1024) void potrf_small_kernel(int n, T* __restrict_
 // current step).  It replaces transpose -> blocked right-side solve (pack kernels, conditioning guard with its host read, one MFMA solve
 // kernel) -> transpose: ~190 us of launches and a host round trip per 256-block for 2 * 256^2 * rest flops (C3's 1024 x 1024 Gram matrix:
 // 1.38 ms for the whole factorization, 0.74 of it in the four diagonal blocks).  Plain substitution: no explicit inverse, no guard needed.
-__device__ __forceinline__ double cr_lane(double v, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ float cr_lane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-
 template <typename T>
 __global__ __launch_bounds__(256) void chol_rowsolve_kernel(int jb, int64_t rest, const T* __restrict__ UT, T* __restrict__ A12, int64_t lda,
                                                             const int* __restrict__ info) {
@@ -242,7 +239,7 @@ __global__ __launch_bounds__(256) void chol_rowsolve_kernel(int jb, int64_t rest
             for (int t = 0; t < PD; ++t) {
                 const int l0 = l4 + t, k = 64 * q0 + l0;
                 if (k < jb) {                               // (wave-uniform)
-                    const T xk = cr_lane(x[q0], l0) / cr_lane(u[t][q0], l0);
+                    const T xk = lane_get(x[q0], l0) / lane_get(u[t][q0], l0);
                     if (lane == l0) x[q0] = xk;
 #pragma unroll
                     for (int q = q0; q < RPL; ++q) {
@@ -264,14 +261,6 @@ __global__ __launch_bounds__(256) void chol_rowsolve_kernel(int jb, int64_t rest
 }  // namespace
 
 namespace rlhip {
-
-template <typename T>
-int gemm_impl(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_t k, T alpha, const T* A,
-              int64_t lda, const T* B, int64_t ldb, T beta, T* C, int64_t ldc, int tri, double* ssqA_dev = nullptr,
-              int* ssq_done = nullptr);
-
-template <typename T>
-int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, const T* A, int64_t lda, T* B, int64_t ldb);
 
 template <typename T>
 int potrf_upper(rlhip_ctx* c, int64_t n, T* A, int64_t lda, int* info_host) {

@@ -649,10 +649,6 @@ int gemm_dispatch(rlhip_ctx* c, GemmArgs<T> g, int tri) {
 namespace rlhip {
 
 template <typename T>
-int gemm_streamk(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda, const T* B,
-                 int64_t ldb, T beta, T* C, int64_t ldc, double* ssqA_dev, int tri);
-
-template <typename T>
 static int try_streamk(rlhip_ctx* c, int ta, int tb, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda, const T* B, int64_t ldb,
                        T beta, T* C, int64_t ldc, double* ssq, int tri) {
     return gemm_streamk<T>(c, ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, ssq, tri);

@@ -18,12 +18,6 @@
 #include <cmath>
 #include <cstdlib>
 
-namespace rlhip {
-template <typename T>
-int gemm_impl(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda,
-              const T* B, int64_t ldb, T beta, T* C, int64_t ldc, int tri, double* ssqA_dev = nullptr, int* ssq_done = nullptr);
-}
-
 namespace {
 
 constexpr int LB = 32;
@@ -164,14 +158,6 @@ __global__ void zero_int2(int* p) { *p = 0; }
 }  // namespace
 
 namespace rlhip {
-
-template <typename T> int laset(rlhip_ctx*, int, int64_t, int64_t, T, T, T*, int64_t);
-template <typename T> int lacpy(rlhip_ctx*, int, int64_t, int64_t, const T*, int64_t, T*, int64_t);
-template <typename T> int trsm_right_upper(rlhip_ctx*, int, int64_t, int64_t, T, const T*, int64_t, T*, int64_t);
-template <typename T> int gemm(rlhip_ctx*, int, int, int64_t, int64_t, int64_t, T, const T*, int64_t, const T*, int64_t, T, T*, int64_t);
-
-template <typename T>
-int lunp_blk(rlhip_ctx* c, int64_t n, T* A, int64_t lda, T* D);
 
 template <typename T>
 static int lunp_top(rlhip_ctx* c, int64_t n, T* A, int64_t lda, T* D);
@@ -485,7 +471,6 @@ static int skinny_trsm(rlhip_ctx* c, int64_t m, int64_t n, const T* R, int64_t l
     RLHIP_LAUNCH_CHECK();
     return 0;
 }
-template <typename T> int potrf_upper_enqueue(rlhip_ctx* c, int64_t n, T* A, int64_t lda, int* info_dev);
 
 template <typename T>
 static int cholqr2_skinny(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* R1, T* R2, T* dev1, bool* good) {
@@ -550,12 +535,6 @@ static int cholqr2_inplace(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda
     if (!rc) *good = true;
     return rc;
 }
-
-struct SasoOp;
-int saso_build(rlhip_ctx* c, int64_t d, int64_t m, int nnz, int mode, const uint32_t ctr[4], const uint32_t key[2], uint32_t next_ctr[4], SasoOp** out);
-int saso_destroy(rlhip_ctx* c, SasoOp* op);
-template <typename T> int saso_apply(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T* A, int64_t lda, T beta, T* B, int64_t ldb);
-template <typename T> int geqrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev);
 
 // A (m x n, tall) <- its orthonormal factor by Cholesky-QR twice, R2 (n x n, ld n) <- the upper-triangular R with A_in = Q R2; for an
 // ill-conditioned panel once more behind a sparse-sketch preconditioner (below).  *good = false: A holds its input (up to rounding, or bit

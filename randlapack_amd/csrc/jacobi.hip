@@ -14,31 +14,17 @@
 // convergence from ~11 to >30 sweeps on graded 256-column factors.)  Callers should hand in a
 // pre-conditioned factor: Jacobi on R^T of a QR factorisation converges in ~11 sweeps regardless of
 // grading, on R itself it can take 30+ (measured).
-#include "rlhip_internal.h"
+#include "rlhip_device.h"
 #include <cstring>
 #include <cstdlib>
 #include <cmath>
 #include <limits>
 
-namespace rlhip {
-template <typename T>
-int gemm(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda, const T* B, int64_t ldb,
-         T beta, T* C, int64_t ldc);
-}
 using rlhip::gemm;
-namespace rlhip {
-template <typename T>
-int lacpy(rlhip_ctx* c, int uplo, int64_t m, int64_t n, const T* A, int64_t lda, T* B, int64_t ldb);
-}
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ T wsum(T v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
+using namespace rlhip_dev;   // wave_sum, dpp_ror_add
 
 template <typename T>
 __global__ __launch_bounds__(256) void jacobi_round_kernel(int64_t m, int n, int N, int round, T* __restrict__ A,
@@ -61,7 +47,7 @@ __global__ __launch_bounds__(256) void jacobi_round_kernel(int64_t m, int n, int
         T x = ap[i], y = aq[i];
         aa += x * x; bb += y * y; ab += x * y;
     }
-    aa = wsum(aa); bb = wsum(bb); ab = wsum(ab);
+    aa = wave_sum(aa); bb = wave_sum(bb); ab = wave_sum(ab);
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (lane == 0) { red[0][w] = aa; red[1][w] = bb; red[2][w] = ab; }
     __syncthreads();
@@ -171,17 +157,6 @@ constexpr int JM = 256;           // panel rows (LDS)
 // and the instruction stream (dot products, DPP row-rotate all-reduce, rcp/rsq based rotation, update) is issued once
 // for four pairs.  The earlier one-pair-per-wavefront layout was VALU-issue bound: ~150 instructions per pair with
 // four wavefronts per SIMD = 1.5 us per round; this layout issues ~65 per pair from one or two wavefronts per SIMD.
-__device__ __forceinline__ double dpp_ror_add(double v, const int n) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    int lo2, hi2;
-    switch (n) {   // row_ror:n  (rotate inside each 16-lane row)
-        case 1: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x121, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x121, 0xF, 0xF, false); break;
-        case 2: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x122, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x122, 0xF, 0xF, false); break;
-        case 4: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x124, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x124, 0xF, 0xF, false); break;
-        default: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x128, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x128, 0xF, 0xF, false); break;
-    }
-    return v + __hiloint2double(hi2, lo2);
-}
 // every lane of a 16-lane row ends up with the row's sum
 __device__ __forceinline__ double row16_allsum(double v) {
     v = dpp_ror_add(v, 8);
@@ -757,7 +732,7 @@ __global__ __launch_bounds__(256) void colnorm_kernel(int64_t m, const T* __rest
     // scaled accumulation is unnecessary here: entries are bounded by the singular values themselves
     T acc = 0;
     for (int64_t i = threadIdx.x; i < m; i += 256) acc += col[i] * col[i];
-    acc = wsum(acc);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) S[blockIdx.x] = sqrt(red[0] + red[1] + red[2] + red[3]);
@@ -999,11 +974,6 @@ int block_jacobi_sweeps(rlhip_ctx* c, int m, int n, T* A, int64_t lda, T* V, T t
 }  // namespace
 
 namespace rlhip {
-
-template <typename T>
-int lacpy(rlhip_ctx* c, int uplo, int64_t m, int64_t n, const T* A, int64_t lda, T* B, int64_t ldb);
-template <typename T>
-int laset(rlhip_ctx* c, int uplo, int64_t m, int64_t n, T offdiag, T diag, T* A, int64_t lda);
 
 // ENQUEUES the one-launch Jacobi sweeps of an n x n matrix X -- trans_upper = 0: X = the matrix stored in `R` (e.g. a full symmetric Gram
 // matrix); 1: X = R^T of the upper triangle stored in `R` (a Cholesky factor as potrf left it) -- and returns without touching the host: the swept columns (X J, mutually orthogonal, norms = singular values) land in the

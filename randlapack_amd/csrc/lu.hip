@@ -14,35 +14,15 @@
 //       rendezvous (8-byte write-through stores read after one L1 invalidate, double-buffered by column parity);
 //     in both, after the exchange everybody knows the winner, the two owners swap rows and every workgroup eliminates its own rows.
 //   * dlaswp on the columns outside the panel is a thread-per-column kernel walking the 32 swaps in order.
-#include "rlhip_internal.h"
+#include "rlhip_device.h"
 #include <algorithm>
 #include <cstdio>
-
-namespace rlhip {
-template <typename T>
-int gemm_impl(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda,
-              const T* B, int64_t ldb, T beta, T* C, int64_t ldc, int tri, double* ssqA_dev = nullptr, int* ssq_done = nullptr);
-}
-
 #include "lu_common.h"
 
 namespace {
 
 using namespace rlhip_lu;
-
-template <typename T>
-__device__ __forceinline__ void pstore(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ void lu_barrier(unsigned* bar, unsigned target) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) __builtin_amdgcn_s_sleep(1);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-}
+using namespace rlhip_dev;   // pub_store, grid_barrier
 
 template <typename T>
 __global__ __launch_bounds__(256) void getrf_panel_kernel(LuArgs<T> g) {
@@ -89,13 +69,13 @@ __global__ __launch_bounds__(256) void getrf_panel_kernel(LuArgs<T> g) {
         }
         const T lbest = s_val[0]; const int64_t lrow = s_row[0];
         if (tid == 0) {
-            pstore(g.cand_val + par * G + me, lbest);
+            pub_store(g.cand_val + par * G + me, lbest);
             __hip_atomic_store(g.cand_row + par * G + me, lrow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (lrow < g.m && tid < pb) pstore(g.cand_data + ((int64_t)par * G + me) * PB + tid, P[tid * rpw + (lrow - lo)]);
-        if (j >= lo && j < hi && tid < pb) pstore(g.diag_data + par * PB + tid, P[tid * rpw + (j - lo)]);
+        if (lrow < g.m && tid < pb) pub_store(g.cand_data + ((int64_t)par * G + me) * PB + tid, P[tid * rpw + (lrow - lo)]);
+        if (j >= lo && j < hi && tid < pb) pub_store(g.diag_data + par * PB + tid, P[tid * rpw + (j - lo)]);
         __syncthreads();
-        lu_barrier(g.bar, (unsigned)(G * (++epoch)));
+        grid_barrier(g.bar, (unsigned)(G * (++epoch)));
         // ---- winner (every workgroup, redundantly): max |value|, ties -> smallest row
         {
             T v = T(-1); int64_t r = g.m; int w = 0;
@@ -315,7 +295,7 @@ __device__ __forceinline__ void lu_reg_step(const LuArgs<T>& g, LuRegState<T, RP
         }
     } else {
     if (tid == 0) {
-        pstore(g.cand_val + par * G + me, lbest);
+        pub_store(g.cand_val + par * G + me, lbest);
         __hip_atomic_store(g.cand_row + par * G + me, lrow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // the owners of the candidate row and of the diagonal row publish those rows' 32 values
@@ -324,15 +304,15 @@ __device__ __forceinline__ void lu_reg_step(const LuArgs<T>& g, LuRegState<T, RP
         if (st.gr[q] == lrow && lrow < m) {
             T* dst = g.cand_data + ((int64_t)par * G + me) * PB;
 #pragma unroll
-            for (int c2 = 0; c2 < PB; ++c2) pstore(dst + c2, st.x[q][c2]);
+            for (int c2 = 0; c2 < PB; ++c2) pub_store(dst + c2, st.x[q][c2]);
         }
         if (st.gr[q] == j) {
             T* dst = g.diag_data + par * PB;
 #pragma unroll
-            for (int c2 = 0; c2 < PB; ++c2) pstore(dst + c2, st.x[q][c2]);
+            for (int c2 = 0; c2 < PB; ++c2) pub_store(dst + c2, st.x[q][c2]);
         }
     }
-    lu_barrier(g.bar, (unsigned)(G * (++epoch)));
+    grid_barrier(g.bar, (unsigned)(G * (++epoch)));
     // ---- winner (every workgroup, redundantly): thread w looks at workgroup w's candidate.  The winner's row is needed right
     //      after the decision; instead of a dependent second round trip every thread prefetches, together with the candidates,
     //      element (tid % 32) of the candidate rows of workgroups tid / 32, tid / 32 + 8, ... (G <= 64 covers 32768+ rows) and the

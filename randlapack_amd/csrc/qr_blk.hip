@@ -14,7 +14,7 @@
 //     product V^T C is reduced over the wave by a transposing butterfly (64 sums for 63 exchanges) and over the waves through LDS.
 // The critical path is one chunk factorization + one hand-over + one block application per 8 columns instead of per column.
 // Same reflectors as LAPACK's geqr2 / larfg (beta = -sign(alpha) ||x||, tau = (beta - alpha) / beta, v = x / (alpha - beta)), same T as larft.
-#include "rlhip_internal.h"
+#include "rlhip_device.h"
 #include <cstdlib>
 #include <cstdio>
 
@@ -32,9 +32,9 @@ struct QbArgs {
 #endif
 };
 
-template <typename T>
-__device__ __forceinline__ void qb_pub(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// The same write-through (sc1) store, but issued without the s_waitcnt vmcnt(0) hipcc puts in front of every agent-scope atomic store: a
+using namespace rlhip_dev;   // pub_store, lane_get
+
+// The write-through (sc1) store of pub_store, but issued without the s_waitcnt vmcnt(0) hipcc puts in front of every agent-scope atomic store: a
 // thread's 32 stores of a chunk would otherwise go out one memory round trip at a time.  The workgroup drains them once, before its flag.
 __device__ __forceinline__ void qb_store_wt(float* p, float v) { asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
 __device__ __forceinline__ void qb_store_wt(double* p, double v) { asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
@@ -55,11 +55,6 @@ template <int D> __device__ __forceinline__ double qb_fetch(double v) {
 // workgroup rendezvous that orders LDS traffic only: the write-through stores of finished columns stay in flight across it
 // (__syncthreads() would drain them: its fence waits for vmcnt(0))
 __device__ __forceinline__ void qb_barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// value held by lane l (compile-time constant after unrolling): v_readlane, a scalar
-__device__ __forceinline__ float qb_lane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-__device__ __forceinline__ double qb_lane(double v, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
 // One exchange step across lane bit log2(D): lanes with the bit clear receive  a(lane) + a(lane ^ D), lanes with it set  b(lane) + b(lane ^ D).
 // D = 16, 32: v_permlane16_swap / v_permlane32_swap (gfx950) trade the odd rows (upper half) of the first operand for the even rows (lower half)
 // of the second one, which is exactly this step in one instruction per 32 bits; D <= 8: select + DPP fetch.
@@ -246,7 +241,7 @@ __global__ __launch_bounds__(NT) void qr_blk_kernel(QbArgs<T> g) {
             const T totv = QbRed<T, 1, 32, 4>::run(tot, lane);     // exchange steps across lane bits 5, 4, 3 only
             T ds[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) ds[k] = qb_lane(totv, k);
+            for (int k = 0; k < 8; ++k) ds[k] = lane_get(totv, k);
             const T alpha = s_bc[par][cc];
             T beta = alpha, tcc = T(0), scale = T(0);
             if (ds[cc] != T(0)) {
@@ -300,9 +295,9 @@ __global__ __launch_bounds__(NT) void qr_blk_kernel(QbArgs<T> g) {
                 }
             }
             row[cc] = val;
-            qb_pub(g.Tx + (int64_t)me * 64 + i + 8 * cc, val);
+            pub_store(g.Tx + (int64_t)me * 64 + i + 8 * cc, val);
         }
-        if (i < cw) qb_pub(g.tau + j0m + i, s_tau[i]);
+        if (i < cw) pub_store(g.tau + j0m + i, s_tau[i]);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -446,7 +441,7 @@ __global__ __launch_bounds__(NT) void lunp_blk_kernel(LbArgs<T> g) {
         }
     }
     __syncthreads();
-    if (tid < cw) qb_pub(g.D + j0m + tid, s_d[tid]);
+    if (tid < cw) pub_store(g.D + j0m + tid, s_d[tid]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) __hip_atomic_store(g.flag + me, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);

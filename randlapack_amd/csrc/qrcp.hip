@@ -14,7 +14,7 @@
 // barrier) and down-dates their norms.  Published buffers are double-buffered by step parity (a workgroup can be
 // at most one rendezvous ahead).  Measured 1280 x 1024: two-rendezvous/global-memory version 61 ms -> LDS
 // columns 36 ms -> single rendezvous + fence-free publication: see DESIGN.md.
-#include "rlhip_internal.h"
+#include "rlhip_device.h"
 #include <cstdlib>
 #include <cstdio>
 #include <cmath>
@@ -40,50 +40,14 @@ struct QrcpArgs {
     int v_in_lds;             // the step's reflector is staged in LDS (m fits) or read from its published slot (tall inputs)
 };
 
-// ---- cross-workgroup traffic uses agent-scope relaxed atomics on 8-byte granules (sc1 write-through stores /
-//      L1-bypassing loads): no cache-maintenance fences are needed around the rendezvous (guide section 6, G16:
-//      "8-B agent atomics both sides"), which keeps a step's single grid barrier at a few microseconds.
-template <typename T>
-__device__ __forceinline__ void pub_store(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename T>
-__device__ __forceinline__ T pub_load(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+using namespace rlhip_dev;   // pub_store, grid_barrier, wave_allsum, dpp_ror_add
 
-__device__ __forceinline__ void grid_barrier(unsigned* bar, unsigned target) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's published stores have left
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) __builtin_amdgcn_s_sleep(1);
-        // one L1 invalidate per step: everything published before the rendezvous was stored write-through (sc1),
-        // so after this acquire it can be read with ordinary wide loads
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// the same sum with DPP row rotations (VALU speed) + four readlanes instead of six dependent cross-lane shuffles through the LDS
+// wave_allsum with DPP row rotations (VALU speed) + four readlanes instead of six dependent cross-lane shuffles through the LDS
 // crossbar: the reductions sit on the critical path of every column step of the barrier-free kernel below
-__device__ __forceinline__ double dpp_ror_add_f64(double v, const int n) {
-    int lo = __double2loint(v), hi = __double2hiint(v), lo2, hi2;
-    switch (n) {
-        case 8: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x128, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x128, 0xF, 0xF, false); break;
-        case 4: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x124, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x124, 0xF, 0xF, false); break;
-        case 2: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x122, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x122, 0xF, 0xF, false); break;
-        default: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x121, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x121, 0xF, 0xF, false); break;
-    }
-    return v + __hiloint2double(hi2, lo2);
-}
 template <typename T>
 __device__ __forceinline__ T wave_sum_fast(T x) {
     double v = (double)x;                                       // (fp32 inputs: the sum itself in double, rounded once)
-    v = dpp_ror_add_f64(v, 8); v = dpp_ror_add_f64(v, 4); v = dpp_ror_add_f64(v, 2); v = dpp_ror_add_f64(v, 1);
+    v = dpp_ror_add(v, 8); v = dpp_ror_add(v, 4); v = dpp_ror_add(v, 2); v = dpp_ror_add(v, 1);
     const int lo = __double2loint(v), hi = __double2hiint(v);
     double r = 0;
 #pragma unroll
@@ -130,7 +94,7 @@ __global__ __launch_bounds__(256) void qrcp_kernel(QrcpArgs<T> g) {
         const T* col = colptr(j);
         T ss = 0;
         for (int64_t i = lane; i < m; i += 64) ss += col[i] * col[i];
-        ss = wave_sum(ss);
+        ss = wave_allsum(ss);
         if (lane == 0) {
             T nr = sqrt(ss);
             l_vn1[j / G] = nr; l_vn2[j / G] = nr;
@@ -159,7 +123,7 @@ __global__ __launch_bounds__(256) void qrcp_kernel(QrcpArgs<T> g) {
             const T* col = colptr(bpos);
             T ss = 0;
             for (int64_t i = k + 1 + tid; i < m; i += 256) ss += col[i] * col[i];
-            ss = wave_sum(ss);
+            ss = wave_allsum(ss);
             __syncthreads();
             if (lane == 0) s_val[wid] = ss;
             __syncthreads();
@@ -262,7 +226,7 @@ __global__ __launch_bounds__(256) void qrcp_kernel(QrcpArgs<T> g) {
                     for (int u = 0; u < 8; ++u) w8[u] += vx[u] * cv[u];
                 }
                 for (; i < m; i += 64) w8[0] += ((i == k) ? T(1) : vv[i]) * col[i];
-                T w = wave_sum(((w8[0] + w8[1]) + (w8[2] + w8[3])) + ((w8[4] + w8[5]) + (w8[6] + w8[7]))) * tauk;
+                T w = wave_allsum(((w8[0] + w8[1]) + (w8[2] + w8[3])) + ((w8[4] + w8[5]) + (w8[6] + w8[7]))) * tauk;
                 i = k + lane;
                 for (; i + 448 < m; i += 512) {
                     T cv[8], vx[8];
@@ -287,7 +251,7 @@ __global__ __launch_bounds__(256) void qrcp_kernel(QrcpArgs<T> g) {
                 if (temp2 <= g.tol3z) {
                     T ss = 0;
                     for (int64_t i = k + 1 + lane; i < m; i += 64) ss += col[i] * col[i];
-                    ss = wave_sum(ss);
+                    ss = wave_allsum(ss);
                     v1 = sqrt(ss);
                     if (lane == 0) { l_vn1[j / G] = v1; l_vn2[j / G] = v1; }
                 } else {
@@ -776,7 +740,7 @@ __global__ __launch_bounds__(256) void qr_pipe_kernel(QrPipeArgs<T> g) {
         T ss = 0;
 #pragma unroll 8
         for (int64_t i = k + 1 + tid; i < m; i += 256) ss += col[i] * col[i];
-        ss = wave_sum(ss);
+        ss = wave_allsum(ss);
         __syncthreads();
         if (lane == 0) s_val[wid] = ss;
         __syncthreads();
@@ -813,7 +777,7 @@ __global__ __launch_bounds__(256) void qr_pipe_kernel(QrPipeArgs<T> g) {
         T w = 0;
 #pragma unroll 4
         for (int64_t i = k + lane; i < m; i += 64) w += ((i == k) ? T(1) : vread(l_v, gv, i)) * col[i];
-        w = wave_sum(w) * tk;
+        w = wave_allsum(w) * tk;
 #pragma unroll 4
         for (int64_t i = k + lane; i < m; i += 64) col[i] -= w * ((i == k) ? T(1) : vread(l_v, gv, i));
     };
@@ -822,7 +786,7 @@ __global__ __launch_bounds__(256) void qr_pipe_kernel(QrPipeArgs<T> g) {
         T w = 0;
 #pragma unroll 8
         for (int64_t i = k + tid; i < m; i += 256) w += ((i == k) ? T(1) : vread(l_v, gv, i)) * col[i];
-        w = wave_sum(w);
+        w = wave_allsum(w);
         __syncthreads();
         if (lane == 0) s_val[wid] = w;
         __syncthreads();
@@ -910,34 +874,8 @@ __global__ void zero_u32_n(unsigned* p, int64_t n) {
 namespace rlhip {
 
 template <typename T>
-int gemqrt_lt(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, int64_t nb, const T* V, int64_t ldv, const T* Tm, int64_t ldt, T* C, int64_t ldc);
-template <typename T>
-int larft_gram(rlhip_ctx* c, int64_t m, int64_t k, const T* V, int64_t ldv, const T* tau, T* Tm, int64_t ldt);
-template <typename T>
-int gemm(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda,
-         const T* B, int64_t ldb, T beta, T* C, int64_t ldc);
-
-template <typename T>
-int geqrf_cholqr(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau, int* done);
-template <typename T>
-int geqrf_blk(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev);
-
-template <typename T>
 static int qr_core(rlhip_ctx* c, int pivot, int64_t m, int64_t n, T* A, int64_t lda, int64_t* jpvt_dev, T* tau_dev, int64_t max_steps = -1,
                    int hq_formula = 0);
-
-// dynamic-LDS limit (150 KiB) of one instantiation of the cooperative QR kernels, raised once per (device, kernel address)
-static hipError_t qr_kernel_lds_limit(rlhip_ctx* c, const void* kern) {
-    static std::mutex mu;
-    static std::vector<std::pair<int, const void*>> seen;
-    std::lock_guard<std::mutex> lk(mu);
-    const std::pair<int, const void*> key(c->device, kern);
-    for (auto const& e : seen) if (e == key) return hipSuccess;
-    hipError_t le = hipSetDevice(c->device);
-    if (le == hipSuccess) le = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (le == hipSuccess) seen.push_back(key);
-    return le;
-}
 
 template <typename T>
 static int qrcp_guarded(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* jpvt_dev, T* tau_dev, int64_t steps, int hq_formula);
@@ -1304,8 +1242,8 @@ static int qr_core(rlhip_ctx* c, int pivot, int64_t m, int64_t n, T* A, int64_t 
             void* kargs[] = {(void*)&pa};
             const void* kern = use_lds ? (const void*)qr_pipe_kernel<T, true, true>            // (columns in LDS implies the reflector in LDS)
                                        : (pa.v_in_lds ? (const void*)qr_pipe_kernel<T, false, true> : (const void*)qr_pipe_kernel<T, false, false>);
-            hipError_t le = qr_kernel_lds_limit(c, kern);
-            if (le == hipSuccess) le = hipLaunchCooperativeKernel(kern, dim3((unsigned)Gp), dim3(256), kargs, (unsigned)dyn2, c->stream);
+            RLHIP_FUNC_LDS_DYN(c, kern, 150 * 1024);
+            const hipError_t le = hipLaunchCooperativeKernel(kern, dim3((unsigned)Gp), dim3(256), kargs, (unsigned)dyn2, c->stream);
             if (le != hipSuccess) return RLHIP_ERR_HIP(le);
         }
         return 0;
@@ -1387,8 +1325,8 @@ static int qr_core(rlhip_ctx* c, int pivot, int64_t m, int64_t n, T* A, int64_t 
         void* kargs[] = {(void*)&g};
         const void* kern = use_lds ? (const void*)qrcp_kernel<T, true, true>
                                    : (g.v_in_lds ? (const void*)qrcp_kernel<T, false, true> : (const void*)qrcp_kernel<T, false, false>);
-        hipError_t le = qr_kernel_lds_limit(c, kern);
-        if (le == hipSuccess) le = hipLaunchCooperativeKernel(kern, dim3((unsigned)G), dim3(256), kargs, (unsigned)dyn, c->stream);
+        RLHIP_FUNC_LDS_DYN(c, kern, 150 * 1024);
+        const hipError_t le = hipLaunchCooperativeKernel(kern, dim3((unsigned)G), dim3(256), kargs, (unsigned)dyn, c->stream);
         if (le != hipSuccess) return RLHIP_ERR_HIP(le);
     }
     return 0;

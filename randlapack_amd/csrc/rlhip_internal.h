@@ -1,4 +1,7 @@
-// Internal (non-ABI) declarations shared by the HIP translation units of librlhip.so.
+// Internal (non-ABI) declarations shared by the HIP translation units of librlhip.so: the error / LDS-limit macros, the execution
+// context with its scratch arena, and THE declaration of every namespace rlhip host function that one .hip file defines and another
+// calls (grouped by defining file, at the end).  A .hip file declares no function of another file itself; forward declarations of
+// functions local to one file stay in that file.  The device-side helpers shared between kernel files are in rlhip_device.h.
 // Everything here is MI355X / gfx950 only: 64-lane wavefronts, MFMA, 160 KiB LDS.
 #pragma once
 #include <mutex>
@@ -146,7 +149,7 @@ struct ws_scope {
 void* rlhip_xchg_buffer(rlhip_ctx* c, size_t bytes);
 void* rlhip_xloc_buffer(rlhip_ctx* c, size_t bytes);
 
-// ---- typed internal entry points (implemented in the .hip files; the extern "C" ABI wraps them) ----
+// ---- typed internal entry points (implemented in the .hip files; the extern "C" ABI wraps them): each one is declared here and nowhere else ----
 namespace rlhip {
 
 enum Op : int { NoTrans = 0, Trans = 1 };
@@ -229,5 +232,140 @@ int transpose(rlhip_ctx* c, int64_t m, int64_t n, const T* A, int64_t lda, T* AT
 template <typename T>
 int gesdd_tall(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* S, T* U, int64_t ldu, T* VT,
                int64_t ldvt, int* sweeps_host);
+
+// ---- gemm.hip
+// the router behind gemm (tri = 0) and syrk (tri = 1).  ssqA_dev / ssq_done: the sum of squares of A fused into the product
+// (rlhip_gemm_norma_f64); *ssq_done says how much of A the route taken covered, see the definition
+template <typename T>
+int gemm_impl(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda,
+              const T* B, int64_t ldb, T beta, T* C, int64_t ldc, int tri, double* ssqA_dev = nullptr, int* ssq_done = nullptr);
+
+// ---- gemm_sk.hip
+// returns 1 if the problem was handled here, 0 if the caller should use the generic kernel, <0 on error
+template <typename T>
+int gemm_streamk(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_t k, T alpha, const T* A, int64_t lda, const T* B,
+                 int64_t ldb, T beta, T* C, int64_t ldc, double* ssqA_dev, int tri);
+
+// ---- fill.hip
+// rows [row0, row0 + loc_rows) of the glob_rows x cols matrix that fill_dense draws from the same counter / key
+template <typename T>
+int fill_dense_rows(rlhip_ctx* c, int dist, int64_t glob_rows, int64_t cols, int64_t row0, int64_t loc_rows, T* buf, int64_t ld,
+                    const uint32_t ctr[4], const uint32_t key[2], uint32_t next_ctr[4]);
+int philox_raw(rlhip_ctx* c, int64_t nblk, uint32_t* out_dev, const uint32_t ctr[4], const uint32_t key[2]);
+
+// ---- chol.hip
+// The one-workgroup factorization ENQUEUED only: LAPACK's info (0, or the 1-based index of the first non-positive pivot) goes to the DEVICE
+// word `info_dev`, which later kernels of the stream may test; nothing is read back.  n <= 448 only (returns 1 otherwise: not available).
+template <typename T>
+int potrf_upper_enqueue(rlhip_ctx* c, int64_t n, T* A, int64_t lda, int* info_dev);
+
+// ---- tri.hip
+// Cholesky-QR, Q factor only: R (k x k, ld k) = chol(A^T A), A <- A R^-1, *info_host = LAPACK's potrf info, one host read.  `reduce_gram`:
+// row-sharded input, the Gram matrix is summed over the ranks first.  Returns 1 when the shape is not served here: the caller runs the three calls.
+template <typename T>
+int cholqrq(rlhip_ctx* c, int64_t m, int64_t k, T* A, int64_t lda, T* R, int reduce_gram, int* info_host);
+
+// ---- jacobi.hip
+// ENQUEUES the one-launch Jacobi sweeps of an n x n matrix (trans_upper = 0: the matrix stored in R, 1: R^T of the upper triangle in R) and
+// returns without touching the host; the contract is at the definition.  Returns 0 when enqueued, 1 when the path is not available, < 0 on error.
+template <typename T>
+int jacobi_enqueue_rt(rlhip_ctx* c, int n, const T* R, int64_t ldr, int trans_upper, float norm_ratio_lim, const int* skip_dev, int* out_dev,
+                      const T** X_out);
+
+// ---- sketch.hip
+struct SasoOp;   // sparse sign operator S (d x m); the ABI's rlhip_saso is this type
+int saso_build(rlhip_ctx* c, int64_t d, int64_t m, int nnz, int mode, const uint32_t ctr[4], const uint32_t key[2],
+               uint32_t next_ctr[4], SasoOp** out);
+int saso_destroy(rlhip_ctx* c, SasoOp* op);
+template <typename T>
+int saso_dense(rlhip_ctx* c, const SasoOp* op, T* S /* d x m, zeroed here */);
+// B (d x n, ldb) = alpha * S[:, row0 : row0 + mloc] * A_loc (mloc x n, lda) + beta * B : the contribution of one row shard
+// (the whole product when row0 = 0, mloc = m)
+template <typename T>
+int saso_apply_rows(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T* A, int64_t lda, int64_t row0, int64_t mloc, T beta,
+                    T* B, int64_t ldb);
+template <typename T>
+int saso_apply(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T* A, int64_t lda, T beta, T* B, int64_t ldb);
+// B (d x n, ldb) = alpha * S * A + beta * B for a sparse A (m x n) given by the CSR of its transpose
+template <typename T>
+int saso_apply_csr(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const int64_t* rowptrT, const int64_t* colidxT, const T* valsT, T beta,
+                   T* B, int64_t ldb, int64_t row0);
+template <typename T>
+int col_swap(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, T* A, int64_t lda, const int64_t* idx_dev);
+int col_swap_i64(rlhip_ctx* c, int64_t n, int64_t k, int64_t* A, const int64_t* idx_dev);
+
+// ---- qrcp.hip
+template <typename T>
+int geqp3(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* jpvt_dev, T* tau_dev);
+// pivoted Householder QR restricted to the first `steps` columns, norm down-date in HQRRP's form; jpvt returns the whole permutation (1-based)
+template <typename T>
+int qrp_partial(rlhip_ctx* c, int64_t m, int64_t n, int64_t steps, T* A, int64_t lda, int64_t* jpvt_dev, T* tau_dev);
+// the first `steps` steps of geqp3 itself (LAPACK's norm down-date form)
+template <typename T>
+int geqp3_steps(rlhip_ctx* c, int64_t m, int64_t n, int64_t steps, T* A, int64_t lda, int64_t* jpvt_dev, T* tau_dev);
+template <typename T>
+int geqrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev);
+// lapack::ungqr(m, n, k = n, A, lda, tau): A (m x n, reflectors below the diagonal) <- Q[:, 0:n]
+template <typename T>
+int ungqr(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, const T* tau_dev);
+
+// ---- qr_blk.hip
+// Householder QR of the leading n <= m columns of A (m x n, column-major) in the geqrf output format.  Returns 1 when the problem was
+// factored here, 0 when it does not fit this kernel (the caller carries on with its other routes), < 0 on error.
+template <typename T>
+int geqrf_blk(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau_dev);
+// Sign-modified LU without pivoting of the n x n matrix A (what lapack::orhr_col runs on the top block of Q): L (unit lower) and U in
+// place, D(i) = -sign of the i-th pivot before its modification.  Returns 1 when done here, 0 when the problem does not fit the kernel.
+template <typename T>
+int lunp_blk(rlhip_ctx* c, int64_t n, T* A, int64_t lda, T* D);
+
+// ---- house.hip
+// A (m x n, orthonormal columns) -> V (unit lower trapezoidal, in place), T (nb x n), D (n)
+template <typename T>
+int orhr_col(rlhip_ctx* c, int64_t m, int64_t n, int64_t nb, T* A, int64_t lda, T* Tm, int64_t ldt, T* D);
+// C (m x n) <- Q^T C,  Q = H_1 ... H_k in compact-WY blocks of width nb: V (m x k, unit lower trapezoidal, only the
+// strictly lower part is read), T (nb x k).  Side::Left, Op::Trans.
+template <typename T>
+int gemqrt_lt(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, int64_t nb, const T* V, int64_t ldv, const T* Tm, int64_t ldt,
+              T* C, int64_t ldc);
+// the same apply for ONE compact-WY block (k reflectors), cut where the first k rows of C are final:
+//   head:  W2 = T^T (V1^T C1 + V2^T C2),  C1 -= V1 W2;   tail:  C2 -= V2 W2.   W2 is the caller's k x n buffer (ld k)
+template <typename T>
+int gemqrt_lt_head(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, const T* V, int64_t ldv, const T* Tm, int64_t ldt, T* C, int64_t ldc, T* W2);
+template <typename T>
+int gemqrt_lt_tail(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, const T* V, int64_t ldv, const T* W2, T* C, int64_t ldc);
+// C (m x n) <- C Q,  Q = I - V T V^T one compact-WY block (V: n x k unit lower trapezoidal, T: k x k upper).  Side::Right, Op::NoTrans
+template <typename T>
+int gemqrt_rn(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, const T* V, int64_t ldv, const T* Tm, int64_t ldt, T* C, int64_t ldc);
+// T (k x k upper, ldt) from V (m x k unit lower trapezoidal) and tau (k): one compact-WY block for all k reflectors
+template <typename T>
+int larft_gram(rlhip_ctx* c, int64_t m, int64_t k, const T* V, int64_t ldv, const T* tau, T* Tm, int64_t ldt);
+// R <- diag(D) R
+template <typename T>
+int row_sign(rlhip_ctx* c, int64_t n, T* R, int64_t ldr, const T* D);
+template <typename T>
+int tau_from_t(rlhip_ctx* c, int64_t k, int64_t nb, const T* Tm, int64_t ldt, T* tau);
+// returns 1 in *any_host if some |x[i]| > thr
+template <typename T>
+int any_abs_gt(rlhip_ctx* c, int64_t n, const T* x, T thr, int* any_host);
+// geqrf of a tall panel by Cholesky-QR twice + Householder reconstruction (orhr_col); *done = 0: not taken, the caller takes the Householder route
+template <typename T>
+int geqrf_cholqr(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* tau, int* done);
+// geqrf followed by ungqr(m, n, n) in ONE pass for a tall panel: A <- the first n columns of the Householder Q, R (n x n, ld ldr) <- the
+// triangle geqrf would have left (zero below).  *done = 0: not taken (A as geqrf_cholqr leaves it), the caller runs geqrf + ungqr.
+template <typename T>
+int geqrf_q(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, T* R, int64_t ldr, int* done);
+template <typename T>
+int vrows_explicit(rlhip_ctx* c, int64_t br, int64_t toff, int64_t tcnt, const T* Vtop, int64_t ldv, T* out, int64_t ldo);
+
+// ---- lu.hip
+// row-pivoted LU (lapack::getrf) of a tall-skinny matrix on the device
+template <typename T>
+int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_dev, int* info_host, int pivots_only);
+// lapack::laswp(n, A, lda, k1, k2, ipiv, incx = 1) with 1-based k1..k2
+template <typename T>
+int laswp(rlhip_ctx* c, int64_t n, T* A, int64_t lda, int64_t k1, int64_t k2, const int64_t* ipiv_dev);
+// the pivot post-processing of BQRRP's LU-based qrcp_wide
+int luqrcp_piv(rlhip_ctx* c, int64_t sd, int64_t cols, const int64_t* ipiv_dev, int64_t* J_dev);
 
 }  // namespace rlhip

@@ -818,7 +818,6 @@ static int saso_default_mode(const rlhip_ctx* c) { return c->opt[RLHIP_OPT_SASO_
         if (_rc) { saso_destroy(c, op); return _rc; }                                     \
         field = reinterpret_cast<decltype(field)>(_p);                                    \
     } while (0)
-int saso_destroy(rlhip_ctx* c, SasoOp* op);
 
 int saso_build(rlhip_ctx* c, int64_t d, int64_t m, int nnz, int mode, const uint32_t ctr[4], const uint32_t key[2],
                uint32_t next_ctr[4], SasoOp** out) {

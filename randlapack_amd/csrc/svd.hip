@@ -163,9 +163,6 @@ __global__ __launch_bounds__(256) void identity_defect_kernel(int n, const T* __
 namespace rlhip {
 
 template <typename T>
-int jacobi_enqueue_rt(rlhip_ctx* c, int n, const T* R, int64_t ldr, int trans_upper, float norm_ratio_lim, const int* skip_dev, int* out_dev, const T** X_out);
-
-template <typename T>
 int transpose(rlhip_ctx* c, int64_t m, int64_t n, const T* A, int64_t lda, T* AT, int64_t ldat, int upper_only) {
     if (m <= 0 || n <= 0) return 0;
     dim3 grid((unsigned)((m + 63) / 64), (unsigned)((n + 63) / 64));

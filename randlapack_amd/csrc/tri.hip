@@ -15,15 +15,7 @@
 //     registers, earlier x values of the same row in an LDS tile.
 #include <cstdlib>
 #include "rlhip_internal.h"
-#include "rlhip.h"
 #include <cstdio>
-
-namespace rlhip {
-template <typename T>
-int gemm_impl(rlhip_ctx* c, int transA, int transB, int64_t m, int64_t n, int64_t k, T alpha, const T* A,
-              int64_t lda, const T* B, int64_t ldb, T beta, T* C, int64_t ldc, int tri, double* ssqA_dev = nullptr,
-              int* ssq_done = nullptr);
-}
 
 namespace {
 
@@ -776,9 +768,6 @@ int tf_launch(rlhip_ctx* c, int64_t m, int64_t n, int64_t n_pad, T alpha, const 
 namespace rlhip {
 
 template <typename T>
-int lacpy(rlhip_ctx* c, int uplo, int64_t m, int64_t n, const T* A, int64_t lda, T* B, int64_t ldb);
-
-template <typename T>
 int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, const T* A, int64_t lda, T* B,
                      int64_t ldb) {
     if (m < 0) return -6;
@@ -1113,9 +1102,6 @@ int trmm_left_upper(rlhip_ctx* c, int trans, int diag, int64_t m, int64_t n, T a
 }
 template int trmm_left_upper<double>(rlhip_ctx*, int, int, int64_t, int64_t, double, const double*, int64_t, double*, int64_t);
 template int trmm_left_upper<float>(rlhip_ctx*, int, int, int64_t, int64_t, float, const float*, int64_t, float*, int64_t);
-
-template <typename T>
-int potrf_upper_enqueue(rlhip_ctx* c, int64_t n, T* A, int64_t lda, int* info_dev);
 
 // Cholesky-QR, Q factor only (RandLAPACK/comps/rl_orth.hh:69-98: syrk -> potrf -> trsm) as ONE stream of kernels with ONE host read:
 //   R (k x k, ld k) = chol(A^T A) (upper; the strictly lower part is zero), A <- A R^-1, *info_host = LAPACK's potrf info.
