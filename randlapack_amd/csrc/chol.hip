@@ -13,7 +13,7 @@
 
 namespace {
 
-using namespace rlhip_dev;   // lane_get
+using namespace rlhip_dev;   // lane_get, dpp_mov
 
 constexpr int NB = 32;
 
@@ -34,25 +34,11 @@ constexpr int PS_LD = 34;          // column stride (doubles) of the LDS copy of
 // value of lane `src` (0..3) of the caller's quad, in all four lanes (DPP quad_perm broadcast)
 template <typename T>
 __device__ __forceinline__ T quad_bcast(T v, const int src) {
-    if constexpr (sizeof(T) == 8) {
-        const double d = (double)v;
-        int lo = __double2loint(d), hi = __double2hiint(d), lo2, hi2;
-        switch (src) {
-            case 0: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x00, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x00, 0xF, 0xF, false); break;
-            case 1: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x55, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x55, 0xF, 0xF, false); break;
-            case 2: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0xAA, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0xAA, 0xF, 0xF, false); break;
-            default: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0xFF, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0xFF, 0xF, 0xF, false); break;
-        }
-        return (T)__hiloint2double(hi2, lo2);
-    } else {
-        int w = __float_as_int((float)v), w2;
-        switch (src) {
-            case 0: w2 = __builtin_amdgcn_update_dpp(0, w, 0x00, 0xF, 0xF, false); break;
-            case 1: w2 = __builtin_amdgcn_update_dpp(0, w, 0x55, 0xF, 0xF, false); break;
-            case 2: w2 = __builtin_amdgcn_update_dpp(0, w, 0xAA, 0xF, 0xF, false); break;
-            default: w2 = __builtin_amdgcn_update_dpp(0, w, 0xFF, 0xF, 0xF, false); break;
-        }
-        return (T)__int_as_float(w2);
+    switch (src) {   // (a constant once the caller's loop is unrolled)
+        case 0: return dpp_mov<DPP_QUAD_PERM + 0x00>(v);
+        case 1: return dpp_mov<DPP_QUAD_PERM + 0x55>(v);
+        case 2: return dpp_mov<DPP_QUAD_PERM + 0xAA>(v);
+        default: return dpp_mov<DPP_QUAD_PERM + 0xFF>(v);
     }
 }
 

@@ -24,7 +24,7 @@ using rlhip::gemm;
 
 namespace {
 
-using namespace rlhip_dev;   // wave_sum, dpp_ror_add
+using namespace rlhip_dev;   // wave_sum, dpp_mov, dpp_ror_add
 
 template <typename T>
 __global__ __launch_bounds__(256) void jacobi_round_kernel(int64_t m, int n, int N, int round, T* __restrict__ A,
@@ -91,22 +91,13 @@ __global__ __launch_bounds__(256) void jacobi_round_kernel(int64_t m, int n, int
 // 64-lane sum without LDS traffic: four DPP row_shr steps leave each 16-lane row's total in its last lane, four
 // v_readlane pick those up as scalars.  (__shfl_xor lowers to ds_bpermute_b32 pairs: 36 LDS round trips per
 // column pair, which made the reductions -- not the rotations -- the cost of a round.)
-__device__ __forceinline__ double dpp_shr_add(double v, const int ctrl_sel) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    int lo2, hi2;
-    switch (ctrl_sel) {   // row_shr:1,2,4,8 with bound_ctrl (zero fill)
-        case 1: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x111, 0xF, 0xF, true); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x111, 0xF, 0xF, true); break;
-        case 2: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x112, 0xF, 0xF, true); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x112, 0xF, 0xF, true); break;
-        case 4: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x114, 0xF, 0xF, true); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x114, 0xF, 0xF, true); break;
-        default: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x118, 0xF, 0xF, true); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x118, 0xF, 0xF, true); break;
-    }
-    return v + __hiloint2double(hi2, lo2);
-}
+template <int N>   // v + (v from N lanes below inside each 16-lane row, zero fill)
+__device__ __forceinline__ double dpp_shr_add(double v) { return v + dpp_mov<DPP_ROW_SHR + N, true>(v); }
 __device__ __forceinline__ double wave_sum_dpp(double v) {
-    v = dpp_shr_add(v, 1);
-    v = dpp_shr_add(v, 2);
-    v = dpp_shr_add(v, 4);
-    v = dpp_shr_add(v, 8);
+    v = dpp_shr_add<1>(v);
+    v = dpp_shr_add<2>(v);
+    v = dpp_shr_add<4>(v);
+    v = dpp_shr_add<8>(v);
     const int lo = __double2loint(v), hi = __double2hiint(v);
     const double r0 = __hiloint2double(__builtin_amdgcn_readlane(hi, 15), __builtin_amdgcn_readlane(lo, 15));
     const double r1 = __hiloint2double(__builtin_amdgcn_readlane(hi, 31), __builtin_amdgcn_readlane(lo, 31));
@@ -159,10 +150,10 @@ constexpr int JM = 256;           // panel rows (LDS)
 // four wavefronts per SIMD = 1.5 us per round; this layout issues ~65 per pair from one or two wavefronts per SIMD.
 // every lane of a 16-lane row ends up with the row's sum
 __device__ __forceinline__ double row16_allsum(double v) {
-    v = dpp_ror_add(v, 8);
-    v = dpp_ror_add(v, 4);
-    v = dpp_ror_add(v, 2);
-    return dpp_ror_add(v, 1);
+    v = dpp_ror_add<8>(v);
+    v = dpp_ror_add<4>(v);
+    v = dpp_ror_add<2>(v);
+    return dpp_ror_add<1>(v);
 }
 
 // every lane of a 32-lane half wave ends up with the half's sum: the 16-lane all-reduce, then v_permlane16_swap (gfx950) trades row 1 of one copy

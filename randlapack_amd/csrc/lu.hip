@@ -159,35 +159,33 @@ __device__ __attribute__((noinline)) unsigned lu_tag_get(const unsigned long lon
     return (unsigned)w;
 }
 
-// one column step with the column index as a template parameter: every x[q][c] index is a compile-time constant, so the panel
-// really stays in registers (a runtime-indexed loop put it in scratch)
-template <typename T, int RPT, int C, bool TAG>
-__device__ __forceinline__ void lu_reg_step(const LuArgs<T>& g, LuRegState<T, RPT>& st, unsigned& epoch, T* s_wv, int64_t* s_wr, int* s_ww, T* s_piv,
-                                            T* s_drow) {
-    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int64_t G = gridDim.x, me = blockIdx.x, m = g.m;
-    const int64_t j = g.j0 + C;
-    constexpr int par = C & 1;
-    // ---- local candidate: first maximum of |x[.][C]| over owned rows >= j (rows increase with q, then with tid)
-    T bv = T(-1); int64_t br = m;
+// column step C of the general register kernel: any number of workgroups, 64-bit rows, rows exchanged by value
+struct LuRegStep {   // (a type: lu_panel_steps<Step> calls Step::run<C> for every column)
+    template <int C, typename T, int RPT>
+    static __device__ __forceinline__ void run(const LuArgs<T>& g, LuRegState<T, RPT>& st, T* s_wv, int64_t* s_wr, int* s_ww, T* s_piv, T* s_drow) {
+        const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+        const int64_t G = gridDim.x, me = blockIdx.x, m = g.m;
+        const int64_t j = g.j0 + C;
+        constexpr int par = C & 1;
+        // ---- local candidate: first maximum of |x[.][C]| over owned rows >= j (rows increase with q, then with tid)
+        T bv = T(-1); int64_t br = m;
 #pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        const T v = fabs(st.x[q][C]);
-        if (st.gr[q] >= j && st.gr[q] < m && v > bv) { bv = v; br = st.gr[q]; }
-    }
+        for (int q = 0; q < RPT; ++q) {
+            const T v = fabs(st.x[q][C]);
+            if (st.gr[q] >= j && st.gr[q] < m && v > bv) { bv = v; br = st.gr[q]; }
+        }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const T v2 = __shfl_xor(bv, off); const int64_t r2 = __shfl_xor(br, off);
-        argmax_take(bv, br, v2, r2, m);
-    }
-    if (lane == 0) { s_wv[wid] = bv; s_wr[wid] = br; }
-    __syncthreads();
-    T lbest = s_wv[0]; int64_t lrow = s_wr[0];
+        for (int off = 32; off > 0; off >>= 1) {
+            const T v2 = __shfl_xor(bv, off); const int64_t r2 = __shfl_xor(br, off);
+            argmax_take(bv, br, v2, r2, m);
+        }
+        if (lane == 0) { s_wv[wid] = bv; s_wr[wid] = br; }
+        __syncthreads();
+        T lbest = s_wv[0]; int64_t lrow = s_wr[0];
 #pragma unroll
-    for (int w = 1; w < 4; ++w) argmax_take(lbest, lrow, s_wv[w], s_wr[w], m);
-    int64_t p; int wstar;
-    LU_MARK(0)
-    if constexpr (TAG) {
+        for (int w = 1; w < 4; ++w) argmax_take(lbest, lrow, s_wv[w], s_wr[w], m);
+        int64_t p; int wstar;
+        LU_MARK(0)
         // ---- flag-less exchange: every published item travels as 8-byte words {tag : 32-bit payload} (a double is two words); a
         //      reader simply re-reads a word until it carries this step's tag.  No store drain, no barrier counter, no acquire fence:
         //      the chain per column is "store lands -> poll sees it" instead of drain + arrive + poll + read.
@@ -197,12 +195,9 @@ __device__ __forceinline__ void lu_reg_step(const LuArgs<T>& g, LuRegState<T, RP
         const unsigned tag = g.tag_base + C + 1;
         unsigned long long* base = g.tw + (size_t)par * (size_t)(W * G + G + W * G * PB + W * PB);
         unsigned long long* cw0 = base, *cw1 = cw0 + W * G, *rw = cw1 + G, *dw = rw + W * G * PB;
-        auto putw = [&](unsigned long long* q, unsigned payload) {
-            __hip_atomic_store(q, ((unsigned long long)tag << 32) | payload, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        };
         auto putv = [&](unsigned long long* q, int64_t idx, T v) {
-            if constexpr (W == 1) putw(q + idx, __float_as_uint((float)v));
-            else { const unsigned long long bits = (unsigned long long)__double_as_longlong((double)v); putw(q + 2 * idx, (unsigned)bits); putw(q + 2 * idx + 1, (unsigned)(bits >> 32)); }
+            if constexpr (W == 1) lu_tag_put(q + idx, tag, __float_as_uint((float)v));
+            else { const unsigned long long bits = (unsigned long long)__double_as_longlong((double)v); lu_tag_put(q + 2 * idx, tag, (unsigned)bits); lu_tag_put(q + 2 * idx + 1, tag, (unsigned)(bits >> 32)); }
         };
         auto getv = [&](const unsigned long long* q, int64_t idx) -> T {
             if constexpr (W == 1) return (T)__uint_as_float(lu_tag_get(q + idx, tag, g.info));
@@ -211,7 +206,7 @@ __device__ __forceinline__ void lu_reg_step(const LuArgs<T>& g, LuRegState<T, RP
                 return (T)__longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
             }
         };
-        if (tid == 0) { putv(cw0, me, lbest); putw(cw1 + me, (unsigned)lrow); }
+        if (tid == 0) { putv(cw0, me, lbest); lu_tag_put(cw1 + me, tag, (unsigned)lrow); }
         if (lrow >= m && tid < PB) putv(rw, me * PB + tid, T(0));   // nothing to offer: a dummy row, so that readers never wait for one
 #pragma unroll
         for (int q = 0; q < RPT; ++q) {
@@ -293,158 +288,46 @@ __device__ __forceinline__ void lu_reg_step(const LuArgs<T>& g, LuRegState<T, RP
             s_drow[tid] = dv_pref;
             s_piv[tid] = (p != j) ? getv(rw, (int64_t)wstar * PB + tid) : dv_pref;
         }
-    } else {
-    if (tid == 0) {
-        pub_store(g.cand_val + par * G + me, lbest);
-        __hip_atomic_store(g.cand_row + par * G + me, lrow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // the owners of the candidate row and of the diagonal row publish those rows' 32 values
+        if (me == 0 && tid == 0) g.ipiv[j] = p + 1;
+        __syncthreads();
+        LU_MARK(3)
+        // ---- exchange rows j <-> p in the owners' registers, then eliminate
+        const T piv = s_piv[C];
+        const T rp = T(1) / piv;
 #pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        if (st.gr[q] == lrow && lrow < m) {
-            T* dst = g.cand_data + ((int64_t)par * G + me) * PB;
+        for (int q = 0; q < RPT; ++q) {
+            if (p != j) {
+                if (st.gr[q] == j) {
 #pragma unroll
-            for (int c2 = 0; c2 < PB; ++c2) pub_store(dst + c2, st.x[q][c2]);
-        }
-        if (st.gr[q] == j) {
-            T* dst = g.diag_data + par * PB;
+                    for (int c2 = 0; c2 < PB; ++c2) st.x[q][c2] = s_piv[c2];
+                } else if (st.gr[q] == p) {
 #pragma unroll
-            for (int c2 = 0; c2 < PB; ++c2) pub_store(dst + c2, st.x[q][c2]);
-        }
-    }
-    grid_barrier(g.bar, (unsigned)(G * (++epoch)));
-    // ---- winner (every workgroup, redundantly): thread w looks at workgroup w's candidate.  The winner's row is needed right
-    //      after the decision; instead of a dependent second round trip every thread prefetches, together with the candidates,
-    //      element (tid % 32) of the candidate rows of workgroups tid / 32, tid / 32 + 8, ... (G <= 64 covers 32768+ rows) and the
-    //      decision then picks the winner's copy out of registers.
-    constexpr int PF = 8;                                        // 8 x 8 = 64 workgroups prefetched
-    T pf[PF];
-    const bool pf_ok = G <= 8 * PF;
-    if (pf_ok) {
+                    for (int c2 = 0; c2 < PB; ++c2) st.x[q][c2] = s_drow[c2];
+                }
+            }
+            if (piv != T(0) && st.gr[q] > j && st.gr[q] < m) {
+                const T l = st.x[q][C] * rp;
+                st.x[q][C] = l;
 #pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            const int64_t ww = (tid >> 5) + 8 * u;
-            pf[u] = g.cand_data[((int64_t)par * G + (ww < G ? ww : G - 1)) * PB + (tid & 31)];
-        }
-    }
-    const T dv_pref = g.diag_data[par * PB + (tid & 31)];
-    {
-        T v = T(-1); int64_t r = m; int w = 0;
-        for (int64_t ww = tid; ww < G; ww += 256) {
-            const T v2 = g.cand_val[par * G + ww]; const int64_t r2 = g.cand_row[par * G + ww];
-            if (r2 < m && (v2 > v || (v2 == v && r2 < r))) { v = v2; r = r2; w = (int)ww; }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const T v2 = __shfl_xor(v, off); const int64_t r2 = __shfl_xor(r, off); const int w2 = __shfl_xor(w, off);
-            if (r2 < m && (v2 > v || (v2 == v && r2 < r))) { v = v2; r = r2; w = w2; }
-        }
-        if (lane == 0) { s_wv[wid] = v; s_wr[wid] = r; s_ww[wid] = w; }
-    }
-    __syncthreads();
-    T gv = s_wv[0]; p = s_wr[0]; wstar = s_ww[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-        if (s_wr[w] < m && (s_wv[w] > gv || (s_wv[w] == gv && s_wr[w] < p))) { gv = s_wv[w]; p = s_wr[w]; wstar = s_ww[w]; }
-    if (p >= m) p = j;                                           // empty / NaN column: no exchange
-    if (pf_ok) {
-        // the thread group (tid / 32) == wstar % 8 holds the winner's row in pf[wstar / 8]
-        if ((tid >> 5) == (wstar & 7)) {
-            T pv = pf[0];
-#pragma unroll
-            for (int u = 1; u < PF; ++u) pv = ((wstar >> 3) == u) ? pf[u] : pv;
-            s_piv[tid & 31] = (p != j) ? pv : dv_pref;
-        }
-        if (tid < PB) s_drow[tid] = dv_pref;
-    } else if (tid < PB) {
-        const T* prow = g.cand_data + ((int64_t)par * G + wstar) * PB;   // contents of row p (becomes row j)
-        s_drow[tid] = dv_pref;
-        s_piv[tid] = (p != j) ? prow[tid] : dv_pref;
-    }
-    }
-    if (me == 0 && tid == 0) g.ipiv[j] = p + 1;
-    __syncthreads();
-    LU_MARK(3)
-    // ---- exchange rows j <-> p in the owners' registers, then eliminate
-    const T piv = s_piv[C];
-    const T rp = T(1) / piv;
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        if (p != j) {
-            if (st.gr[q] == j) {
-#pragma unroll
-                for (int c2 = 0; c2 < PB; ++c2) st.x[q][c2] = s_piv[c2];
-            } else if (st.gr[q] == p) {
-#pragma unroll
-                for (int c2 = 0; c2 < PB; ++c2) st.x[q][c2] = s_drow[c2];
+                for (int c2 = C + 1; c2 < PB; ++c2) st.x[q][c2] -= l * s_piv[c2];
             }
         }
-        if (piv != T(0) && st.gr[q] > j && st.gr[q] < m) {
-            const T l = st.x[q][C] * rp;
-            st.x[q][C] = l;
-#pragma unroll
-            for (int c2 = C + 1; c2 < PB; ++c2) st.x[q][c2] -= l * s_piv[c2];
-        }
+        if (piv == T(0) && me == 0 && tid == 0 && *g.info == 0) *g.info = (int)(j + 1);
+        __syncthreads();                                              // s_piv / s_drow / s_w* are rewritten next column
+        LU_MARK(4)
     }
-    if (piv == T(0) && me == 0 && tid == 0 && *g.info == 0) *g.info = (int)(j + 1);
-    __syncthreads();                                              // s_piv / s_drow / s_w* are rewritten next column
-    LU_MARK(4)
-}
-template <typename T, int RPT, int C, bool TAG>
-__device__ __forceinline__ void lu_reg_steps(const LuArgs<T>& g, LuRegState<T, RPT>& st, unsigned& epoch, T* s_wv, int64_t* s_wr, int* s_ww,
-                                             T* s_piv, T* s_drow) {
-    if constexpr (C < PB) {
-        if (C < g.pb) {                                           // uniform: pb is a kernel argument
-            lu_reg_step<T, RPT, C, TAG>(g, st, epoch, s_wv, s_wr, s_ww, s_piv, s_drow);
-            lu_reg_steps<T, RPT, C + 1, TAG>(g, st, epoch, s_wv, s_wr, s_ww, s_piv, s_drow);
-        }
-    }
-}
-template <typename T, int RPT, bool TAG>
+};
+template <typename T, int RPT>
 __global__ __launch_bounds__(256, (sizeof(T) == 8) ? 2 : 1) void getrf_panel_reg_kernel(LuArgs<T> g) {
     __builtin_amdgcn_s_setprio(3);          // latency-bound: when a look-ahead runs this beside a GEMM on the same CUs, its waves issue first
     __shared__ T s_wv[4];
     __shared__ int64_t s_wr[4];
     __shared__ int s_ww[4];
     __shared__ T s_piv[PB], s_drow[PB];
-    const int tid = threadIdx.x;
-    const int64_t me = blockIdx.x;
-    const int pb = g.pb;
-    const int64_t j0 = g.j0, m = g.m;
-    const int64_t lo = j0 + me * (256 * RPT);
     LuRegState<T, RPT> st;
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        st.gr[q] = lo + tid + 256 * q;
-        const int64_t rr = st.gr[q] < m ? st.gr[q] : m - 1;           // clamped row: unconditional coalesced loads
-#pragma unroll
-        for (int c = 0; c < PB; ++c) st.x[q][c] = g.A[rr + (j0 + (c < pb ? c : pb - 1)) * g.lda];    // clamped row and column: unconditional, all in flight together
-    }
-    // (the selects come after ALL loads: written as `cond ? load : 0` per entry, hipcc sinks every load into its own branch with an
-    // s_waitcnt vmcnt(0) behind it -- 128 dependent L2 round trips = ~30 us per panel launch)
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-#pragma unroll
-        for (int c = 0; c < PB; ++c) st.x[q][c] = (st.gr[q] < m && c < pb) ? st.x[q][c] : T(0);
-    }
-#ifdef RLHIP_LU_PROF
-    for (int i = 0; i < 5; ++i) st.pf[i] = 0;
-    st.pt = wall_clock64();
-#endif
-    unsigned epoch = 0;
-    lu_reg_steps<T, RPT, 0, TAG>(g, st, epoch, s_wv, s_wr, s_ww, s_piv, s_drow);
-#ifdef RLHIP_LU_PROF
-    if (me == (int64_t)gridDim.x / 2 && tid == 0) for (int i = 0; i < 5; ++i) atomicAdd((unsigned long long*)(g.diag_data + 2 * PB) + i, (unsigned long long)st.pf[i]);
-#endif
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        if (st.gr[q] < m) {
-#pragma unroll
-            for (int c = 0; c < PB; ++c)
-                if (c < pb) g.A[st.gr[q] + (j0 + c) * g.lda] = st.x[q][c];
-        }
-    }
+    LU_PANEL_LOAD(T, RPT, g, st)
+    lu_panel_steps<LuRegStep>(g, st, s_wv, s_wr, s_ww, s_piv, s_drow);
+    LU_PANEL_STORE(RPT, g, st)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -693,6 +576,45 @@ __global__ __launch_bounds__(256) void luqrcp_piv_lds_kernel(int64_t sd, int64_t
 
 __global__ void lu_zero_kernel(unsigned* bar, int* info, int zero_info) { *bar = 0; if (zero_info) *info = 0; }
 
+template <typename T>
+constexpr int LU_RPT_BIG = (sizeof(T) == 4) ? 4 : 2;      // rows per thread of the register kernels: 128 VGPRs of panel per thread either way
+
+// the fast step of the type (lu_f32.hip / lu_f64.hip): G <= 64 workgroups
+void launch_getrf_panel_fast(const LuArgs<float>& g, unsigned G, hipStream_t stream) { rlhip_lu::launch_getrf_panel_f32(g, G, stream); }
+void launch_getrf_panel_fast(const LuArgs<double>& g, unsigned G, hipStream_t stream) { rlhip_lu::launch_getrf_panel_f64(g, G, stream); }
+
+// Factors the panel that g describes (g.j0, g.pb, g.rpw; rows = m - j0 of them on and below the diagonal) with the kernel its height asks for.
+// reg_cap: resident capacity of the general register kernel in workgroups (every workgroup spins on the others: all of them must be on
+// the device at once).
+template <typename T>
+int getrf_panel(rlhip_ctx* c, ws_scope& ws, LuArgs<T> g, int64_t rows, int64_t reg_cap) {
+    constexpr int RPT = LU_RPT_BIG<T>;
+    const int64_t G_reg = (rows + 256 * RPT - 1) / (256 * RPT);
+    if (G_reg > reg_cap && G_reg > 64) {
+        // taller than the resident kernels can hold (fp64: 262144 rows, fp32: 262144): column-at-a-time launches on the L2-resident panel
+        const int nparts = (int)((rows / 2048 < 1) ? 1 : (rows / 2048 > 1024 ? 1024 : rows / 2048));
+        T* pval = ws.alloc<T>(1024); int64_t* prow = ws.alloc<int64_t>(1024);
+        if (!pval || !prow) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
+        for (int64_t j = g.j0; j < g.j0 + g.pb; ++j) {
+            hipLaunchKernelGGL(getf2_colmax_kernel<T>, dim3((unsigned)nparts), dim3(256), 0, c->stream, g.m, j, g.A, g.lda, pval, prow);
+            hipLaunchKernelGGL(getf2_pivot_kernel<T>, dim3(1), dim3(256), 0, c->stream, g.m, g.j0, g.pb, j, nparts, g.A, g.lda, pval, prow, g.ipiv, g.info);
+            if (j + 1 < g.m) hipLaunchKernelGGL(getf2_update_kernel<T>, dim3((unsigned)nparts), dim3(256), 0, c->stream, g.m, g.j0, g.pb, j, g.A, g.lda);
+        }
+        c->path_count[7]++;
+    } else if (g.tw && rows >= 1024) {
+        // tagged-word exchange (g.tw is set when m < 2^31): up to 64 workgroups -- 65536 rows in fp32, 32768 in fp64 -- take the fast step
+        g.tag_base = (unsigned)(g.j0 / PB + 1) * 64u;
+        if (G_reg <= 64) launch_getrf_panel_fast(g, (unsigned)G_reg, c->stream);
+        else hipLaunchKernelGGL((getrf_panel_reg_kernel<T, RPT>), dim3((unsigned)G_reg), dim3(256), 0, c->stream, g);
+    } else {
+        // short panels (< 1024 rows, at most 4 workgroups): the LDS-resident kernel
+        const int64_t G = (rows + g.rpw - 1) / g.rpw;
+        hipLaunchKernelGGL(getrf_panel_kernel<T>, dim3((unsigned)G), dim3(256), (size_t)g.pb * g.rpw * sizeof(T), c->stream, g);
+    }
+    RLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
 
 namespace rlhip {
@@ -742,117 +664,81 @@ int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_d
     // default: with the faster fp32 panel step the HBM-bound K = 32 updates of a very tall matrix are worth saving again -- 65536 x 2048
     // fp32: 32.1 ms (outer = panel), 27.0 (64), 25.0 (128), 25.1 (256); 32768 rows: 20.7 / 20.4 / 20.5 / 21.5; 8192 rows: 16.4 / 17.1 / 17.9
     const int64_t nbo = (m >= 49152 && n >= 256) ? 128 : PB;
+    // resident capacity of the general register kernel
+    static int64_t reg_cap[64] = {};
+    if (!reg_cap[c->device & 63]) {
+        int nb = 0;
+        RLHIP_CHECK(hipSetDevice(c->device));
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)getrf_panel_reg_kernel<T, LU_RPT_BIG<T>>, 256, 0) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = 1; }
+        reg_cap[c->device & 63] = (int64_t)nb * num_cu;
+    }
 #ifdef RLHIP_LU_PROF
     hipMemsetAsync(g.diag_data, 0, (2 * PB + 64) * sizeof(T), c->stream);
 #endif
     for (int64_t J0 = 0; J0 < mn; J0 += nbo) {
-    const int64_t Jend = (J0 + nbo < mn) ? J0 + nbo : mn;      // columns factored by this outer block
-    const int64_t Cin = (J0 + nbo < n) ? J0 + nbo : n;         // columns the panel steps keep up to date
-    for (int64_t j0 = J0; j0 < Jend; j0 += PB) {
-        const int pb = (int)((Jend - j0 < PB) ? (Jend - j0) : PB);
-        const int64_t rows = m - j0;
-        // rows per workgroup: at least 64, LDS piece pb*rpw*sizeof(T) <= 96 KiB
-        int64_t rpw = (rows + Gmax - 1) / Gmax;
-        if (rpw < 256) rpw = 256;   // fewer, fatter workgroups: the per-column rendezvous and winner search shrink with G
-        const int64_t rpw_max = (96 * 1024) / (PB * (int64_t)sizeof(T));
-        if (rpw > rpw_max && !(use_tag && rows >= 1024)) return -2;   // LDS variant only: > num_cu * 384 rows (fp64)
-        int64_t G = (rows + rpw - 1) / rpw;
-        g.j0 = j0; g.pb = pb; g.rpw = rpw;
-        // (the tagged-word kernels never touch the barrier counter: only the first panel of a call needs the launch, for `info`)
-        if (j0 == 0 || !(use_tag && rows >= 1024))
-            hipLaunchKernelGGL(lu_zero_kernel, dim3(1), dim3(1), 0, c->stream, g.bar, g.info, j0 == 0 ? 1 : 0);
-        constexpr int RPT_BIG = (sizeof(T) == 4) ? 4 : 2;             // 128 VGPRs of panel per thread either way
-        // resident capacity of the general register kernel (every workgroup spins on the others: all of them must be on the device at once)
-        static int64_t reg_cap[64] = {};
-        if (!reg_cap[c->device & 63]) {
-            int nb = 0;
-            RLHIP_CHECK(hipSetDevice(c->device));
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)getrf_panel_reg_kernel<T, RPT_BIG, true>, 256, 0) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = 1; }
-            reg_cap[c->device & 63] = (int64_t)nb * num_cu;
+        const int64_t Jend = (J0 + nbo < mn) ? J0 + nbo : mn;      // columns factored by this outer block
+        const int64_t Cin = (J0 + nbo < n) ? J0 + nbo : n;         // columns the panel steps keep up to date
+        for (int64_t j0 = J0; j0 < Jend; j0 += PB) {
+            const int pb = (int)((Jend - j0 < PB) ? (Jend - j0) : PB);
+            const int64_t rows = m - j0;
+            // rows per workgroup: at least 64, LDS piece pb*rpw*sizeof(T) <= 96 KiB
+            int64_t rpw = (rows + Gmax - 1) / Gmax;
+            if (rpw < 256) rpw = 256;   // fewer, fatter workgroups: the per-column rendezvous and winner search shrink with G
+            const int64_t rpw_max = (96 * 1024) / (PB * (int64_t)sizeof(T));
+            if (rpw > rpw_max && !(use_tag && rows >= 1024)) return -2;   // LDS variant only: > num_cu * 384 rows (fp64)
+            g.j0 = j0; g.pb = pb; g.rpw = rpw;
+            // (the tagged-word kernels never touch the barrier counter: only the first panel of a call needs the launch, for `info`)
+            if (j0 == 0 || !(use_tag && rows >= 1024))
+                hipLaunchKernelGGL(lu_zero_kernel, dim3(1), dim3(1), 0, c->stream, g.bar, g.info, j0 == 0 ? 1 : 0);
+            if (int rc = getrf_panel(c, ws, g, rows, reg_cap[c->device & 63])) return rc;
+            // row interchanges left of the panel.  The columns of this outer block feed its closing GEMM, so they always follow; the
+            // columns of earlier blocks only keep L consistent and never feed a later pivot decision
+            const int64_t left_lo = pivots_only ? J0 : 0;
+            if (j0 > left_lo)
+                hipLaunchKernelGGL((laswp_kernel<T, false>), dim3(laswp_grid(j0 - left_lo)), dim3(256), 0, c->stream, left_lo, j0, j0, pb, A, lda, ipiv_dev);
+            const int64_t rest = Cin - j0 - pb;
+            if (rest > 0) {
+                // interchanges + U12 = L11^-1 A12 of the columns right of the panel, one launch
+                hipLaunchKernelGGL((laswp_kernel<T, true>), dim3(laswp_grid(rest)), dim3(256), 0, c->stream, j0 + pb, Cin, j0, pb, A, lda, ipiv_dev);
+                RLHIP_LAUNCH_CHECK();
+                const int64_t mrest = m - j0 - pb;
+                if (mrest > 0) {
+                    int rc = gemm_impl<T>(c, 0, 0, mrest, rest, pb, T(-1), A + (j0 + pb) + j0 * lda, lda, A + j0 + (j0 + pb) * lda, lda, T(1),
+                                          A + (j0 + pb) + (j0 + pb) * lda, lda, 0);
+                    if (rc) return rc;
+                }
+            }
         }
-        const int64_t G_reg = (rows + 256 * RPT_BIG - 1) / (256 * RPT_BIG);
-        if (G_reg > reg_cap[c->device & 63] && G_reg > 64) {
-            // taller than the resident kernels can hold (fp64: 262144 rows, fp32: 262144): column-at-a-time launches on the L2-resident panel
-            const int nparts = (int)((rows / 2048 < 1) ? 1 : (rows / 2048 > 1024 ? 1024 : rows / 2048));
-            T* pval = ws.alloc<T>(1024); int64_t* prow = ws.alloc<int64_t>(1024);
-            if (!pval || !prow) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
-            for (int64_t j = j0; j < j0 + pb; ++j) {
-                hipLaunchKernelGGL(getf2_colmax_kernel<T>, dim3((unsigned)nparts), dim3(256), 0, c->stream, m, j, A, lda, pval, prow);
-                hipLaunchKernelGGL(getf2_pivot_kernel<T>, dim3(1), dim3(256), 0, c->stream, m, j0, pb, j, nparts, A, lda, pval, prow, ipiv_dev, g.info);
-                if (j + 1 < m) hipLaunchKernelGGL(getf2_update_kernel<T>, dim3((unsigned)nparts), dim3(256), 0, c->stream, m, j0, pb, j, A, lda);
+        // ---- the columns right of the outer block: interchanges, U12 = L11^-1 A12 by 32-row blocks, A22 -= L21 U12
+        const int64_t right = n - Cin;
+        if (right > 0) {
+            const unsigned gr = laswp_grid(right);
+            const bool one_panel = (Jend - J0 <= PB);                  // the outer block is a single panel: interchanges + its forward substitution in one launch
+            for (int64_t q0 = J0; q0 < Jend; q0 += PB) {
+                const int cnt = (int)((Jend - q0 < PB) ? (Jend - q0) : PB);
+                if (one_panel) hipLaunchKernelGGL((laswp_kernel<T, true>), dim3(gr), dim3(256), 0, c->stream, Cin, n, q0, cnt, A, lda, ipiv_dev);
+                else hipLaunchKernelGGL((laswp_kernel<T, false>), dim3(gr), dim3(256), 0, c->stream, Cin, n, q0, cnt, A, lda, ipiv_dev);
             }
-            c->path_count[7]++;
-        } else
-        if (use_tag && rows >= 1024) {
-            G = (rows + 256 * RPT_BIG - 1) / (256 * RPT_BIG);
-            g.tag_base = (unsigned)(j0 / PB + 1) * 64u;
-            bool launched = false;
-            if constexpr (sizeof(T) == 4) {
-                if (G <= 64 && m < ((int64_t)1 << 31)) {        // up to 65536 rows below the diagonal: the step of lu_f32_step
-                    rlhip_lu::launch_getrf_panel_f32(g, (unsigned)G, c->stream);
-                    launched = true;
+            const unsigned gs = (unsigned)((right + 255) / 256);
+            for (int64_t s0 = J0; s0 < Jend && !one_panel; s0 += PB) {
+                const int sb = (int)((Jend - s0 < PB) ? (Jend - s0) : PB);
+                hipLaunchKernelGGL(unit_lower_solve_kernel<T>, dim3(gs), dim3(256), 0, c->stream, Cin, n, s0, sb, A, lda);
+                RLHIP_LAUNCH_CHECK();
+                const int64_t below = Jend - (s0 + sb);
+                if (below > 0) {
+                    int rc = gemm_impl<T>(c, 0, 0, below, right, sb, T(-1), A + (s0 + sb) + s0 * lda, lda, A + s0 + Cin * lda, lda, T(1),
+                                          A + (s0 + sb) + Cin * lda, lda, 0);
+                    if (rc) return rc;
                 }
             }
-            if constexpr (sizeof(T) == 8) {
-                if (G <= 64 && m < ((int64_t)1 << 31)) {        // up to 32768 rows below the diagonal: the step of lu_f64_step
-                    rlhip_lu::launch_getrf_panel_f64(g, (unsigned)G, c->stream);
-                    launched = true;
-                }
-            }
-            if (!launched)
-            hipLaunchKernelGGL((getrf_panel_reg_kernel<T, RPT_BIG, true>), dim3((unsigned)G), dim3(256), 0, c->stream, g);
-        } else   // short panels (< 1024 rows, at most 4 workgroups): the LDS-resident kernel; one register-kernel instantiation per type keeps the
-                 // build of this file (32 unrolled column steps) within minutes
-            hipLaunchKernelGGL(getrf_panel_kernel<T>, dim3((unsigned)G), dim3(256), (size_t)pb * rpw * sizeof(T), c->stream, g);
-        RLHIP_LAUNCH_CHECK();
-        // row interchanges left of the panel.  The columns of this outer block feed its closing GEMM, so they always follow; the
-        // columns of earlier blocks only keep L consistent and never feed a later pivot decision
-        const int64_t left_lo = pivots_only ? J0 : 0;
-        if (j0 > left_lo)
-            hipLaunchKernelGGL((laswp_kernel<T, false>), dim3(laswp_grid(j0 - left_lo)), dim3(256), 0, c->stream, left_lo, j0, j0, pb, A, lda, ipiv_dev);
-        const int64_t rest = Cin - j0 - pb;
-        if (rest > 0) {
-            // interchanges + U12 = L11^-1 A12 of the columns right of the panel, one launch
-            hipLaunchKernelGGL((laswp_kernel<T, true>), dim3(laswp_grid(rest)), dim3(256), 0, c->stream, j0 + pb, Cin, j0, pb, A, lda, ipiv_dev);
             RLHIP_LAUNCH_CHECK();
-            const int64_t mrest = m - j0 - pb;
+            const int64_t mrest = m - Jend;
             if (mrest > 0) {
-                int rc = gemm_impl<T>(c, 0, 0, mrest, rest, pb, T(-1), A + (j0 + pb) + j0 * lda, lda, A + j0 + (j0 + pb) * lda, lda, T(1),
-                                      A + (j0 + pb) + (j0 + pb) * lda, lda, 0);
+                int rc = gemm_impl<T>(c, 0, 0, mrest, right, Jend - J0, T(-1), A + Jend + J0 * lda, lda, A + J0 + Cin * lda, lda, T(1),
+                                      A + Jend + Cin * lda, lda, 0);
                 if (rc) return rc;
             }
         }
-    }
-    // ---- the columns right of the outer block: interchanges, U12 = L11^-1 A12 by 32-row blocks, A22 -= L21 U12
-    const int64_t right = n - Cin;
-    if (right > 0) {
-        const unsigned gr = laswp_grid(right);
-        const bool one_panel = (Jend - J0 <= PB);                  // the outer block is a single panel: interchanges + its forward substitution in one launch
-        for (int64_t q0 = J0; q0 < Jend; q0 += PB) {
-            const int cnt = (int)((Jend - q0 < PB) ? (Jend - q0) : PB);
-            if (one_panel) hipLaunchKernelGGL((laswp_kernel<T, true>), dim3(gr), dim3(256), 0, c->stream, Cin, n, q0, cnt, A, lda, ipiv_dev);
-            else hipLaunchKernelGGL((laswp_kernel<T, false>), dim3(gr), dim3(256), 0, c->stream, Cin, n, q0, cnt, A, lda, ipiv_dev);
-        }
-        const unsigned gs = (unsigned)((right + 255) / 256);
-        for (int64_t s0 = J0; s0 < Jend && !one_panel; s0 += PB) {
-            const int sb = (int)((Jend - s0 < PB) ? (Jend - s0) : PB);
-            hipLaunchKernelGGL(unit_lower_solve_kernel<T>, dim3(gs), dim3(256), 0, c->stream, Cin, n, s0, sb, A, lda);
-            RLHIP_LAUNCH_CHECK();
-            const int64_t below = Jend - (s0 + sb);
-            if (below > 0) {
-                int rc = gemm_impl<T>(c, 0, 0, below, right, sb, T(-1), A + (s0 + sb) + s0 * lda, lda, A + s0 + Cin * lda, lda, T(1),
-                                      A + (s0 + sb) + Cin * lda, lda, 0);
-                if (rc) return rc;
-            }
-        }
-        RLHIP_LAUNCH_CHECK();
-        const int64_t mrest = m - Jend;
-        if (mrest > 0) {
-            int rc = gemm_impl<T>(c, 0, 0, mrest, right, Jend - J0, T(-1), A + Jend + J0 * lda, lda, A + J0 + Cin * lda, lda, T(1),
-                                  A + Jend + Cin * lda, lda, 0);
-            if (rc) return rc;
-        }
-    }
     }
 #ifdef RLHIP_LU_PROF
     {

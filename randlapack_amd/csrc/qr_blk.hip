@@ -32,7 +32,7 @@ struct QbArgs {
 #endif
 };
 
-using namespace rlhip_dev;   // pub_store, lane_get
+using namespace rlhip_dev;   // pub_store, lane_get, dpp_mov
 
 // The write-through (sc1) store of pub_store, but issued without the s_waitcnt vmcnt(0) hipcc puts in front of every agent-scope atomic store: a
 // thread's 32 stores of a chunk would otherwise go out one memory round trip at a time.  The workgroup drains them once, before its flag.
@@ -42,11 +42,10 @@ __device__ __forceinline__ void qb_store_wt(double* p, double v) { asm volatile(
 // value of lane ^ D for D = 1, 2, 4, 8 on the VALU (DPP quad permutations / row rotations; no LDS crossbar round trip)
 template <int D>
 __device__ __forceinline__ int qb_fetch_i(int x) {
-    if constexpr (D == 1) return __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false);            // quad_perm [1,0,3,2]
-    else if constexpr (D == 2) return __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false);       // quad_perm [2,3,0,1]
-    else if constexpr (D == 4)                                                                          // row_half_mirror (l ^ 7) then quad_perm [3,2,1,0] (l ^ 3)
-        return __builtin_amdgcn_update_dpp(0, __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, false), 0x1B, 0xF, 0xF, false);
-    else return __builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, false);                             // row_ror:8
+    if constexpr (D == 1) return dpp_mov<DPP_QUAD_PERM + 0xB1>(x);                                     // quad_perm [1,0,3,2]
+    else if constexpr (D == 2) return dpp_mov<DPP_QUAD_PERM + 0x4E>(x);                                // quad_perm [2,3,0,1]
+    else if constexpr (D == 4) return dpp_mov<DPP_QUAD_PERM + 0x1B>(dpp_mov<DPP_ROW_HALF_MIRROR>(x));  // row_half_mirror (l ^ 7) then quad_perm [3,2,1,0] (l ^ 3)
+    else return dpp_mov<DPP_ROW_ROR + 8>(x);
 }
 template <int D> __device__ __forceinline__ float qb_fetch(float v) { return __int_as_float(qb_fetch_i<D>(__float_as_int(v))); }
 template <int D> __device__ __forceinline__ double qb_fetch(double v) {

@@ -47,7 +47,7 @@ using namespace rlhip_dev;   // pub_store, grid_barrier, wave_allsum, dpp_ror_ad
 template <typename T>
 __device__ __forceinline__ T wave_sum_fast(T x) {
     double v = (double)x;                                       // (fp32 inputs: the sum itself in double, rounded once)
-    v = dpp_ror_add(v, 8); v = dpp_ror_add(v, 4); v = dpp_ror_add(v, 2); v = dpp_ror_add(v, 1);
+    v = dpp_ror_add<8>(v); v = dpp_ror_add<4>(v); v = dpp_ror_add<2>(v); v = dpp_ror_add<1>(v);
     const int lo = __double2loint(v), hi = __double2hiint(v);
     double r = 0;
 #pragma unroll

@@ -44,18 +44,33 @@ __device__ __forceinline__ T wave_allsum(T v) {
     return v;
 }
 
-// v + (v rotated right by n lanes inside each 16-lane row), n = 8, 4, 2 or 1: one DPP step of a row all-reduce at VALU speed
-__device__ __forceinline__ double dpp_ror_add(double v, const int n) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    int lo2, hi2;
-    switch (n) {   // row_ror:n  (rotate inside each 16-lane row)
-        case 1: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x121, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x121, 0xF, 0xF, false); break;
-        case 2: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x122, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x122, 0xF, 0xF, false); break;
-        case 4: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x124, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x124, 0xF, 0xF, false); break;
-        default: lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x128, 0xF, 0xF, false); hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x128, 0xF, 0xF, false); break;
-    }
-    return v + __hiloint2double(hi2, lo2);
+// ---- the one DPP move: every lane receives x from the lane that the control word CTRL names (v_mov_b32 with a DPP modifier, VALU speed,
+//      no LDS crossbar), all rows and banks enabled; a lane whose source falls outside its row gets 0, with or without BOUND_CTRL.
+//      The control is an immediate of the instruction, hence a template argument.  64-bit values move as two words, low half first.
+constexpr int DPP_QUAD_PERM = 0x000;         // + a | b << 2 | c << 4 | d << 6: lanes 0..3 of every quad take the quad's lanes a, b, c, d
+constexpr int DPP_ROW_SHR = 0x110;           // + n (1..15): from n lanes below, inside each 16-lane row
+constexpr int DPP_ROW_ROR = 0x120;           // + n (1..15): the same, wrapping around inside the row
+constexpr int DPP_ROW_HALF_MIRROR = 0x141;   // lane l of each 8-lane half row takes lane 7 - l
+template <int CTRL, bool BOUND_CTRL = false>
+__device__ __forceinline__ int dpp_mov(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, BOUND_CTRL); }
+template <int CTRL, bool BOUND_CTRL = false>
+__device__ __forceinline__ unsigned dpp_mov(unsigned x) { return (unsigned)dpp_mov<CTRL, BOUND_CTRL>((int)x); }
+template <int CTRL, bool BOUND_CTRL = false>
+__device__ __forceinline__ float dpp_mov(float x) { return __int_as_float(dpp_mov<CTRL, BOUND_CTRL>(__float_as_int(x))); }
+template <int CTRL, bool BOUND_CTRL = false>
+__device__ __forceinline__ unsigned long long dpp_mov(unsigned long long x) {
+    const unsigned lo = dpp_mov<CTRL, BOUND_CTRL>((unsigned)x), hi = dpp_mov<CTRL, BOUND_CTRL>((unsigned)(x >> 32));
+    return ((unsigned long long)hi << 32) | lo;
 }
+template <int CTRL, bool BOUND_CTRL = false>
+__device__ __forceinline__ double dpp_mov(double x) {
+    const int lo = dpp_mov<CTRL, BOUND_CTRL>(__double2loint(x)), hi = dpp_mov<CTRL, BOUND_CTRL>(__double2hiint(x));
+    return __hiloint2double(hi, lo);
+}
+
+// v + (v rotated right by N lanes inside each 16-lane row), N = 8, 4, 2 or 1: one DPP step of a row all-reduce at VALU speed
+template <int N>
+__device__ __forceinline__ double dpp_ror_add(double v) { return v + dpp_mov<DPP_ROW_ROR + N>(v); }
 
 // value held by lane l (wave-uniform l; a compile-time constant after unrolling): v_readlane, a scalar
 __device__ __forceinline__ float lane_get(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
