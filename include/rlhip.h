@@ -511,6 +511,13 @@ int rlhip_allreduce_sum_host_f64(rlhip_ctx* ctx, double* x_host, int64_t n);   /
  * kernel (gemm_tn_skinny_kernel), 30 scale-only calls (k == 0 or alpha == 0: C = beta C, also counted for beta == 1, which launches nothing),
  * 31 a contraction cut in two or more calls by gemm_impl itself (the k-remainder peel, the fp32 chunks of 16384 and their Gram twin; the
  * pieces count their own routes), 32 a product whose last m % 128 rows were peeled off a persistent launch and given to another route.
+ * The sketching operator (sketch.hip, one count per call): 33 a sketch application that launched the register-staged kernel
+ * (saso_apply_kernel; beside 14 when a ragged first or last row block went to it), 34 that call used 2-column slabs, 35 a 1-column slab
+ * (both beside 33; neither: 4 columns); an independent-column operator built 36 by the one-workgroup-per-block LDS kernel
+ * (saso_ind_block_kernel) or 37 by the generate / scan / scatter / sort chain.  The CSR kernels (sparse.hip): a product served by 38 the
+ * wavefront-per-row kernel (csr_spmm_rm_kernel), 39 the narrow row-major kernel (csr_spmm_rm_narrow_kernel), 40 the narrow kernel with a
+ * column-major result (csr_spmm_cmout_narrow_kernel); a transpose scattered 41 by entry number and sorted row by row, 42 by the stable
+ * counting sort over chunks.
  * -1 for an unknown index.  Tests use it to assert that the kernel / route under test is the one that ran. */
 int64_t rlhip_path_count(rlhip_ctx* ctx, int which);
 /* the host layers above this ABI (include/RandLAPACK_amd/) report their own route decisions into the same counters */

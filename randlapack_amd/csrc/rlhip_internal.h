@@ -59,7 +59,7 @@
 
 // Execution context: one HIP stream + a growable device scratch arena + a small
 // pinned host mailbox for info codes / scalars coming back from the device.
-constexpr int RLHIP_NPATH = 33;          // slots of rlhip_path_count (indices: include/rlhip.h)
+constexpr int RLHIP_NPATH = 43;          // slots of rlhip_path_count (indices: include/rlhip.h)
 struct rlhip_ctx {
     int device = 0;
     int num_cu = 256;            // compute units of THIS context's device (persistent kernels size their grids with it)

@@ -864,6 +864,7 @@ int saso_build(rlhip_ctx* c, int64_t d, int64_t m, int nnz, int mode, const uint
             hipLaunchKernelGGL(saso_ind_block_kernel, dim3((unsigned)op->T), dim3(SIB_THREADS), sib_lds, c->stream, d, m, nnz, st, op->T, op->rows, op->ptr,
                                op->src, op->src16);
             RLHIP_LAUNCH_CHECK();
+            c->path_count[36]++;
         } else if (op->T > 0) {
             ws_scope ws(c);
             int32_t* cnt = ws.alloc<int32_t>(nkeys);
@@ -878,6 +879,7 @@ int saso_build(rlhip_ctx* c, int64_t d, int64_t m, int nnz, int mode, const uint
                                op->ptr, cursor, op->src);
             hipLaunchKernelGGL(saso_ind_sort_kernel, dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, c->stream, (int64_t)nkeys, op->ptr, op->src, op->src16);
             RLHIP_LAUNCH_CHECK();
+            c->path_count[37]++;
         }
         inc = (uint64_t)m * (uint64_t)((nnz + 1) / 2);
     }
@@ -943,7 +945,7 @@ int saso_apply_rows(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T*
     int64_t G = (1024 + ctiles - 1) / ctiles;                       // ~4 workgroups per CU in flight
     if (G > nTb) G = nTb;
     if (G < 1) G = 1;
-    const int64_t tpg = (nTb + G - 1) / G;
+    const int64_t tpg = std::max<int64_t>((nTb + G - 1) / G, 1);    // (1: a shard without rows, nTb == 0 -- B = beta B below; 0 here divided by zero in the next line)
     G = (nTb + tpg - 1) / tpg;
     if (G < 1) G = 1;
     // LDS-DMA route (saso_apply_dma_kernel): independent-column operator with 16-bit lists, whole 4-column slabs, 16-byte aligned
@@ -999,6 +1001,11 @@ int saso_apply_rows(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T*
         else rc = (CT == 4) ? RLHIP_SASO_LAUNCH(4, 0, partial, G, tpg, tb0, tb1) : (CT == 2) ? RLHIP_SASO_LAUNCH(2, 0, partial, G, tpg, tb0, tb1) : RLHIP_SASO_LAUNCH(1, 0, partial, G, tpg, tb0, tb1);
 #undef RLHIP_SASO_LAUNCH
         if (rc) return rc;
+        if (!dma || head || tail) {                                      // the register-staged kernel ran (beside 14: a ragged head or tail block)
+            c->path_count[33]++;
+            if (CT == 2) c->path_count[34]++;
+            if (CT == 1) c->path_count[35]++;
+        }
     }
     RLHIP_LAUNCH_CHECK();
     const int64_t total = d * n;

@@ -184,6 +184,7 @@ int csr_spmm_rowmajor(rlhip_ctx* c, int64_t nrows, int64_t nc, const int64_t* ro
         if (nc <= 16) hipLaunchKernelGGL((csr_spmm_rm_narrow_kernel<T, 16>), grid, dim3(256), 0, c->stream, nrows, nc, rowptr, colidx, vals, alpha, B, ldb, beta, C, ldc);
         else hipLaunchKernelGGL((csr_spmm_rm_narrow_kernel<T, 32>), grid, dim3(256), 0, c->stream, nrows, nc, rowptr, colidx, vals, alpha, B, ldb, beta, C, ldc);
         RLHIP_LAUNCH_CHECK();
+        c->path_count[39]++;
         return 0;
     }
     if (nc > 128) {
@@ -197,6 +198,7 @@ int csr_spmm_rowmajor(rlhip_ctx* c, int64_t nrows, int64_t nc, const int64_t* ro
         hipLaunchKernelGGL((csr_spmm_rm_kernel<T, 1>), grid, dim3(256), 0, c->stream, nrows, nc, rowptr, colidx, vals, alpha, B, ldb, beta, C, ldc);
     }
     RLHIP_LAUNCH_CHECK();
+    c->path_count[38]++;
     return 0;
 }
 
@@ -218,6 +220,7 @@ int csr_spmm(rlhip_ctx* c, int layout_rowmajor, int64_t nrows, int64_t k, int64_
             else hipLaunchKernelGGL((csr_spmm_cmout_narrow_kernel<T, 32>), grid, dim3(256), 0, c->stream, nrows, nc, rowptr, colidx, vals, alpha, Bt, nc, beta, C, ldc);
             const hipError_t le = hipGetLastError();
             if (le != hipSuccess) rc = RLHIP_ERR_HIP(le);
+            else c->path_count[40]++;
         }
         return rc;
     }
@@ -490,6 +493,7 @@ int csr_transpose(rlhip_ctx* c, int64_t m, int64_t k, const int64_t* rowptr, con
             hipLaunchKernelGGL(ct_scatter_key_kernel, dim3(gh), dim3(256), 0, c->stream, nnz, colidx, (const int64_t*)rowptrT, cursor, colidxT);
             hipLaunchKernelGGL(ct_sortfill_kernel<T>, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, k, (const int64_t*)rowptrT, colidxT, (const int64_t*)rowid, vals, valsT);
             if (hipGetLastError() != hipSuccess) rc = -1;
+            else c->path_count[41]++;
             break;
         }
         // ---- a long transposed row somewhere: the stable counting sort over chunks of the entry list
@@ -506,6 +510,7 @@ int csr_transpose(rlhip_ctx* c, int64_t m, int64_t k, const int64_t* rowptr, con
         hipLaunchKernelGGL(ct_chunk_scan_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, nb, k, cnt, total);   // (total: the same values again)
         hipLaunchKernelGGL(ct_scatter_kernel<T>, dim3((unsigned)nb), dim3(64), 0, c->stream, m, nnz, per, k, rowptr, colidx, vals, rowptrT, cnt, colidxT, valsT, (const int64_t*)rowid);
         if (hipGetLastError() != hipSuccess) rc = -1;
+        else c->path_count[42]++;
     } while (0);
     return rc;
 }
