@@ -142,31 +142,31 @@ int lange_fro(rlhip_ctx* c, int64_t m, int64_t n, const T* A, int64_t lda, T* re
     if (!partial) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     hipLaunchKernelGGL(ssq_partial_kernel<T>, grid, dim3(256), 0, c->stream, m, n, A, lda, partial);
     RLHIP_LAUNCH_CHECK();
-    double* d_out = (double*)c->d_mail;
+    double* d_out = (double*)(c->d_mail + MAIL_SCALAR);
     hipLaunchKernelGGL(ssq_final_kernel, dim3(1), dim3(256), 0, c->stream, np, partial, d_out);
     RLHIP_LAUNCH_CHECK();
-    RLHIP_CHECK(hipMemcpyAsync(c->h_mail, d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_SCALAR, d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     RLHIP_CHECK(rlhip_stream_sync(c));
-    double ssq = *(double*)c->h_mail;
+    double ssq = *(double*)(c->h_mail + MAIL_SCALAR);
     if (!(ssq > 0.0) || ssq > 1.7e308) {
         // all zeros, NaN, or the plain sum of squares over- / underflowed (entries beyond ~1e154 or below ~1e-154): redo it the way
         // LAPACK's dlassq does, relative to the largest entry -- one more pass, taken only here
-        unsigned long long* d_mx = (unsigned long long*)(c->d_mail + 1);
+        unsigned long long* d_mx = (unsigned long long*)(c->d_mail + MAIL_ABSMAX);
         RLHIP_CHECK(hipMemsetAsync(d_mx, 0, sizeof(unsigned long long), c->stream));
         hipLaunchKernelGGL(absmax_kernel<T>, grid, dim3(256), 0, c->stream, m, n, A, lda, d_mx);
         RLHIP_LAUNCH_CHECK();
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 1, d_mx, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_ABSMAX, d_mx, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
         double mx;
-        memcpy(&mx, c->h_mail + 1, sizeof(double));
+        memcpy(&mx, c->h_mail + MAIL_ABSMAX, sizeof(double));
         if (mx != mx || mx > 1.7e308) { *result_host = (T)mx; return 0; }     // NaN / inf entries: that is the norm
         if (mx == 0.0) { *result_host = T(0); return 0; }
         hipLaunchKernelGGL(ssq_scaled_partial_kernel<T>, grid, dim3(256), 0, c->stream, m, n, A, lda, mx, partial);
         hipLaunchKernelGGL(ssq_final_kernel, dim3(1), dim3(256), 0, c->stream, np, partial, d_out);
         RLHIP_LAUNCH_CHECK();
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail, d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_SCALAR, d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
-        *result_host = (T)(mx * sqrt(*(double*)c->h_mail));
+        *result_host = (T)(mx * sqrt(*(double*)(c->h_mail + MAIL_SCALAR)));
         return 0;
     }
     *result_host = (T)sqrt(ssq);

@@ -132,8 +132,8 @@ int rlhip_create(rlhip_ctx** out, int device, void* hip_stream, int own_stream) 
         RLHIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
         c->owns_stream = true;
     }
-    RLHIP_CHECK(hipHostMalloc((void**)&c->h_mail, 64 * sizeof(int64_t), hipHostMallocDefault));
-    RLHIP_CHECK(hipMalloc((void**)&c->d_mail, 64 * sizeof(int64_t)));
+    RLHIP_CHECK(hipHostMalloc((void**)&c->h_mail, MAIL_WORDS * sizeof(int64_t), hipHostMallocDefault));
+    RLHIP_CHECK(hipMalloc((void**)&c->d_mail, MAIL_WORDS * sizeof(int64_t)));
     RLHIP_CHECK(hipEventCreate(&c->ev0));
     RLHIP_CHECK(hipEventCreate(&c->ev1));
     RLHIP_CHECK(hipEventCreateWithFlags(&c->ev_flag, hipEventDisableTiming));
@@ -596,7 +596,7 @@ int rlhip_gemm_norma_f64(rlhip_ctx* c, char ta, char tb, int64_t m, int64_t n, i
     int fa, fb;
     if (op_flag(ta, &fa)) return -2;
     if (op_flag(tb, &fb)) return -3;
-    double* d_ssq = (double*)(c->d_mail + 40);
+    double* d_ssq = (double*)(c->d_mail + MAIL_NORMA_SSQ);
     hipLaunchKernelGGL(rlhip_zero_f64_kernel, dim3(1), dim3(1), 0, c->stream, d_ssq);
     int done = 0;
     int rc = rlhip::gemm_impl<double>(c, fa, fb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 0, d_ssq, &done);
@@ -608,7 +608,7 @@ int rlhip_gemm_norma_f64(rlhip_ctx* c, char ta, char tb, int64_t m, int64_t n, i
     if (done == 2 && norm_a_host == nullptr) {
         // deferred: the sum of squares travels to the pinned mailbox behind the stream; rlhip_norma_collect_f64 picks it up after whatever
         // synchronisation comes next (QB reads ||A||_F and ||B_i||_F with ONE host round trip this way)
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 40, d_ssq, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_NORMA_SSQ, d_ssq, sizeof(double), hipMemcpyDeviceToHost, c->stream));
         c->norma_state = 1;
         c->norma_epoch = c->sync_epoch;
         return 0;
@@ -619,9 +619,9 @@ int rlhip_gemm_norma_f64(rlhip_ctx* c, char ta, char tb, int64_t m, int64_t n, i
         if (rc) return rc;
     } else {
         double ssq_main = 0, rest = 0;
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 40, d_ssq, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_NORMA_SSQ, d_ssq, sizeof(double), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
-        ssq_main = *(double*)(c->h_mail + 40);
+        ssq_main = *(double*)(c->h_mail + MAIL_NORMA_SSQ);
         const int64_t m_main = (m / 128) * 128;
         if (m_main < m && done != 2) {   // rows (or, for op = T, columns) peeled off to the generic kernel
             const double* A2 = fa ? (A + m_main * lda) : (A + m_main);
@@ -641,8 +641,8 @@ int rlhip_norma_collect_f64(rlhip_ctx* c, int over_ranks, double* norm_a_host) {
     bool global = false;
     if (c->norma_state == 1) {
         if (c->sync_epoch == c->norma_epoch) RLHIP_CHECK(rlhip_stream_sync(c));      // (normally a later call has already waited on the stream: no second round trip)
-        if (over_ranks && c->norma_reduced) { ssq = *(double*)(c->h_mail + 41); global = true; }
-        else ssq = *(double*)(c->h_mail + 40);
+        if (over_ranks && c->norma_reduced) { ssq = *(double*)(c->h_mail + MAIL_NORMA_SSQ_RANKS); global = true; }
+        else ssq = *(double*)(c->h_mail + MAIL_NORMA_SSQ);
     } else if (c->norma_state == 2) {
         ssq = c->norma_value * c->norma_value;
     } else {
@@ -744,7 +744,7 @@ extern "C" int rlhip_dvfs_burn(rlhip_ctx* c, int blocks, int mode, int usec, int
         if (!c->side) RLHIP_CHECK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
         st = c->side;
     }
-    hipLaunchKernelGGL(dvfs_burn_kernel, dim3((unsigned)blocks), dim3(256), 0, st, mode, (long long)usec * 100, (double*)c->d_mail + 32);
+    hipLaunchKernelGGL(dvfs_burn_kernel, dim3((unsigned)blocks), dim3(256), 0, st, mode, (long long)usec * 100, (double*)(c->d_mail + MAIL_DVFS_SINK));
     RLHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -797,7 +797,7 @@ extern "C" int rlhip_avoid_persistent(rlhip_ctx* c, int on) {
 
 extern "C" int rlhip_mfma_peak(rlhip_ctx* c, int is_f64, int iters, double* tflops) {
     const int blocks = 256 * 8, threads = 256;  // 2 waves per SIMD
-    double* d = (double*)c->d_mail;
+    double* d = (double*)(c->d_mail + MAIL_SCALAR);
     for (int rep = 0; rep < 2; ++rep) {
         RLHIP_CHECK(hipEventRecord(c->ev0, c->stream));
         if (is_f64)
@@ -817,7 +817,7 @@ extern "C" int rlhip_mfma_peak(rlhip_ctx* c, int is_f64, int iters, double* tflo
 
 extern "C" int rlhip_hbm_read_peak(rlhip_ctx* c, const void* buf, size_t bytes, double* gbps) {
     size_t n16 = bytes / 16;
-    double* d = (double*)c->d_mail;
+    double* d = (double*)(c->d_mail + MAIL_SCALAR);
     for (int rep = 0; rep < 2; ++rep) {
         RLHIP_CHECK(hipEventRecord(c->ev0, c->stream));
         hipLaunchKernelGGL(hbm_read_kernel, dim3(256 * 16), dim3(256), 0, c->stream, (const double2*)buf, n16, d);

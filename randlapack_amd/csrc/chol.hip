@@ -254,15 +254,15 @@ int potrf_upper(rlhip_ctx* c, int64_t n, T* A, int64_t lda, int* info_host) {
     if (n < 0) return -2;
     if (lda < (n > 1 ? n : 1)) return -4;
     if (n == 0) return 0;
-    int* d_info = (int*)(c->d_mail + 8);
+    int* d_info = (int*)(c->d_mail + MAIL_POTRF_INFO);
     if (n <= PS_MAXN) {
         const size_t smem = (size_t)(32 * 33 + 64 + (size_t)(n + 16) * PS_LD) * sizeof(T);
         RLHIP_FUNC_LDS(c, potrf_small_kernel<T>, 150 * 1024);
         hipLaunchKernelGGL(potrf_small_kernel<T>, dim3(1), dim3(1024), smem, c->stream, (int)n, A, lda, d_info, 0);
         RLHIP_LAUNCH_CHECK();
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 8, d_info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_POTRF_INFO, d_info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
-        *info_host = *(int*)(c->h_mail + 8);
+        *info_host = *(int*)(c->h_mail + MAIL_POTRF_INFO);
         return 0;
     }
     {
@@ -300,9 +300,9 @@ int potrf_upper(rlhip_ctx* c, int64_t n, T* A, int64_t lda, int* info_host) {
             }
         }
         if (rc) return rc;
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 8, d_info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_POTRF_INFO, d_info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
-        const int v = *(int*)(c->h_mail + 8);
+        const int v = *(int*)(c->h_mail + MAIL_POTRF_INFO);
         *info_host = v ? v - 1 : 0;
         return 0;
     }

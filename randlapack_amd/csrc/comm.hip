@@ -189,8 +189,8 @@ int rlhip_allreduce_sum_f64(rlhip_ctx* c, double* buf, int64_t count) { return a
 int rlhip_allreduce_sum_f32(rlhip_ctx* c, float* buf, int64_t count) { return allreduce_impl(c, buf, count, 0); }
 
 int rlhip_allreduce_sum_host_f64(rlhip_ctx* c, double* x_host, int64_t n) {
-    if (n <= 0 || n > 16 || !c->comm || comm_of(c)->nranks <= 1) return (n > 16) ? -3 : 0;
-    double* d = (double*)(c->d_mail + 32);
+    if (n <= 0 || n > MAIL_HOST_REDUCE_WORDS || !c->comm || comm_of(c)->nranks <= 1) return (n > MAIL_HOST_REDUCE_WORDS) ? -3 : 0;
+    double* d = (double*)(c->d_mail + MAIL_HOST_REDUCE);
     RLHIP_CHECK(hipMemcpyAsync(d, x_host, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     int rc = allreduce_impl(c, d, n, 1);
     if (rc) return rc;

@@ -18,7 +18,7 @@
 //  * tall reductions (A^T*Q, Gram matrices) use a deterministic split-K: each K-slice writes a slab
 //    to scratch and a second kernel sums the slabs in fixed order (bitwise reproducible run to run,
 //    unlike atomics).
-#include "rlhip_internal.h"
+#include "rlhip_device.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -28,25 +28,7 @@ typedef double d4_t __attribute__((ext_vector_type(4)));
 typedef float f4_t __attribute__((ext_vector_type(4)));
 
 template <typename T>
-struct Mma;
-template <>
-struct Mma<double> {
-    using acc_t = d4_t;
-    static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) {
-        return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-    }
-    // f64 D layout: col = lane & 15, row = (lane >> 4) + 4 * r
-    static __device__ __forceinline__ int drow(int lane, int r) { return (lane >> 4) + 4 * r; }
-};
-template <>
-struct Mma<float> {
-    using acc_t = f4_t;
-    static __device__ __forceinline__ acc_t mma(float a, float b, acc_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-    }
-    // f32 D layout: col = lane & 15, row = 4 * (lane >> 4) + r
-    static __device__ __forceinline__ int drow(int lane, int r) { return 4 * (lane >> 4) + r; }
-};
+using Mma = rlhip_dev::Mfma16x4<T>;   // D layout: col = lane & 15, row = drow(lane, r)
 
 template <typename T>
 struct GemmArgs {

@@ -27,12 +27,14 @@
 //     accumulators per wave).  A 16-byte piece now holds four consecutive k, i.e. it feeds FOUR MFMA steps:
 //     step (sigma, h), lane group fk  <->  kk = 16*sigma + 4*fk + h;  MC image: lane fr reads rows 4*fr .. 4*fr+3 of one k-row, i.e.
 //     fragment x, lane fr  <->  row 4*fr + x.  Accumulator layout of the f32 MFMA: lane (fr, fk), register r = C[row(fr)][16u + 4fk + r].
-#include "rlhip_internal.h"
+#include "rlhip_device.h"
 #include <cstdlib>
 #include <type_traits>
 #include <cstdio>
 
 namespace {
+
+using namespace rlhip_dev;   // Mfma16x4, IntC
 
 typedef double d4_t __attribute__((ext_vector_type(4)));
 typedef double d2_t __attribute__((ext_vector_type(2)));
@@ -47,22 +49,14 @@ constexpr int STAGE = STAGE_A + STAGE_B;      // 48 KiB
 constexpr int NSTAGE = 3;
 constexpr int SLAB_ELEMS = BM * BN;
 
-template <int N> struct HC { static constexpr int value = N; };
-
 template <typename T> struct SkT;
-template <> struct SkT<double> {
+template <> struct SkT<double> : Mfma16x4<double> {    // (drow_g(fk, r): the trait's accumulator index is this kernel's COLUMN inside a 16-wide tile, register r)
     static constexpr int BK = 16, EPP = 2, NH = 2;      // k per tile, elements per 16-byte piece, MFMA steps fed by one piece
     typedef d2_t frag_t;                                 // one 16-byte LDS read
-    typedef d4_t acc_t;
-    static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int ccol(int fk, int r) { return fk + 4 * r; }       // column inside a 16-wide tile of register r
 };
-template <> struct SkT<float> {
+template <> struct SkT<float> : Mfma16x4<float> {
     static constexpr int BK = 32, EPP = 4, NH = 4;
     typedef f4_t frag_t;
-    typedef f4_t acc_t;
-    static __device__ __forceinline__ acc_t mma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ int ccol(int fk, int r) { return 4 * fk + r; }
 };
 
 template <typename T>
@@ -360,25 +354,25 @@ __global__ __launch_bounds__(512, 1) void gemm_sk_kernel(SkArgs<T> g) {
                     for (int e = 0; e < 4; ++e) ssq_acc = fma((double)v0[e], (double)v0[e], fma((double)v1[e], (double)v1[e], ssq_acc));
                 }
             }
-            mma16(fa0, fb0, HC<0>{});
-            mma16(fa0, fb0, HC<1>{});
-            if constexpr (NH == 4) { mma16(fa0, fb0, HC<2>{}); mma16(fa0, fb0, HC<3>{}); }
+            mma16(fa0, fb0, IntC<0>{});
+            mma16(fa0, fb0, IntC<1>{});
+            if constexpr (NH == 4) { mma16(fa0, fb0, IntC<2>{}); mma16(fa0, fb0, IntC<3>{}); }
             if (t + 1 < nk_i) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             // unconditional (straight-line code lets hipcc use a counted lgkmcnt for F1 instead of lgkmcnt(0));
             // on the last tile this reads a stale stage and the values are never used
             fetch(smem + st_next * STAGE, 0, fa0, fb0);
-            mma16(fa1, fb1, HC<0>{});
-            if constexpr (NH == 4) mma16(fa1, fb1, HC<1>{});
+            mma16(fa1, fb1, IntC<0>{});
+            if constexpr (NH == 4) mma16(fa1, fb1, IntC<1>{});
             __builtin_amdgcn_sched_barrier(0);
             if (t + 2 < nk_i) issue(t + 2, st_prev);   // DMA issue slots hidden behind the MFMAs just queued
             __builtin_amdgcn_sched_barrier(0);
-            mma16(fa1, fb1, HC<NH / 2>{});
-            if constexpr (NH == 4) mma16(fa1, fb1, HC<3>{});
+            mma16(fa1, fb1, IntC<NH / 2>{});
+            if constexpr (NH == 4) mma16(fa1, fb1, IntC<3>{});
             st_cur = st_next;
         }
 
-        // ---- epilogue: lane owns C[i = crow(x)][j = 16u + ccol(fk, r)] of its 64 x 64 wave tile
+        // ---- epilogue: lane owns C[i = crow(x)][j = 16u + drow_g(fk, r)] of its 64 x 64 wave tile
         // C row of fragment x, lane fr (MC images interleave the fragments' rows, see header)
         auto crow = [&](int x) {
             if constexpr (A_KC) return wm0 + 16 * x + fr;
@@ -398,11 +392,11 @@ __global__ __launch_bounds__(512, 1) void gemm_sk_kernel(SkArgs<T> g) {
                 for (int u = 0; u < 4; ++u) {
                     f4_t cv[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) cv[r] = *reinterpret_cast<const f4_t*>(g.C + i0 + (n0 + wn0 + 16 * u + S::ccol(fk, r)) * g.ldc);
+                    for (int r = 0; r < 4; ++r) cv[r] = *reinterpret_cast<const f4_t*>(g.C + i0 + (n0 + wn0 + 16 * u + S::drow_g(fk, r)) * g.ldc);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        *reinterpret_cast<f4_t*>(g.C + i0 + (n0 + wn0 + 16 * u + S::ccol(fk, r)) * g.ldc) =
+                        *reinterpret_cast<f4_t*>(g.C + i0 + (n0 + wn0 + 16 * u + S::drow_g(fk, r)) * g.ldc) =
                             f4_t{acc[0][u][r], acc[1][u][r], acc[2][u][r], acc[3][u][r]} * g.alpha + g.beta * cv[r];
                 }
             } else if (whole) {
@@ -410,7 +404,7 @@ __global__ __launch_bounds__(512, 1) void gemm_sk_kernel(SkArgs<T> g) {
                 for (int u = 0; u < 4; ++u)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const int64_t j = n0 + wn0 + 16 * u + S::ccol(fk, r);
+                        const int64_t j = n0 + wn0 + 16 * u + S::drow_g(fk, r);
                         f4_t v = f4_t{acc[0][u][r], acc[1][u][r], acc[2][u][r], acc[3][u][r]} * g.alpha;
                         T* dst = g.C + i0 + j * g.ldc;
                         if (i0 >= m_lim) continue;                     // rows of a partial tile that do not exist (4 | M % 128: all four or none)
@@ -432,7 +426,7 @@ __global__ __launch_bounds__(512, 1) void gemm_sk_kernel(SkArgs<T> g) {
                 for (int u = 0; u < 4; ++u)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        *reinterpret_cast<f4_t*>(out + (wm0 + 4 * fr) + (wn0 + 16 * u + S::ccol(fk, r)) * BM) =
+                        *reinterpret_cast<f4_t*>(out + (wm0 + 4 * fr) + (wn0 + 16 * u + S::drow_g(fk, r)) * BM) =
                             f4_t{acc[0][u][r], acc[1][u][r], acc[2][u][r], acc[3][u][r]};
             }
         } else
@@ -447,7 +441,7 @@ __global__ __launch_bounds__(512, 1) void gemm_sk_kernel(SkArgs<T> g) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         int64_t i, j;
-                        const bool ok = sk_cpos(td, g.tri, crow(x), wn0 + 16 * u + S::ccol(fk, r), i, j) && i < m_lim;
+                        const bool ok = sk_cpos(td, g.tri, crow(x), wn0 + 16 * u + S::drow_g(fk, r), i, j) && i < m_lim;
                         off[u][r] = ok ? i + j * g.ldc : (int64_t)-1;
                         cv[u][r] = g.C[ok ? off[u][r] : 0];
                     }
@@ -466,7 +460,7 @@ __global__ __launch_bounds__(512, 1) void gemm_sk_kernel(SkArgs<T> g) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         int64_t i, j;
-                        if (!sk_cpos(td, g.tri, crow(x), wn0 + 16 * u + S::ccol(fk, r), i, j) || i >= m_lim) continue;
+                        if (!sk_cpos(td, g.tri, crow(x), wn0 + 16 * u + S::drow_g(fk, r), i, j) || i >= m_lim) continue;
                         g.C[i + j * g.ldc] = g.alpha * acc[x][u][r];
                     }
         } else {
@@ -477,7 +471,7 @@ __global__ __launch_bounds__(512, 1) void gemm_sk_kernel(SkArgs<T> g) {
                 for (int u = 0; u < 4; ++u)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        out[crow(x) + (wn0 + 16 * u + S::ccol(fk, r)) * BM] = acc[x][u][r];
+                        out[crow(x) + (wn0 + 16 * u + S::drow_g(fk, r)) * BM] = acc[x][u][r];
         }
         pos += nk;
     }

@@ -379,13 +379,13 @@ template <typename T>
 int any_abs_gt(rlhip_ctx* c, int64_t n, const T* x, T thr, int* any_host) {
     *any_host = 0;
     if (n <= 0) return 0;
-    int* d_flag = (int*)(c->d_mail + 48);
+    int* d_flag = (int*)(c->d_mail + MAIL_ANY_FLAG);
     hipLaunchKernelGGL(zero_int2, dim3(1), dim3(1), 0, c->stream, d_flag);
     hipLaunchKernelGGL(any_abs_gt_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, x, thr, d_flag);
     RLHIP_LAUNCH_CHECK();
-    RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 48, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_ANY_FLAG, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     RLHIP_CHECK(rlhip_stream_sync(c));
-    *any_host = *(int*)(c->h_mail + 48);
+    *any_host = *(int*)(c->h_mail + MAIL_ANY_FLAG);
     return 0;
 }
 
@@ -491,11 +491,11 @@ static int cholqr2_skinny(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda,
     if (rc) return rc < 0 ? rc : RLHIP_ERR_HIP(hipErrorUnknown);
     hipLaunchKernelGGL(r2_identity_dev_kernel<T>, dim3(1), dim3(256), 0, c->stream, (int)n, R2, (int64_t)n, dev1);
     RLHIP_LAUNCH_CHECK();
-    RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 44, flags, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 46, dev1, sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_GEQRF_CHOLQR, flags, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_GEQRF_CHOLQR + 2, dev1, sizeof(T), hipMemcpyDeviceToHost, c->stream));
     RLHIP_CHECK(rlhip_stream_sync(c));
-    const int info1 = *(const int*)(c->h_mail + 44), info2 = *(const int*)(c->h_mail + 45);
-    const T dev_h = *(const T*)(c->h_mail + 46);
+    const int info1 = *(const int*)(c->h_mail + MAIL_GEQRF_CHOLQR), info2 = *(const int*)(c->h_mail + MAIL_GEQRF_CHOLQR + 1);
+    const T dev_h = *(const T*)(c->h_mail + MAIL_GEQRF_CHOLQR + 2);
     if (info1) return 0;                                                             // A untouched (the solve saw the flag)
     if (info2 || !(dev_h <= T(1e-2))) return trmm_right_upper<T>(c, NonUnit, m, n, T(1), R1, n, A, lda);   // restore A = Q1 R1
     rc = skinny_trsm<T>(c, m, n, R2, n, A, lda, nullptr);                            // A = Q

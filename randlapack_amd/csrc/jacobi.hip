@@ -792,9 +792,9 @@ int jacobi_verify_converged(rlhip_ctx* c, int m, int n, const T* A, int64_t lda,
             // tol the check failed on that noise for every flat-spectrum factor -- one hand-back, one Gram matrix and one sweep that then
             // rotated nothing: 0.23 ms of the 3.66 ms device SVD of the RSVD tail.  The sweeps' own rotation criterion stays at tol.)
             hipLaunchKernelGGL(gram_offdiag_kernel<T>, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, c->stream, n, G, (T)(4 * tol), flag);
-            RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 16, d_nrot, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+            RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_JACOBI, d_nrot, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
             RLHIP_CHECK(rlhip_stream_sync(c));
-            *ok = (*((unsigned*)(c->h_mail + 16) + 1) == 0u);
+            *ok = (*((unsigned*)(c->h_mail + MAIL_JACOBI) + 1) == 0u);
         }
     }
     return 0;
@@ -878,17 +878,17 @@ int persistent_jacobi_sweeps(rlhip_ctx* c, int m, int n, T* A, int64_t lda, T to
         g.n = n; g.sweep0 = sweep; g.max_sweeps = max_sweeps; g.A = A; g.lda = lda; g.tol = tol; g.out = out; g.trans_upper = 0; g.skip = nullptr; g.norm_ratio_lim = 0.f;
         const int lrc = jp_launch<T>(c, g, buf, m, NBk);
         if (lrc) return lrc;
-        hipError_t e2 = hipMemcpyAsync(c->h_mail + 16, out, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+        hipError_t e2 = hipMemcpyAsync(c->h_mail + MAIL_JACOBI, out, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
         if (e2 == hipSuccess) e2 = rlhip_stream_sync(c);
         if (e2 != hipSuccess) return RLHIP_ERR_HIP(e2);
-        const int status = *(int*)(c->h_mail + 16), done_sweeps = *((int*)(c->h_mail + 16) + 1), any_lost = *((int*)(c->h_mail + 16) + 2);
+        const int status = *(int*)(c->h_mail + MAIL_JACOBI), done_sweeps = *((int*)(c->h_mail + MAIL_JACOBI) + 1), any_lost = *((int*)(c->h_mail + MAIL_JACOBI) + 2);
         {
             static int want_clk = -1;
             if (want_clk < 0) { const char* e = getenv("RLHIP_JACOBI_CLOCK"); want_clk = e ? atoi(e) : 0; }
-            const unsigned long long* tk = reinterpret_cast<const unsigned long long*>((const int*)(c->h_mail + 16) + 4);
-            if (want_clk && tk[1]) fprintf(stderr, "[jacobi clock] %d sweeps, %.1f us at %.0f MHz (hold %d, same-XCD hand-over %d)\n", done_sweeps - sweep, (double)tk[1] / 100.0, (double)tk[0] / ((double)tk[1] / 100.0), hold, *((const int*)(c->h_mail + 16) + 3));
+            const unsigned long long* tk = reinterpret_cast<const unsigned long long*>((const int*)(c->h_mail + MAIL_JACOBI) + 4);
+            if (want_clk && tk[1]) fprintf(stderr, "[jacobi clock] %d sweeps, %.1f us at %.0f MHz (hold %d, same-XCD hand-over %d)\n", done_sweeps - sweep, (double)tk[1] / 100.0, (double)tk[0] / ((double)tk[1] / 100.0), hold, *((const int*)(c->h_mail + MAIL_JACOBI) + 3));
         }
-        if (*((const int*)(c->h_mail + 16) + 3) == 1) c->path_count[15]++;     // the workers shared one XCD and handed their blocks over through its L2
+        if (*((const int*)(c->h_mail + MAIL_JACOBI) + 3) == 1) c->path_count[15]++;     // the workers shared one XCD and handed their blocks over through its L2
         if ((status != 1 && status != 2 && status != 3) || any_lost) { *sweeps_out = sweep; return 1; }   // -7, a lost word anywhere, or nothing written: A untouched by this launch
         int rc = rlhip::lacpy<T>(c, 2, m, n, reinterpret_cast<const T*>(buf), m, A, lda);
         if (rc) return rc < 0 ? rc : 1;
@@ -922,9 +922,9 @@ int block_jacobi_sweeps_qw(rlhip_ctx* c, int m, int n, T* A, int64_t lda, T* V, 
         hipLaunchKernelGGL((jacobi_block_kernel<T, JB, JMT, QW>), dim3(1), dim3(NT), smem, c->stream, m, n, NBk, 0, 1, A, lda, V, (int64_t)n, tol, d_nrot,
                            max_sweeps - sweep);
         RLHIP_LAUNCH_CHECK();
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 16, d_nrot, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_JACOBI, d_nrot, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
-        const unsigned* hw = (const unsigned*)(c->h_mail + 16);
+        const unsigned* hw = (const unsigned*)(c->h_mail + MAIL_JACOBI);
         *sweeps_out = sweep + (int)hw[2];
         return 0;                                      // (hw[0] != 0: the sweep limit was reached, as the loop below would leave it)
     }
@@ -936,11 +936,11 @@ int block_jacobi_sweeps_qw(rlhip_ctx* c, int m, int n, T* A, int64_t lda, T* V, 
             hipLaunchKernelGGL((jacobi_block_kernel<T, JB, JMT, QW>), dim3(NBk / 2), dim3(NT), smem, c->stream, m, n, NBk, oround, 0, A, lda,
                                V, (int64_t)n, tol, d_nrot, 0);
         RLHIP_LAUNCH_CHECK();
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 16, d_nrot, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_JACOBI, d_nrot, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
-        const unsigned nrot = *(unsigned*)(c->h_mail + 16);
+        const unsigned nrot = *(unsigned*)(c->h_mail + MAIL_JACOBI);
         float cos2;
-        memcpy(&cos2, (const char*)(c->h_mail + 16) + sizeof(unsigned), sizeof(float));
+        memcpy(&cos2, (const char*)(c->h_mail + MAIL_JACOBI) + sizeof(unsigned), sizeof(float));
         if (nrot == 0) { ++sweep; break; }
         // Every cosine met in this sweep was <= 1e-9: for separated singular values the rotations just applied leave cosines
         // of order n * 1e-18 (quadratic convergence) and a further all-idle sweep would only confirm it.  For CLUSTERED
@@ -1036,7 +1036,7 @@ int gesvdj_core(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T
     T* Sraw = ws.alloc<T>((size_t)n);
     int* rank = ws.alloc<int>((size_t)n);
     if ((VT != nullptr && !V) || !W || !Sraw || !rank) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
-    unsigned* d_nrot = (unsigned*)(c->d_mail + 16);
+    unsigned* d_nrot = (unsigned*)(c->d_mail + MAIL_JACOBI);
     int rc = V ? laset<T>(c, 2, n, n, T(0), T(1), V, n) : 0;
     if (rc) return rc;
     const T tol = std::sqrt((T)m) * std::numeric_limits<T>::epsilon();
@@ -1073,9 +1073,9 @@ int gesvdj_core(rlhip_ctx* c, int64_t m, int64_t n64, T* A, int64_t lda, T* S, T
                                    lda, V, (int64_t)n, tol, d_nrot);
             }
             RLHIP_LAUNCH_CHECK();
-            RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 16, d_nrot, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+            RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_JACOBI, d_nrot, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
             RLHIP_CHECK(rlhip_stream_sync(c));
-            unsigned nrot = *(unsigned*)(c->h_mail + 16);
+            unsigned nrot = *(unsigned*)(c->h_mail + MAIL_JACOBI);
             if (nrot == 0) { ++sweep; break; }
         }
         if (sweep >= max_sweeps) info = 1;

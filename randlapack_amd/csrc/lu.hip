@@ -751,9 +751,9 @@ int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_d
     }
 #endif
     if (info_host) {
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 56, g.info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_PANEL_INFO, g.info, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
-        *info_host = *(int*)(c->h_mail + 56);
+        *info_host = *(int*)(c->h_mail + MAIL_PANEL_INFO);
         if (*info_host < 0) return -9;   // the flag-less exchange timed out (bounded so that a lost word cannot hang the device)
     }
     return 0;

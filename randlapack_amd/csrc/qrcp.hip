@@ -1286,7 +1286,7 @@ static int qr_core(rlhip_ctx* c, int pivot, int64_t m, int64_t n, T* A, int64_t 
                 else (void)hipGetLastError();                          // not resident here: the rendezvous kernel decides for itself
             }
             if (launched) {
-                te = hipMemcpyAsync(c->h_mail + 56, t.info, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+                te = hipMemcpyAsync(c->h_mail + MAIL_PANEL_INFO, t.info, sizeof(int), hipMemcpyDeviceToHost, c->stream);
                 if (te == hipSuccess) te = rlhip_stream_sync(c);
             }
             if (te != hipSuccess) return RLHIP_ERR_HIP(te);
@@ -1298,7 +1298,7 @@ static int qr_core(rlhip_ctx* c, int pivot, int64_t m, int64_t n, T* A, int64_t 
                         pf[0] / 100.0 / kq, pf[1] / 100.0 / kq, pf[2] / 100.0 / kq, pf[3] / 100.0 / kq, pf[4] / 100.0 / kq, pf[5] / 100.0 / kq);
             }
 #endif
-            if (launched && *(int*)(c->h_mail + 56) == 0) {
+            if (launched && *(int*)(c->h_mail + MAIL_PANEL_INFO) == 0) {
                 // the kernel only read A: its results are taken over now (10 MB at 1280 x 1024: microseconds)
                 te = hipMemcpy2DAsync(A, (size_t)lda * sizeof(T), t.Aout, (size_t)m * sizeof(T), (size_t)m * sizeof(T), (size_t)n, hipMemcpyDeviceToDevice, c->stream);
                 if (te == hipSuccess) te = hipMemcpyAsync(jpvt_dev, t.jpvt, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream);

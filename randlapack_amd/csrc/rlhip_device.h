@@ -78,4 +78,27 @@ __device__ __forceinline__ double lane_get(double v, int l) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
 
+// ---- the 16 x 16 x 4 MFMA of either precision: accumulator type, the instruction, and where a lane's four accumulator registers sit.
+//      Lane `lane` holds index lane & 15 along one dimension of the 16 x 16 tile and, in register r, index
+//      drow(lane, r) = CL * (lane >> 4) + CS * r along the other (fp64: (lane >> 4) + 4 r, fp32: 4 (lane >> 4) + r); drow_g is the same for
+//      a caller that already holds the lane group g = lane >> 4.
+template <typename T> struct Mfma16x4;
+template <> struct Mfma16x4<double> {
+    typedef double acc_t __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+    static constexpr int CS = 4, CL = 1;
+    static __device__ __forceinline__ int drow_g(int g, int r) { return CL * g + CS * r; }
+    static __device__ __forceinline__ int drow(int lane, int r) { return drow_g(lane >> 4, r); }
+};
+template <> struct Mfma16x4<float> {
+    typedef float acc_t __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ acc_t mma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+    static constexpr int CS = 1, CL = 4;
+    static __device__ __forceinline__ int drow_g(int g, int r) { return CL * g + CS * r; }
+    static __device__ __forceinline__ int drow(int lane, int r) { return drow_g(lane >> 4, r); }
+};
+
+// an integer as a type: the argument of a generic lambda that needs it at compile time
+template <int N> struct IntC { static constexpr int value = N; };
+
 }  // namespace rlhip_dev

@@ -57,6 +57,54 @@
         }                                                                                                                  \
     } while (0)
 
+// ---- the mailbox slots (c->h_mail / c->d_mail: MAIL_WORDS 8-byte words each; a slot index holds in both unless a line says otherwise).
+// Owner file, extent in words, lifetime.  "transient": written, waited for and read inside ONE call of the owner (copy, wait, read), so
+// two transient ranges may overlap -- several do, each noted below; "across calls": the value waits in the slot for a LATER call.
+constexpr int MAIL_WORDS = 64;
+constexpr int MAIL_SCALAR = 0;              // aux.hip lange_fro: sum of squares; capi.hip peak probes: their never-taken store.  1, transient
+constexpr int MAIL_ABSMAX = 1;              // aux.hip lange_fro: largest |entry| of the rescaled pass.  1, transient
+constexpr int MAIL_POTRF_INFO = 8;          // chol.hip potrf_upper: LAPACK's info.  1, transient
+constexpr int MAIL_JACOBI = 16;             // jacobi.hip: rotation counters on the device (4 unsigned), up to 8 ints read back.  4, transient
+constexpr int MAIL_TRSM_VERDICT = 16;       // tri.hip (h_mail only): block verdicts + pivot verdict, 33 ints.  17 (reaches MAIL_SVD_RATIO,
+constexpr int MAIL_TRSM_VERDICT_WORDS = 17; //   MAIL_SVD_GRAM_DEV and the first word of MAIL_SVD_GRAM), transient
+constexpr int MAIL_SVD_RATIO = 24;          // svd.hip gesdd_tall_core: diagonal ratio of the first Cholesky factor.  1, transient
+constexpr int MAIL_SVD_GRAM_DEV = 25;       // svd.hip gesdd_tall_core: max |Q^T Q - I| after pass 1.  1, transient
+constexpr int MAIL_SVD_GRAM = 32;           // svd.hip gesdd_tall_gram (h_mail only): the Jacobi launch's 8 ints, then the defect (double) in
+constexpr int MAIL_SVD_GRAM_WORDS = 5;      //   word MAIL_SVD_GRAM_DEFECT.  5, transient
+constexpr int MAIL_SVD_GRAM_DEFECT = MAIL_SVD_GRAM + 4;
+constexpr int MAIL_HOST_REDUCE = 32;        // comm.hip rlhip_allreduce_sum_host_f64 (d_mail only): up to 16 doubles.  16, transient -- but from
+constexpr int MAIL_HOST_REDUCE_WORDS = 16;  //   the 9th double on it OVERWRITES d_mail's MAIL_NORMA_SSQ (across calls): see the note below
+constexpr int MAIL_DVFS_SINK = 32;          // capi.hip rlhip_dvfs_burn (d_mail only): the burn kernel's never-taken store.  1, transient
+constexpr int MAIL_NORMA_SSQ = 40;          // capi.hip rlhip_gemm_norma_f64: ||A||_F^2 fused into a product.  1, ACROSS CALLS while norma_state == 1:
+                                            //   h_mail for rlhip_norma_collect_f64, d_mail for tri.hip cholqrq (rides on the Gram all-reduce)
+constexpr int MAIL_NORMA_SSQ_RANKS = 41;    // tri.hip cholqrq -> capi.hip rlhip_norma_collect_f64 (h_mail only): that sum over the row shards.
+                                            //   1, ACROSS CALLS while norma_reduced == 1
+constexpr int MAIL_GEQRF_CHOLQR = 44;       // house.hip geqrf_cholqr (h_mail only): two potrf infos (words 0, 1), |R2 - I| (word 2).  3, transient
+constexpr int MAIL_CHOLQRQ = 44;            // tri.hip cholqrq (h_mail only): potrf info + block verdicts, 40 ints.  20 (to the mailbox's end: covers
+constexpr int MAIL_CHOLQRQ_WORDS = 20;      //   every slot from MAIL_GEQRF_CHOLQR to MAIL_SAMPLE_HDR), transient
+constexpr int MAIL_ANY_FLAG = 48;           // house.hip any_abs_gt: the flag.  1, transient
+constexpr int MAIL_CSR_NNZ = 50;            // sparse.hip csr_transpose (h_mail only): rowptr[m].  1, transient
+constexpr int MAIL_CSR_BAD = 51;            // sparse.hip csr_transpose: index-check flag, then the longest transposed row in word
+constexpr int MAIL_CSR_MAXLEN = MAIL_CSR_BAD + 1;   //   MAIL_CSR_MAXLEN; cleared and read back together.  2, transient
+constexpr int MAIL_PANEL_INFO = 56;         // lu.hip getrf, qrcp.hip (h_mail only): the panel kernel's info word.  1, transient
+constexpr int MAIL_SAMPLE_HDR = 60;         // rpchol.hip (h_mail only): SampleHdr.  4, transient
+constexpr int MAIL_SAMPLE_HDR_WORDS = 4;
+constexpr bool mail_disjoint(int a, int na, int b, int nb) { return a + na <= b || b + nb <= a; }
+static_assert(MAIL_TRSM_VERDICT + MAIL_TRSM_VERDICT_WORDS <= MAIL_WORDS && MAIL_SVD_GRAM + MAIL_SVD_GRAM_WORDS <= MAIL_WORDS &&
+              MAIL_HOST_REDUCE + MAIL_HOST_REDUCE_WORDS <= MAIL_WORDS && MAIL_CHOLQRQ + MAIL_CHOLQRQ_WORDS <= MAIL_WORDS &&
+              MAIL_CSR_BAD + 2 <= MAIL_WORDS && MAIL_SAMPLE_HDR + MAIL_SAMPLE_HDR_WORDS <= MAIL_WORDS, "a mailbox extent ends within the mailbox");
+// no transient range of h_mail covers the two across-call slots
+static_assert(mail_disjoint(MAIL_TRSM_VERDICT, MAIL_TRSM_VERDICT_WORDS, MAIL_NORMA_SSQ, 2) && mail_disjoint(MAIL_SVD_GRAM, MAIL_SVD_GRAM_WORDS, MAIL_NORMA_SSQ, 2) &&
+              mail_disjoint(MAIL_JACOBI, 4, MAIL_NORMA_SSQ, 2) && mail_disjoint(MAIL_CHOLQRQ, MAIL_CHOLQRQ_WORDS, MAIL_NORMA_SSQ, 2),
+              "a transient h_mail range covers the deferred norm");
+// The same does NOT hold in d_mail: MAIL_HOST_REDUCE's 16 doubles span words 32 .. 47 and MAIL_NORMA_SSQ is word 40.  A host all-reduce of
+// more than 8 doubles issued between a product that deferred its norm (norma_state == 1) and the cholqrq(reduce_gram) that reads
+// d_mail + MAIL_NORMA_SSQ replaces the sum of squares by the all-reduce's 9th value.  Such a caller exists: blas::Queue::shard_extent
+// (include/RandLAPACK_amd/rl_blaspp.hh) reduces one double per rank, n = world size, so from nine ranks on it writes d_mail words 40 .. 47.
+// It is called from rl_rs.hh, rl_linops.hh (twice), rl_cqrrpt.hh (twice), rl_cqrrt.hh, rl_bqrrp.hh, rl_abrik.hh, rl_qr_linops.hh and
+// rl_sharded_panel.hh.  Whether one of those calls can fall between a product that defers its norm and the cholqrq(reduce_gram) behind
+// it has NOT been established for any of them; until it has, treat the overlap as reachable with more than eight ranks.
+
 // Execution context: one HIP stream + a growable device scratch arena + a small
 // pinned host mailbox for info codes / scalars coming back from the device.
 constexpr int RLHIP_NPATH = 43;          // slots of rlhip_path_count (indices: include/rlhip.h)
@@ -76,8 +124,8 @@ struct rlhip_ctx {
     size_t cur_used = 0;      // bytes used inside segs[cur_seg]
     size_t ws_highwater = 0;  // largest virtual offset ever reached
     // pinned mailbox
-    int64_t* h_mail = nullptr;   // 64 x int64 host-pinned
-    int64_t* d_mail = nullptr;   // 64 x int64 device
+    int64_t* h_mail = nullptr;   // MAIL_WORDS x int64 host-pinned (slots: the MAIL_ table above)
+    int64_t* d_mail = nullptr;   // MAIL_WORDS x int64 device
     void* xchg = nullptr;        // exchange words of the persistent panel kernels (see rlhip_xchg_buffer)
     size_t xchg_bytes = 0;
     void* xloc = nullptr;        // ordinary (cached) twin of the exchange buffer: same-XCD hand-overs of the persistent Jacobi launch (rlhip_xloc_buffer)
@@ -86,10 +134,10 @@ struct rlhip_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_flag = nullptr;   // marks a flag read-back INSIDE a stream of launches: the host waits for the flags only, the device runs on (tri.hip)
     // ||A||_F fused into a product and not yet collected (rlhip_gemm_norma_f64 with a null result pointer): 0 nothing, 1 the sum of squares
-    // is on its way to h_mail[40] behind the stream, 2 norma_value holds the norm
+    // is on its way to h_mail[MAIL_NORMA_SSQ] behind the stream, 2 norma_value holds the norm
     int norma_state = 0;
     double norma_value = 0;
-    int norma_reduced = 0;           // 1: the sum over the row shards is on its way to h_mail[41] as well (rode on the Gram matrix's all-reduce, tri.hip::cholqrq)
+    int norma_reduced = 0;           // 1: the sum over the row shards is on its way to h_mail[MAIL_NORMA_SSQ_RANKS] as well (rode on the Gram matrix's all-reduce, tri.hip::cholqrq)
     unsigned long norma_epoch = 0;   // sync_epoch when the deferred copy was enqueued
     unsigned long sync_epoch = 0;    // completed host waits on the stream (rlhip_stream_sync): anything enqueued before the last one has landed
     // != 0: products take the tiled kernel whose workgroups come and go, not the persistent stream-K kernel that holds every CU for its whole

@@ -133,6 +133,7 @@ struct SampleHdr {
     int64_t status;      // 0 / 1 / 2
     int64_t count;       // indices written by the draw kernel
 };
+static_assert(sizeof(SampleHdr) == MAIL_SAMPLE_HDR_WORDS * sizeof(int64_t), "the header is read back through its mailbox slot");
 
 template <typename T>
 __global__ void sample_partial_kernel(int64_t n, const T* __restrict__ d, double* __restrict__ S, int64_t* __restrict__ lastpos,
@@ -494,12 +495,12 @@ int sample_indices_iid(rlhip_ctx* c, int64_t n, const T* d, int64_t k, int uniqu
     }
     hipError_t e = hipGetLastError();
     // the one host read: status (and the unique count) ride in the pinned mailbox, the indices go straight to the caller's buffer
-    if (e == hipSuccess) e = hipMemcpyAsync(c->h_mail + 60, hdr, sizeof(SampleHdr), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->h_mail + MAIL_SAMPLE_HDR, hdr, sizeof(SampleHdr), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && out_host && k > 0) e = hipMemcpyAsync(out_host, out, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = rlhip_stream_sync(c);
     if (e != hipSuccess) return RLHIP_ERR_HIP(e);
     SampleHdr h;
-    memcpy(&h, c->h_mail + 60, sizeof(SampleHdr));
+    memcpy(&h, c->h_mail + MAIL_SAMPLE_HDR, sizeof(SampleHdr));
     *status = (int)h.status;
     *count = h.status != 0 ? 0 : (unique ? h.count : k);
     if (next_ctr) ctr_add(ctr, h.status != 0 ? 0 : (uint64_t)((k + 1) / 2), next_ctr);

@@ -455,15 +455,15 @@ int csr_transpose(rlhip_ctx* c, int64_t m, int64_t k, const int64_t* rowptr, con
     if (k >= ((int64_t)1 << 31)) return -2;
     int64_t nnz = 0;
     if (m > 0) {
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 50, rowptr + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_CSR_NNZ, rowptr + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
-        nnz = c->h_mail[50];
+        nnz = c->h_mail[MAIL_CSR_NNZ];
     }
     if (nnz < 0 || nnz >= ((int64_t)1 << 31)) return -2;      // per-column counters are 32-bit
     if (k == 0) { RLHIP_CHECK(hipMemsetAsync(rowptrT, 0, sizeof(int64_t), c->stream)); return nnz == 0 ? 0 : -2; }
     const int64_t nblk = (k + 1023) / 1024;
-    int* d_bad = (int*)(c->d_mail + 51);
-    unsigned long long* d_maxlen = (unsigned long long*)(c->d_mail + 52);
+    int* d_bad = (int*)(c->d_mail + MAIL_CSR_BAD);
+    unsigned long long* d_maxlen = (unsigned long long*)(c->d_mail + MAIL_CSR_MAXLEN);
     ws_scope ws(c);
     int64_t* total = ws.alloc<int64_t>((size_t)k);
     int64_t* bsum = ws.alloc<int64_t>((size_t)nblk + 1);
@@ -474,7 +474,7 @@ int csr_transpose(rlhip_ctx* c, int64_t m, int64_t k, const int64_t* rowptr, con
     do {
         // ---- column totals, row pointers of the transpose, the longest transposed row (one host read for it and the index check)
         if (hipMemsetAsync(total, 0, sizeof(int64_t) * (size_t)k, c->stream) != hipSuccess || hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)k, c->stream) != hipSuccess ||
-            hipMemsetAsync(c->d_mail + 51, 0, 2 * sizeof(int64_t), c->stream) != hipSuccess) { rc = -1; break; }
+            hipMemsetAsync(c->d_mail + MAIL_CSR_BAD, 0, 2 * sizeof(int64_t), c->stream) != hipSuccess) { rc = -1; break; }
         const unsigned gh = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, (nnz + 255) / 256));
         if (nnz > 0) hipLaunchKernelGGL(ct_hist_kernel, dim3(gh), dim3(256), 0, c->stream, nnz, k, colidx, (unsigned long long*)total, d_bad);
         hipLaunchKernelGGL(ct_blocksum_kernel, dim3((unsigned)nblk), dim3(1024), 0, c->stream, k, (const int64_t*)total, bsum, d_maxlen);
@@ -486,10 +486,10 @@ int csr_transpose(rlhip_ctx* c, int64_t m, int64_t k, const int64_t* rowptr, con
             if (hipMemsetAsync(rowid, 0, (size_t)nnz * sizeof(int64_t), c->stream) != hipSuccess) { rc = -1; break; }
         } else
         if (nnz > 0 && m > 0) hipLaunchKernelGGL(ct_rowid_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, m, rowptr, rowid);
-        if (hipMemcpyAsync(c->h_mail + 51, c->d_mail + 51, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess || rlhip_stream_sync(c) != hipSuccess) { rc = -1; break; }
-        if (*(int*)(c->h_mail + 51)) { rc = -2; break; }                                   // a column index outside [0, k)
+        if (hipMemcpyAsync(c->h_mail + MAIL_CSR_BAD, c->d_mail + MAIL_CSR_BAD, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess || rlhip_stream_sync(c) != hipSuccess) { rc = -1; break; }
+        if (*(int*)(c->h_mail + MAIL_CSR_BAD)) { rc = -2; break; }                                   // a column index outside [0, k)
         if (nnz == 0) break;
-        if (c->h_mail[52] <= CT_SORT_MAX) {
+        if (c->h_mail[MAIL_CSR_MAXLEN] <= CT_SORT_MAX) {
             hipLaunchKernelGGL(ct_scatter_key_kernel, dim3(gh), dim3(256), 0, c->stream, nnz, colidx, (const int64_t*)rowptrT, cursor, colidxT);
             hipLaunchKernelGGL(ct_sortfill_kernel<T>, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, k, (const int64_t*)rowptrT, colidxT, (const int64_t*)rowid, vals, valsT);
             if (hipGetLastError() != hipSuccess) rc = -1;

@@ -214,11 +214,11 @@ int gesdd_tall_gram(rlhip_ctx* c, int64_t m, int64_t n, const T* A, int64_t lda,
         if (rc) return rc < 0 ? rc : 1;
         hipLaunchKernelGGL(identity_defect_kernel<T>, dim3(g2), dim3(256), 0, c->stream, nn, G, defect);            // (defect starts at 0: the Jacobi launch cleared the mailbox)
         RLHIP_LAUNCH_CHECK();
-        hipError_t e = hipMemcpyAsync(c->h_mail + 32, mb, 5 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
+        hipError_t e = hipMemcpyAsync(c->h_mail + MAIL_SVD_GRAM, mb, MAIL_SVD_GRAM_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = rlhip_stream_sync(c);
         if (e != hipSuccess) return RLHIP_ERR_HIP(e);
-        const int* jo = (const int*)(c->h_mail + 32);
-        const double dv = *(const double*)(c->h_mail + 36);
+        const int* jo = (const int*)(c->h_mail + MAIL_SVD_GRAM);
+        const double dv = *(const double*)(c->h_mail + MAIL_SVD_GRAM_DEFECT);
         const bool ok = (jo[0] == 1 || jo[0] == 2) && jo[2] == 0 && dv <= 1e-13;
         if (getenv("RLHIP_GESDD_TRACE")) fprintf(stderr, "[gesdd gram] jacobi status %d sweeps %d lost %d defect %.3e -> %s\n", jo[0], jo[1], jo[2], dv, ok ? "taken" : "classic route");
         if (jo[3] == 1) c->path_count[15]++;       // same-XCD hand-over taken by the Jacobi launch (jacobi.hip)
@@ -255,11 +255,11 @@ static int gesdd_tall_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda
     if (rc) return rc;
     if (info) fallback = true;
     if (!fallback) {
-        double* d_ratio = (double*)(c->d_mail + 24);
+        double* d_ratio = (double*)(c->d_mail + MAIL_SVD_RATIO);
         hipLaunchKernelGGL(diag_ratio_kernel<T>, dim3(1), dim3(256), 0, c->stream, (int)n, R1, (int64_t)n, d_ratio);
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 24, d_ratio, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_SVD_RATIO, d_ratio, sizeof(double), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
-        ratio = *(double*)(c->h_mail + 24);
+        ratio = *(double*)(c->h_mail + MAIL_SVD_RATIO);
         const double lim = (sizeof(T) == 8) ? 1e7 : 1e3;
         if (!(ratio < lim)) fallback = true;
     }
@@ -276,11 +276,11 @@ static int gesdd_tall_core(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda
         // triangle that equals the identity to rounding, so it is skipped (one k x k Cholesky + one m x k triangular solve +
         // the R2 R1 product per call).  Threshold 1e-13 (fp64) keeps ||Q^T Q - I||_F below k * 1e-13.
         {
-            double* d_dev = (double*)(c->d_mail + 25);
+            double* d_dev = (double*)(c->d_mail + MAIL_SVD_GRAM_DEV);
             hipLaunchKernelGGL(gram_identity_dev_kernel<T>, dim3(1), dim3(1024), 0, c->stream, (int)n, R2, (int64_t)n, d_dev);
-            RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 25, d_dev, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_SVD_GRAM_DEV, d_dev, sizeof(double), hipMemcpyDeviceToHost, c->stream));
             RLHIP_CHECK(rlhip_stream_sync(c));
-            const double dev = *(double*)(c->h_mail + 25);
+            const double dev = *(double*)(c->h_mail + MAIL_SVD_GRAM_DEV);
             one_pass = (dev <= ((sizeof(T) == 8) ? 1e-13 : 5e-6));
         }
         if (one_pass) {

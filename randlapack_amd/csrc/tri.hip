@@ -14,15 +14,17 @@
 //     U_JJ is packed row-major so that the values a lane needs next are wave-uniform and contiguous; 32-column sub-blocks live in
 //     registers, earlier x values of the same row in an LDS tile.
 #include <cstdlib>
-#include "rlhip_internal.h"
+#include "rlhip_device.h"
 #include <cstdio>
 
 namespace {
 
+using namespace rlhip_dev;   // Mfma16x4, IntC
+
 constexpr int SB = 32;    // sub-block solved by the row-per-lane kernel (SB = 64 halves the passes but its LDS tile allows only
                           // two waves per CU: measured 714 us per pass against 123 us for SB = 32)
 constexpr int RW = 256;   // rows (= threads) per workgroup of that kernel: LDS tile SB x RW + packed triangle SB x SB
-constexpr int DB = 256;   // diagonal block handled by one fused kernel
+constexpr int BW = 256;   // diagonal block: the width handled by one blk-path launch and the block width of the fused kernel
 
 // Ut[l * ldp + c] = U[l, c] for l <= c < nb (row-major, zero below the diagonal), padded with the identity
 // up to ldp (a multiple of SB).  Diagonal entries hold the RECIPROCAL (LAPACK's dtrsm multiplies by
@@ -124,20 +126,14 @@ __global__ void copy_triu_kernel(int64_t n, int unit, const T* __restrict__ U, i
 // Replaces, per 256-block, 8 substitution launches + 8 packs + 7 narrow GEMMs (570 us at m = 32768; 3.85 ms at m = 1e6).
 // The diagonal blocks are applied through their explicit 32 x 32 inverses (as MAGMA / rocBLAS do): the error of a sub-block solve
 // is eps * cond(U_ss) instead of the componentwise bound of substitution.
+
+// the shared MFMA trait plus the one thing these kernels add: an accumulator tile read back as the next product's operand
 template <typename T> struct BlkMma;
-template <> struct BlkMma<double> {
-    typedef double acc_t __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ acc_t mma(double x, double y, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(x, y, c, 0, 0, 0); }
-    static __device__ __forceinline__ int drow(int lane, int r) { return (lane >> 4) + 4 * r; }
-    static constexpr int CS = 4, CL = 1;      // drow(lane, r) = CL * (lane >> 4) + CS * r
+template <> struct BlkMma<double> : Mfma16x4<double> {
     // value T[m = lane & 15][col = c0 + (lane >> 4)] of a 16 x 16 accumulator tile (c0 multiple of 4): already in this lane
     static __device__ __forceinline__ double operand(const acc_t& t, int c0, int) { return t[c0 >> 2]; }
 };
-template <> struct BlkMma<float> {
-    typedef float acc_t __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ acc_t mma(float x, float y, acc_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, c, 0, 0, 0); }
-    static __device__ __forceinline__ int drow(int lane, int r) { return 4 * (lane >> 4) + r; }
-    static constexpr int CS = 1, CL = 4;
+template <> struct BlkMma<float> : Mfma16x4<float> {
     // fp32 accumulators hold columns 4 (lane/16) + r: column c0 + (lane >> 4) sits in lane group c0 / 4, register (lane >> 4)
     static __device__ __forceinline__ float operand(const acc_t& t, int c0, int lane) {
         const int src = (lane & 15) + 16 * (c0 >> 2);
@@ -146,8 +142,6 @@ template <> struct BlkMma<float> {
         return r == 0 ? v0 : r == 1 ? v1 : r == 2 ? v2 : v3;
     }
 };
-
-constexpr int BW = 256;   // block width of the blk path
 
 // blockIdx.y = 256-column block of the n x n triangle A.  bad[blk] is raised when a diagonal 32 x 32 block is too ill conditioned
 // (||U_ss||_F ||U_ss^-1||_F > limit, or not finite) for its explicit inverse to be used: that block then takes the substitution path.
@@ -351,8 +345,6 @@ __global__ __launch_bounds__(256) void trsm_neg_pack_kernel(int64_t n, int64_t n
 #ifndef RLHIP_TF_DRAIN
 #define RLHIP_TF_DRAIN 0
 #endif
-template <int N> struct IntC { static constexpr int value = N; };
-
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // NW = wavefronts per workgroup (16 rows each), HPR = rows of U per LDS stage (32 = two 16-row half panels), two stages
@@ -426,7 +418,6 @@ __global__ __launch_bounds__(NW * 64, 2) void trsm_fused_kernel(int64_t m, int64
 #pragma unroll
         for (int qq = 0; qq < NQ; ++qq) asm volatile("" : "+v"(v[qq]));
     };
-    // raw right-hand-side element of this lane in tile (jj, r) of the 256-block starting at column cb0
     // OOP: the source column of every column of a 256-block is staged in LDS once per block (identity without a pivot vector), so a tile
     // element is ONE lane-indexed LDS read + ONE global load.  (With four scalar loads of the pivot entries and a per-lane choice per element
     // hipcc built ~390 branches with an s_waitcnt vmcnt(0) in most of them: the eight loads of a retired tile went out one HBM round trip at a time.)
@@ -517,7 +508,6 @@ __global__ __launch_bounds__(NW * 64, 2) void trsm_fused_kernel(int64_t m, int64
             for (int e = 0; e < G; ++e) {
                 const int f = g * G + e;
                 if (f < TOT) {
-                    constexpr int dummy = 0; (void)dummy;
                     const int j = JLO + 2 * (f % NP);
                     acc[j] = M::mma(fa[e][0], y[f / NP], acc[j]);
                     acc[j + 1] = M::mma(fa[e][1], y[f / NP], acc[j + 1]);
@@ -558,8 +548,6 @@ __global__ __launch_bounds__(NW * 64, 2) void trsm_fused_kernel(int64_t m, int64
 #pragma unroll
     for (int q = 0; q < NQ; ++q) { xc[q] = T(0); xn[q] = T(0); }
     if (J0 > K0blk) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) xc[q] = T(0);
         xissue(B + (int64_t)K0blk * 256 * ldb, xc);
     }
     for (int J = J0; J < J1; ++J) {
@@ -721,21 +709,69 @@ inline bool tf_xasm(const rlhip_ctx* c) {      // RLHIP_OPT_TRSM_XASM: -1 = what
     const int64_t o = c->opt[RLHIP_OPT_TRSM_XASM];
     return o < 0 ? (RLHIP_TF_XASM_DEFAULT != 0) : (o != 0);
 }
+// the fused kernel keeps a lane's offset into an m-row matrix of leading dimension ld (loff, loffsrc, xoffb) in 32 bits
+inline bool tf_offsets_fit(int64_t ld, int64_t m) { return (4 * ld + m) < ((int64_t)1 << 28); }
 
-template <typename T, int NW, int OOP, int HPR>
-int tf_launch_nw(rlhip_ctx* c, int64_t m, int64_t n, int64_t n_pad, T alpha, const T* Uneg, const T* Dinv, T* B, int64_t ldb, int J0, int J1, int K0blk, T* dump,
-                 const T* Bsrc, int64_t ldsrc, const int64_t* perm, int64_t pbase, const int* gate, int ngate) {
-    const dim3 grid((unsigned)((m + 16 * NW - 1) / (16 * NW)));
-    constexpr int lds = fused_lds_bytes<T, HPR>();
-    if (tf_xasm(c)) {
-        RLHIP_FUNC_LDS(c, (trsm_fused_kernel<T, NW, HPR, OOP, true>), lds);
-        hipLaunchKernelGGL((trsm_fused_kernel<T, NW, HPR, OOP, true>), grid, dim3(64 * NW), lds, c->stream, m, n, n_pad, alpha, Uneg, Dinv, B, ldb, J0, J1, K0blk,
-                           dump, Bsrc, ldsrc, perm, pbase, gate, ngate);
-    } else {
-        RLHIP_FUNC_LDS(c, (trsm_fused_kernel<T, NW, HPR, OOP, false>), lds);
-        hipLaunchKernelGGL((trsm_fused_kernel<T, NW, HPR, OOP, false>), grid, dim3(64 * NW), lds, c->stream, m, n, n_pad, alpha, Uneg, Dinv, B, ldb, J0, J1, K0blk,
-                           dump, Bsrc, ldsrc, perm, pbase, gate, ngate);
-    }
+constexpr int TF_HPR = 32;                   // rows of U per LDS stage of the fused kernel (its only instantiation)
+constexpr double TF_KAPPA2_LIMIT = 1.0e6;    // conditioning guard of the pack kernel: kappa_F^2 of a 32 x 32 diagonal block (kappa_F <= 1e3)
+// Verdict words of one solve (device ints, non-zero = refused): the conditioning guard's word of block b at index b, the pivot check's word
+// behind them.  A solve that reads them back copies TF_VERDICT_WORDS of them to h_mail + MAIL_TRSM_VERDICT.
+constexpr int TF_MAX_BLOCKS = 32;                         // 256-blocks a solve may have: one guard word each
+constexpr int TF_PIVOT_WORD = TF_MAX_BLOCKS;              // raised by perm_check_kernel
+constexpr int TF_VERDICT_WORDS = TF_PIVOT_WORD + 1;       // cleared, copied back, and what the gated launch tests
+constexpr int TF_VERDICT_ALLOC = 40;                      // allocated (cholqrq clears and copies them all: [0] potrf info, [1 .. nblk] guard words)
+static_assert(TF_VERDICT_WORDS <= TF_VERDICT_ALLOC && TF_VERDICT_WORDS * sizeof(int) <= MAIL_TRSM_VERDICT_WORDS * sizeof(int64_t) &&
+              TF_VERDICT_ALLOC * sizeof(int) <= MAIL_CHOLQRQ_WORDS * sizeof(int64_t), "the verdict words fit their mailbox ranges");
+
+// ---- the three enqueues every fused solve is set up from (each returns the launch's status)
+// Upk_all / Dinv_all of all nblk 256-blocks of the n x n triangle; bad[b] raised where block b fails the conditioning guard
+template <typename T>
+hipError_t tf_enqueue_blk_pack(rlhip_ctx* c, int64_t n, int64_t nblk, int diag, const T* A, int64_t lda, T* Upk_all, T* Dinv_all, int* bad) {
+    hipLaunchKernelGGL(trsm_blk_pack_kernel<T>, dim3(BW / 32 + 24, (unsigned)nblk), dim3(256), 0, c->stream, n, diag, A, lda, Upk_all, Dinv_all, bad,
+                       TF_KAPPA2_LIMIT);
+    return hipGetLastError();
+}
+// Uneg (n_pad x n_pad, n_pad a multiple of 32) of the n x n triangle
+template <typename T>
+hipError_t tf_enqueue_neg_pack(rlhip_ctx* c, int64_t n, int64_t n_pad, const T* A, int64_t lda, T* Uneg) {
+    hipLaunchKernelGGL(trsm_neg_pack_kernel<T>, dim3((unsigned)(n_pad / 32), (unsigned)(n_pad / 32)), dim3(256), 0, c->stream, n, n_pad, A, lda, Uneg);
+    return hipGetLastError();
+}
+// *bad = 1 unless the 1-based perm[0 .. n) is injective into 1 .. nsrc (seen: nsrc bits; clear_bad: *bad is not yet zero)
+inline hipError_t tf_enqueue_perm_check(rlhip_ctx* c, int64_t n, const int64_t* perm, int64_t nsrc, unsigned* seen, int* bad, bool clear_bad) {
+    hipError_t e = hipMemsetAsync(seen, 0, ((size_t)nsrc + 31) / 32 * sizeof(unsigned), c->stream);
+    if (e == hipSuccess && clear_bad) e = hipMemsetAsync(bad, 0, sizeof(int), c->stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(perm_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, perm, (int64_t)1, seen, bad, nsrc);
+    return hipGetLastError();
+}
+
+// trsm_fused_kernel's arguments.  In-place callers leave the source, pivot and gate fields at their defaults.
+template <typename T>
+struct TfArgs {
+    int64_t m, n, n_pad;
+    T alpha;
+    const T* Uneg;
+    const T* Dinv;
+    T* B;
+    int64_t ldb;
+    int J0, J1, K0blk;
+    T* dump;
+    const T* Bsrc = nullptr;
+    int64_t ldsrc = 0;
+    const int64_t* perm = nullptr;
+    int64_t pbase = 0;
+    const int* gate = nullptr;
+    int ngate = 0;
+};
+
+// one function per kernel instantiation: RLHIP_FUNC_LDS keeps its per-device flags at the call site
+template <typename T, int NW, int OOP, bool XASM>
+int tf_launch_one(rlhip_ctx* c, const TfArgs<T>& a) {
+    constexpr int lds = fused_lds_bytes<T, TF_HPR>();
+    RLHIP_FUNC_LDS(c, (trsm_fused_kernel<T, NW, TF_HPR, OOP, XASM>), lds);
+    hipLaunchKernelGGL((trsm_fused_kernel<T, NW, TF_HPR, OOP, XASM>), dim3((unsigned)((a.m + 16 * NW - 1) / (16 * NW))), dim3(64 * NW), lds, c->stream, a.m, a.n,
+                       a.n_pad, a.alpha, a.Uneg, a.Dinv, a.B, a.ldb, a.J0, a.J1, a.K0blk, a.dump, a.Bsrc, a.ldsrc, a.perm, a.pbase, a.gate, a.ngate);
     RLHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -745,22 +781,15 @@ int tf_launch_nw(rlhip_ctx* c, int64_t m, int64_t n, int64_t n_pad, T alpha, con
 // rows it does not have: 49152 rows = 384 workgroups = two rounds = the price of 65536 rows.  The fp32 in-place solve (BQRRP's panels, whose
 // row count shrinks by b per iteration) therefore has a 192-row instantiation (twelve wavefronts, three per SIMD: its 148 VGPRs fit) taken
 // when its rounds cost less: 49152 rows = 256 workgroups = ONE round of 12 units instead of two of 8.
-template <typename T, int OOP, int HPR>
-int tf_launch_hpr(rlhip_ctx* c, int64_t m, int64_t n, int64_t n_pad, T alpha, const T* Uneg, const T* Dinv, T* B, int64_t ldb, int J0, int J1, int K0blk, T* dump,
-                  const T* Bsrc, int64_t ldsrc, const int64_t* perm, int64_t pbase, const int* gate, int ngate) {
+template <typename T, int OOP>
+int tf_launch(rlhip_ctx* c, const TfArgs<T>& a) {
+    const bool xasm = tf_xasm(c);
     if constexpr (sizeof(T) == 4 && OOP == 0) {
         const int64_t ncu = c->num_cu > 0 ? c->num_cu : 256;
-        auto cost = [&](int64_t nw) { const int64_t wg = (m + 16 * nw - 1) / (16 * nw); return ((wg + ncu - 1) / ncu) * nw; };
-        if (cost(12) < cost(8))
-            return tf_launch_nw<T, 12, OOP, HPR>(c, m, n, n_pad, alpha, Uneg, Dinv, B, ldb, J0, J1, K0blk, dump, Bsrc, ldsrc, perm, pbase, gate, ngate);
+        auto cost = [&](int64_t nw) { const int64_t wg = (a.m + 16 * nw - 1) / (16 * nw); return ((wg + ncu - 1) / ncu) * nw; };
+        if (cost(12) < cost(8)) return xasm ? tf_launch_one<T, 12, OOP, true>(c, a) : tf_launch_one<T, 12, OOP, false>(c, a);
     }
-    return tf_launch_nw<T, 8, OOP, HPR>(c, m, n, n_pad, alpha, Uneg, Dinv, B, ldb, J0, J1, K0blk, dump, Bsrc, ldsrc, perm, pbase, gate, ngate);
-}
-
-template <typename T, int OOP>
-int tf_launch(rlhip_ctx* c, int64_t m, int64_t n, int64_t n_pad, T alpha, const T* Uneg, const T* Dinv, T* B, int64_t ldb, int J0, int J1, int K0blk, T* dump,
-              const T* Bsrc, int64_t ldsrc, const int64_t* perm, int64_t pbase, const int* gate, int ngate) {
-    return tf_launch_hpr<T, OOP, 32>(c, m, n, n_pad, alpha, Uneg, Dinv, B, ldb, J0, J1, K0blk, dump, Bsrc, ldsrc, perm, pbase, gate, ngate);
+    return xasm ? tf_launch_one<T, 8, OOP, true>(c, a) : tf_launch_one<T, 8, OOP, false>(c, a);
 }
 
 }  // namespace
@@ -782,21 +811,19 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
     // only where those are well conditioned (kappa_F <= 1e3: error eps * kappa stays at 1e-13); graded triangles -- the R factor of an
     // ill-conditioned sketch in CQRRPT's preconditioning step -- keep the componentwise-stable substitution kernels.
     const int64_t nblk = (n + BW - 1) / BW;
-    const bool try_blk = m >= 16 && n >= 128 && nblk <= 32;   // narrow solves (orhr_col, potrf panels: n = 32) are one pack + one substitution launch already
+    const bool try_blk = m >= 16 && n >= 128 && nblk <= TF_MAX_BLOCKS;   // narrow solves (orhr_col, potrf panels: n = 32) are one pack + one substitution launch already
     T* Upk_all = try_blk ? ws.alloc<T>((size_t)nblk * BW * BW) : nullptr;
     T* Dinv_all = try_blk ? ws.alloc<T>((size_t)nblk * (BW / 32) * 1024) : nullptr;
-    int* bad_dev = try_blk ? ws.alloc<int>(32) : nullptr;
-    int bad_host[32];
-    for (int i = 0; i < 32; ++i) bad_host[i] = 1;
+    int* bad_dev = try_blk ? ws.alloc<int>(TF_MAX_BLOCKS) : nullptr;
+    int bad_host[TF_MAX_BLOCKS];
+    for (int i = 0; i < TF_MAX_BLOCKS; ++i) bad_host[i] = 1;
     if (try_blk) {
         if (!Upk_all || !Dinv_all || !bad_dev) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
-        RLHIP_CHECK(hipMemsetAsync(bad_dev, 0, 32 * sizeof(int), c->stream));
-        hipLaunchKernelGGL(trsm_blk_pack_kernel<T>, dim3(BW / 32 + 24, (unsigned)nblk), dim3(256), 0, c->stream, n, diag, A, lda, Upk_all, Dinv_all, bad_dev,
-                           1.0e6);
-        RLHIP_LAUNCH_CHECK();
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 16, bad_dev, 32 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(hipMemsetAsync(bad_dev, 0, TF_MAX_BLOCKS * sizeof(int), c->stream));
+        RLHIP_CHECK(tf_enqueue_blk_pack<T>(c, n, nblk, diag, A, lda, Upk_all, Dinv_all, bad_dev));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_TRSM_VERDICT, bad_dev, TF_MAX_BLOCKS * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         RLHIP_CHECK(rlhip_stream_sync(c));
-        for (int i = 0; i < 32; ++i) bad_host[i] = ((int*)(c->h_mail + 16))[i];
+        for (int i = 0; i < TF_MAX_BLOCKS; ++i) bad_host[i] = ((const int*)(c->h_mail + MAIL_TRSM_VERDICT))[i];
     }
     // Two-level blocking.  Outer 256-column blocks: the contribution of everything to the left is ONE wide MFMA
     // GEMM (N = 256 -> stream-K path at scale).  Inside a block, 32-column sub-blocks: a narrow MFMA GEMM (N = 32,
@@ -813,7 +840,7 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
     // substitution over every wave of every CU.)
     // fused path: ONE launch solves a whole run of well-conditioned 256-blocks (trsm_fused_kernel); blocks whose diagonal sub-blocks are
     // ill conditioned still take the substitution kernels below, with a GEMM bringing in everything to their left.
-    const bool use_fused = try_blk && m >= TF_MIN_ROWS && n >= BW && (4 * ldb + m) < ((int64_t)1 << 28);   // (32-bit lane offsets in the kernel)
+    const bool use_fused = try_blk && m >= TF_MIN_ROWS && n >= BW && tf_offsets_fit(ldb, m);
     const int64_t n_pad = nblk * BW;
     T* Uneg = nullptr;
     T* fdump = nullptr;
@@ -823,14 +850,13 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
         if (any_good) {
             Uneg = ws.alloc<T>((size_t)n_pad * n_pad);
             if (!Uneg) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
-            hipLaunchKernelGGL(trsm_neg_pack_kernel<T>, dim3((unsigned)(n_pad / 32), (unsigned)(n_pad / 32)), dim3(256), 0, c->stream, n, n_pad, A, lda, Uneg);
-            RLHIP_LAUNCH_CHECK();
+            RLHIP_CHECK(tf_enqueue_neg_pack<T>(c, n, n_pad, A, lda, Uneg));
             fdump = ws.alloc<T>(512 + 64);
             if (!fdump) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
         }
     }
-    for (int64_t j0 = 0; j0 < n; j0 += DB) {
-        const int nb = (int)((n - j0 < DB) ? (n - j0) : DB);
+    for (int64_t j0 = 0; j0 < n; j0 += BW) {
+        const int nb = (int)((n - j0 < BW) ? (n - j0) : BW);
         T a = alpha;
         if (Uneg && !bad_host[j0 / BW] && j0 + BW <= n) {
             // run of good blocks [Jb, Je): everything left of Jb comes in through one GEMM, the rest is fused
@@ -844,8 +870,7 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
                 a = T(1);
             }
             {
-                const int lrc = tf_launch<T, 0>(c, m, n, n_pad, a, Uneg, Dinv_all, B, ldb, Jb, Je, Jb, fdump, (const T*)nullptr, (int64_t)0, (const int64_t*)nullptr, (int64_t)0,
-                                                    (const int*)nullptr, 0);
+                const int lrc = tf_launch<T, 0>(c, TfArgs<T>{m, n, n_pad, a, Uneg, Dinv_all, B, ldb, Jb, Je, Jb, fdump});
                 if (lrc) return lrc;
             }
 #ifdef RLHIP_TF_PROF
@@ -859,7 +884,7 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
             }
 #endif
             c->path_count[2]++;
-            j0 = (int64_t)(Je - 1) * DB;     // the loop increment moves on to block Je
+            j0 = (int64_t)(Je - 1) * BW;     // the loop increment moves on to block Je
             continue;
         }
         if (j0 > 0) {
@@ -868,30 +893,16 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
             a = T(1);
         }
         if (try_blk && !bad_host[j0 / BW]) {
-            // (narrower pieces, 128 / 64 columns, let the fused kernel solve pieces of the block with a GEMM in between -- more of the
-            // flops at GEMM speed).  Measured at C3 (m = 2^20, n = 1024): CQRRPT 105.5 ms whole blocks, 107.8 ms halves, 117.2 ms quarters:
+            // One launch for the whole block.  (Narrower pieces, 128 / 64 columns, let the kernel solve pieces of the block with a GEMM in
+            // between -- more of the flops at GEMM speed.)  Measured at C3 (m = 2^20, n = 1024): CQRRPT 105.5 ms whole blocks, 107.8 ms halves, 117.2 ms quarters:
             // the extra passes over B cost more than the fused kernel's lower rate, so whole blocks stay the default.
-            constexpr int hb_env = BW;
             const T* Upk_b = Upk_all + (j0 / BW) * (int64_t)BW * BW;
             const T* Dinv_b = Dinv_all + (j0 / BW) * (int64_t)(BW / 32) * 1024;
-            for (int h0 = 0; h0 < nb; h0 += hb_env) {
-                const int hb = (nb - h0 < hb_env) ? (nb - h0) : hb_env;
-                T ah = a;
-                if (h0 > 0) {
-                    const int64_t jc = j0 + h0;
-                    // columns [j0, jc) of this block (the columns left of j0 went in above, with alpha)
-                    int rc = gemm_impl<T>(c, 0, 0, m, hb, h0, T(-1), B + j0 * ldb, ldb, A + j0 + jc * lda, lda, a, B + jc * ldb, ldb, 0);
-                    if (rc) return rc;
-                    ah = T(1);
-                }
-                if (m >= 65536)       // enough rows to fill the chip with 128-row workgroups: two row tiles per wave halve the U-fragment traffic (four: slower, 108.6 vs 105.5 ms at C3)
-                    hipLaunchKernelGGL((trsm_blk_kernel<T, 2>), dim3((unsigned)((m + 127) / 128)), dim3(256), 0, c->stream, m, h0 + hb, ah, Upk_b, Dinv_b,
-                                       B + j0 * ldb, ldb, h0 / 32, h0);
-                else
-                    hipLaunchKernelGGL((trsm_blk_kernel<T, 1>), dim3((unsigned)((m + 63) / 64)), dim3(256), 0, c->stream, m, h0 + hb, ah, Upk_b, Dinv_b,
-                                       B + j0 * ldb, ldb, h0 / 32, h0);
-                RLHIP_LAUNCH_CHECK();
-            }
+            if (m >= 65536)       // enough rows to fill the chip with 128-row workgroups: two row tiles per wave halve the U-fragment traffic (four: slower, 108.6 vs 105.5 ms at C3)
+                hipLaunchKernelGGL((trsm_blk_kernel<T, 2>), dim3((unsigned)((m + 127) / 128)), dim3(256), 0, c->stream, m, nb, a, Upk_b, Dinv_b, B + j0 * ldb, ldb, 0, 0);
+            else
+                hipLaunchKernelGGL((trsm_blk_kernel<T, 1>), dim3((unsigned)((m + 63) / 64)), dim3(256), 0, c->stream, m, nb, a, Upk_b, Dinv_b, B + j0 * ldb, ldb, 0, 0);
+            RLHIP_LAUNCH_CHECK();
             continue;
         }
         for (int s0 = 0; s0 < nb; s0 += SB) {
@@ -915,6 +926,54 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
     return 0;
 }
 
+// ONE fused attempt at columns [col0, col1) of the out-of-place solve  B = alpha * (Bsrc * P) * inv(A)  (the two public forms below say what the
+// arguments mean).  Returns 0 (done), 1 (not taken: sizes or conditioning outside the fused kernel's domain -- nothing written) or an error
+// (< 0; -7: perm is not injective into 1 .. nsrc).  *perm_checked: the pivot vector has been validated (only ever set when one was given).
+// `may_ident`: without a pivot vector the identity-column twin of the kernel (OOP = 2) may be taken when the source's lane offsets fit too.
+// HIP errors leave through RLHIP_CHECK: the call returns RLHIP_ERR_HIP(e) at once and the scope gives the scratch back.
+template <typename T>
+static int trsm_oop_fused(rlhip_ctx* c, int diag, int64_t m, int64_t nsrc, T alpha, const T* A, int64_t lda, const T* Bsrc, int64_t ldsrc,
+                          const int64_t* perm_dev, T* B, int64_t ldb, int64_t col0, int64_t col1, bool may_ident, bool* perm_checked) {
+    const int64_t n = col1, nblk = (n + BW - 1) / BW;
+    if (m < TF_MIN_ROWS || n < BW || n % BW != 0 || nblk > TF_MAX_BLOCKS || !tf_offsets_fit(ldb, m)) return 1;
+    ws_scope ws(c);
+    T* Upk_all = ws.alloc<T>((size_t)nblk * BW * BW);
+    T* Dinv_all = ws.alloc<T>((size_t)nblk * (BW / 32) * 1024);
+    int* bad_dev = ws.alloc<int>(TF_VERDICT_ALLOC);
+    unsigned* seen = ws.alloc<unsigned>((size_t)nsrc / 32 + 2);
+    T* Uneg = ws.alloc<T>((size_t)n * n);
+    T* fdump = ws.alloc<T>(512);
+    if (!Upk_all || !Dinv_all || !bad_dev || !seen || !Uneg || !fdump) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
+    RLHIP_CHECK(hipMemsetAsync(bad_dev, 0, TF_VERDICT_WORDS * sizeof(int), c->stream));
+    RLHIP_CHECK(tf_enqueue_blk_pack<T>(c, n, nblk, diag, A, lda, Upk_all, Dinv_all, bad_dev));
+    if (perm_dev) {     // the pivot vector is validated on the device; its verdict rides on the guard's read-back
+        RLHIP_CHECK(tf_enqueue_perm_check(c, n, perm_dev, nsrc, seen, bad_dev + TF_PIVOT_WORD, false));
+        *perm_checked = true;
+    }
+    // The verdict (the conditioning guard of every block, the pivot check) travels to the host while the device runs on: the packed
+    // triangle and the fused solve are enqueued right behind the read-back, GATED on the same device words (a launch that finds one of
+    // them set does nothing), and the host waits for the read-back only -- no idle device during the round trip.
+    const int* verdict = (const int*)(c->h_mail + MAIL_TRSM_VERDICT);
+    RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_TRSM_VERDICT, bad_dev, TF_VERDICT_WORDS * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RLHIP_CHECK(hipEventRecord(c->ev_flag, c->stream));
+    RLHIP_CHECK(tf_enqueue_neg_pack<T>(c, n, n, A, lda, Uneg));
+    {
+        TfArgs<T> a{m, n, n, alpha, Uneg, Dinv_all, B, ldb, (int)(col0 / BW), (int)nblk, 0, fdump};
+        a.Bsrc = Bsrc; a.ldsrc = ldsrc;
+        a.perm = perm_dev; a.pbase = 1;
+        a.gate = bad_dev; a.ngate = TF_VERDICT_WORDS;
+        const bool ident = may_ident && !perm_dev && tf_offsets_fit(ldsrc, m);
+        const int lrc = ident ? tf_launch<T, 2>(c, a) : tf_launch<T, 1>(c, a);
+        if (lrc) return lrc;
+    }
+    RLHIP_CHECK(hipEventSynchronize(c->ev_flag));
+    if (perm_dev && verdict[TF_PIVOT_WORD] != 0) return -7;     // not a permutation (as col_swap reports it): before the block verdicts
+    for (int64_t b = 0; b < nblk; ++b)
+        if (verdict[b] != 0) return 1;                          // the gated launch did nothing
+    c->path_count[4]++;
+    return 0;
+}
+
 // Out-of-place solve with the column pivoting folded in:  B = alpha * (Bsrc * P) * inv(A),  column c of Bsrc * P = column perm[c] - 1
 // of Bsrc (perm: LAPACK-style 1-based pivot vector on the device, or nullptr for P = I).  CQRRPT's "permute A, then precondition it"
 // (rl_cqrrpt.hh:288-300) is one pass over A this way instead of two, and its second solve writes Q straight back into A.
@@ -930,65 +989,18 @@ int trsm_right_upper_oop(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, 
     if (ldb < (m > 1 ? m : 1)) return -15;
     if (m == 0 || n == 0) return 0;
     if ((const T*)B == Bsrc) { if (perm_dev) return -14; return trsm_right_upper<T>(c, diag, m, n, alpha, A, lda, B, ldb); }
-    const int64_t nblk = (n + BW - 1) / BW;
-    bool fused = m >= TF_MIN_ROWS && n >= BW && n % BW == 0 && nblk <= 32 && (4 * ldb + m) < ((int64_t)1 << 28);
     bool perm_checked = false;
-    if (fused) {
-        ws_scope ws(c);
-        T* Upk_all = ws.alloc<T>((size_t)nblk * BW * BW);
-        T* Dinv_all = ws.alloc<T>((size_t)nblk * (BW / 32) * 1024);
-        int* bad_dev = ws.alloc<int>(40);
-        unsigned* seen = ws.alloc<unsigned>((size_t)n / 32 + 2);
-        T* Uneg = ws.alloc<T>((size_t)n * n);
-        T* fdump = ws.alloc<T>(512);
-        if (!Upk_all || !Dinv_all || !bad_dev || !seen || !Uneg || !fdump) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
-        RLHIP_CHECK(hipMemsetAsync(bad_dev, 0, 33 * sizeof(int), c->stream));
-        hipLaunchKernelGGL(trsm_blk_pack_kernel<T>, dim3(BW / 32 + 24, (unsigned)nblk), dim3(256), 0, c->stream, n, diag, A, lda, Upk_all, Dinv_all, bad_dev,
-                           1.0e6);
-        RLHIP_LAUNCH_CHECK();
-        if (perm_dev) {     // the pivot vector is validated on the device; its verdict rides on the guard's read-back (slot 32)
-            RLHIP_CHECK(hipMemsetAsync(seen, 0, ((size_t)n + 31) / 32 * sizeof(unsigned), c->stream));
-            hipLaunchKernelGGL(perm_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, perm_dev, (int64_t)1, seen, bad_dev + 32, n);
-            RLHIP_LAUNCH_CHECK();
-            perm_checked = true;
-        }
-        // The verdict (33 words: the conditioning guard of every block, the pivot check) travels to the host while the device runs on: the
-        // packed triangle and the fused solve are enqueued right behind the read-back, GATED on the same device words (a launch that finds
-        // one of them set does nothing), and the host waits for the read-back only -- no idle device during the round trip.
-        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + 16, bad_dev, 33 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        RLHIP_CHECK(hipEventRecord(c->ev_flag, c->stream));
-        hipLaunchKernelGGL(trsm_neg_pack_kernel<T>, dim3((unsigned)(n / 32), (unsigned)(n / 32)), dim3(256), 0, c->stream, n, n, A, lda, Uneg);
-        RLHIP_LAUNCH_CHECK();
-        {
-            // (no pivot vector: the identity-column twin of the kernel, when the source's lane offsets fit 32 bits too)
-            const bool ident = !perm_dev && (4 * ldsrc + m) < ((int64_t)1 << 28);
-            const int lrc = ident ? tf_launch<T, 2>(c, m, n, n, alpha, Uneg, Dinv_all, B, ldb, 0, (int)nblk, 0, fdump, Bsrc, ldsrc, perm_dev, (int64_t)1, (const int*)bad_dev, 33)
-                                  : tf_launch<T, 1>(c, m, n, n, alpha, Uneg, Dinv_all, B, ldb, 0, (int)nblk, 0, fdump, Bsrc, ldsrc, perm_dev, (int64_t)1, (const int*)bad_dev, 33);
-            if (lrc) return lrc;
-        }
-        RLHIP_CHECK(hipEventSynchronize(c->ev_flag));
-        if (perm_checked && ((int*)(c->h_mail + 16))[32] != 0) return -7;     // jpvt is not a permutation of 1..n (as col_swap reports it)
-        for (int64_t b = 0; b < nblk; ++b) fused = fused && ((int*)(c->h_mail + 16))[b] == 0;
-        if (fused) {
-            c->path_count[4]++;
-            return 0;
-        }
-    }
+    const int frc = trsm_oop_fused<T>(c, diag, m, n, alpha, A, lda, Bsrc, ldsrc, perm_dev, B, ldb, 0, n, true, &perm_checked);
+    if (frc <= 0) return frc;
     if (perm_dev && !perm_checked) {     // gather-copy route: validate before anything is written
         ws_scope ws(c);
         unsigned* seen = ws.alloc<unsigned>((size_t)n / 32 + 2);
         int* bad = ws.alloc<int>(8);
         if (!seen || !bad) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
-        hipError_t pe = hipMemsetAsync(seen, 0, ((size_t)n + 31) / 32 * sizeof(unsigned), c->stream);
-        if (pe == hipSuccess) pe = hipMemsetAsync(bad, 0, sizeof(int), c->stream);
-        if (pe == hipSuccess) {
-            hipLaunchKernelGGL(perm_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, perm_dev, (int64_t)1, seen, bad, n);
-            pe = hipGetLastError();
-        }
-        if (pe == hipSuccess) pe = hipMemcpyAsync(c->h_mail + 16, bad, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (pe == hipSuccess) pe = rlhip_stream_sync(c);
-        if (pe != hipSuccess) return RLHIP_ERR_HIP(pe);
-        if (*(int*)(c->h_mail + 16) != 0) return -7;
+        RLHIP_CHECK(tf_enqueue_perm_check(c, n, perm_dev, n, seen, bad, true));
+        RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_TRSM_VERDICT, bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        RLHIP_CHECK(rlhip_stream_sync(c));
+        if (*(const int*)(c->h_mail + MAIL_TRSM_VERDICT) != 0) return -7;
     }
     {
         unsigned gx = (unsigned)((m + 256 * 8 - 1) / (256 * 8));
@@ -1018,47 +1030,8 @@ int trsm_right_upper_oop_range(rlhip_ctx* c, int diag, int64_t m, int64_t nsrc, 
     if (ldb < (m > 1 ? m : 1)) return -15;
     if (m == 0) return 0;
     if ((const T*)B == Bsrc) return -14;
-    const int64_t n = col1, nblk = n / BW;
-    if (m < TF_MIN_ROWS || nblk > 32 || (4 * ldb + m) >= ((int64_t)1 << 28)) return 1;
-    ws_scope ws(c);
-    T* Upk_all = ws.alloc<T>((size_t)nblk * BW * BW);
-    T* Dinv_all = ws.alloc<T>((size_t)nblk * (BW / 32) * 1024);
-    int* bad_dev = ws.alloc<int>(40);
-    unsigned* seen = ws.alloc<unsigned>((size_t)nsrc / 32 + 2);
-    T* Uneg = ws.alloc<T>((size_t)n * n);
-    T* fdump = ws.alloc<T>(512);
-    if (!Upk_all || !Dinv_all || !bad_dev || !seen || !Uneg || !fdump) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
-    hipError_t he = hipMemsetAsync(bad_dev, 0, 33 * sizeof(int), c->stream);
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(trsm_blk_pack_kernel<T>, dim3(BW / 32 + 24, (unsigned)nblk), dim3(256), 0, c->stream, n, diag, A, lda, Upk_all, Dinv_all, bad_dev, 1.0e6);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess && perm_dev) {
-        he = hipMemsetAsync(seen, 0, ((size_t)nsrc + 31) / 32 * sizeof(unsigned), c->stream);
-        if (he == hipSuccess) {
-            hipLaunchKernelGGL(perm_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, perm_dev, (int64_t)1, seen, bad_dev + 32, nsrc);
-            he = hipGetLastError();
-        }
-    }
-    // (the verdict is read back while the device runs on: the solve is enqueued behind the read-back and gated on the same words -- see the
-    //  whole-matrix form above)
-    if (he == hipSuccess) he = hipMemcpyAsync(c->h_mail + 16, bad_dev, 33 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    if (he == hipSuccess) he = hipEventRecord(c->ev_flag, c->stream);
-    if (he != hipSuccess) return RLHIP_ERR_HIP(he);
-    hipLaunchKernelGGL(trsm_neg_pack_kernel<T>, dim3((unsigned)(n / 32), (unsigned)(n / 32)), dim3(256), 0, c->stream, n, n, A, lda, Uneg);
-    he = hipGetLastError();
-    int lrc = (he == hipSuccess) ? 0 : RLHIP_ERR_HIP(he);
-    if (!lrc) lrc = tf_launch<T, 1>(c, m, n, n, alpha, Uneg, Dinv_all, B, ldb, (int)(col0 / BW), (int)nblk, 0, fdump, Bsrc, ldsrc, perm_dev, (int64_t)1, (const int*)bad_dev, 33);
-    he = hipEventSynchronize(c->ev_flag);
-    if (!lrc && he != hipSuccess) lrc = RLHIP_ERR_HIP(he);
-    if (!lrc && perm_dev && ((int*)(c->h_mail + 16))[32] != 0) lrc = -7;
-    if (!lrc) {
-        bool good = true;
-        for (int64_t bb = 0; bb < nblk; ++bb) good = good && ((int*)(c->h_mail + 16))[bb] == 0;
-        if (!good) lrc = 1;                       // the gated launch did nothing
-    }
-    if (!lrc) c->path_count[4]++;
-    return lrc;
+    bool perm_checked = false;
+    return trsm_oop_fused<T>(c, diag, m, nsrc, alpha, A, lda, Bsrc, ldsrc, perm_dev, B, ldb, col0, col1, false, &perm_checked);
 }
 
 template <typename T>
@@ -1117,14 +1090,14 @@ int cholqrq(rlhip_ctx* c, int64_t m, int64_t k, T* A, int64_t lda, T* R, int red
     // collectives with the same counts (shards that straddle the row threshold used to split into an all-reduce of k*k + 1 words here
     // and one of k*k words in the caller's fallback).  What is rank-local -- too few rows for the fused solve, the 32-bit lane offsets, no room
     // for its scratch -- only selects the SOLVE kernel behind the common Gram / all-reduce / Cholesky sequence.
-    if (c->opt[RLHIP_OPT_CHOLQRQ_ONE_STREAM] == 0 || k < BW || k % BW != 0 || k > 448 || nblk > 31 || lda < (m > 1 ? m : 1)) return 1;
-    bool local_ok = m >= TF_MIN_ROWS && (4 * lda + m) < ((int64_t)1 << 28);
+    if (c->opt[RLHIP_OPT_CHOLQRQ_ONE_STREAM] == 0 || k < BW || k % BW != 0 || k > 448 || nblk > TF_MAX_BLOCKS - 1 || lda < (m > 1 ? m : 1)) return 1;
+    bool local_ok = m >= TF_MIN_ROWS && tf_offsets_fit(lda, m);
     if (!reduce_gram && !local_ok) return 1;
     *info_host = 0;
     hipError_t e1 = hipSuccess;
     {
         ws_scope ws(c);
-        int* words = ws.alloc<int>(40);                            // [0] potrf info, [1 .. nblk] guard verdicts
+        int* words = ws.alloc<int>(TF_VERDICT_ALLOC);                            // [0] potrf info, [1 .. nblk] guard verdicts
         if (!words) return reduce_gram ? RLHIP_ERR_HIP(hipErrorOutOfMemory) : 1;
         T *Upk_all = nullptr, *Dinv_all = nullptr, *Uneg = nullptr, *fdump = nullptr;
         if (local_ok) {
@@ -1137,7 +1110,7 @@ int cholqrq(rlhip_ctx* c, int64_t m, int64_t k, T* A, int64_t lda, T* R, int red
                 local_ok = false;                                     // (rank-local: the substitution route below needs none of them)
             }
         }
-        hipError_t e0 = hipMemsetAsync(words, 0, 40 * sizeof(int), c->stream);
+        hipError_t e0 = hipMemsetAsync(words, 0, TF_VERDICT_ALLOC * sizeof(int), c->stream);
         if (e0 != hipSuccess) return RLHIP_ERR_HIP(e0);
         int rc = laset<T>(c, 2, k, k, T(0), T(0), R, k);
         if (!rc && m > 0) rc = syrk<T>(c, Upper, 1, k, m, T(1), A, lda, T(0), R, k);
@@ -1149,12 +1122,12 @@ int cholqrq(rlhip_ctx* c, int64_t m, int64_t k, T* A, int64_t lda, T* R, int red
                 double* G2 = ws.alloc<double>((size_t)k * k + 1);
                 if (!G2) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
                 hipError_t e = hipMemcpyAsync(G2, R, (size_t)k * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-                if (e == hipSuccess) e = hipMemcpyAsync(G2 + (size_t)k * k, (double*)(c->d_mail + 40), sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+                if (e == hipSuccess) e = hipMemcpyAsync(G2 + (size_t)k * k, (double*)(c->d_mail + MAIL_NORMA_SSQ), sizeof(double), hipMemcpyDeviceToDevice, c->stream);
                 if (e != hipSuccess) return RLHIP_ERR_HIP(e);
                 rc = rlhip_allreduce_sum_f64(c, G2, k * k + 1);
                 if (!rc) {
                     e = hipMemcpyAsync(R, G2, (size_t)k * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-                    if (e == hipSuccess) e = hipMemcpyAsync(c->h_mail + 41, G2 + (size_t)k * k, sizeof(double), hipMemcpyDeviceToHost, c->stream);
+                    if (e == hipSuccess) e = hipMemcpyAsync(c->h_mail + MAIL_NORMA_SSQ_RANKS, G2 + (size_t)k * k, sizeof(double), hipMemcpyDeviceToHost, c->stream);
                     if (e != hipSuccess) return RLHIP_ERR_HIP(e);
                     c->norma_reduced = 1;
                 }
@@ -1165,20 +1138,18 @@ int cholqrq(rlhip_ctx* c, int64_t m, int64_t k, T* A, int64_t lda, T* R, int red
         if (!rc) rc = potrf_upper_enqueue<T>(c, k, R, k, words);
         if (rc) return rc < 0 ? rc : RLHIP_ERR_HIP(hipErrorUnknown);
         if (local_ok) {
-            hipLaunchKernelGGL(trsm_blk_pack_kernel<T>, dim3(BW / 32 + 24, (unsigned)nblk), dim3(256), 0, c->stream, k, (int)NonUnit, R, k, Upk_all, Dinv_all, words + 1, 1.0e6);
-            hipLaunchKernelGGL(trsm_neg_pack_kernel<T>, dim3((unsigned)(k / 32), (unsigned)(k / 32)), dim3(256), 0, c->stream, k, k, R, k, Uneg);
-            {
-                hipError_t le = hipGetLastError();
-                if (le != hipSuccess) return RLHIP_ERR_HIP(le);
-            }
-            rc = tf_launch<T, 0>(c, m, k, k, T(1), Uneg, Dinv_all, A, lda, 0, (int)nblk, 0, fdump, (const T*)nullptr, (int64_t)0, (const int64_t*)nullptr, (int64_t)0, words, 1 + (int)nblk);
+            RLHIP_CHECK(tf_enqueue_blk_pack<T>(c, k, nblk, (int)NonUnit, R, k, Upk_all, Dinv_all, words + 1));
+            RLHIP_CHECK(tf_enqueue_neg_pack<T>(c, k, k, R, k, Uneg));
+            TfArgs<T> a{m, k, k, T(1), Uneg, Dinv_all, A, lda, 0, (int)nblk, 0, fdump};
+            a.gate = words; a.ngate = 1 + (int)nblk;
+            rc = tf_launch<T, 0>(c, a);
             if (rc) return rc;
         }
-        e1 = hipMemcpyAsync(c->h_mail + 44, words, 40 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+        e1 = hipMemcpyAsync(c->h_mail + MAIL_CHOLQRQ, words, TF_VERDICT_ALLOC * sizeof(int), hipMemcpyDeviceToHost, c->stream);
         if (e1 == hipSuccess) e1 = rlhip_stream_sync(c);
     }
     if (e1 != hipSuccess) return RLHIP_ERR_HIP(e1);
-    const int* w = (const int*)(c->h_mail + 44);
+    const int* w = (const int*)(c->h_mail + MAIL_CHOLQRQ);
     *info_host = w[0];
     if (w[0] != 0) return 0;                                      // not positive definite: A untouched, R partially factored (as dpotrf leaves it)
     bool guard = !local_ok;

@@ -930,7 +930,7 @@ def test_trsm_fused_asm_and_plain_loads_agree_bitwise(ctx, monkeypatch, m, n, dt
 @pytest.mark.parametrize("m,n", [(40970, 512), (49152, 256), (33000, 1024)])
 def test_trsm_fused_fp32_192_row_workgroups_equal_128_row_ones_bitwise(ctx, m, n):
     """fp32 in-place fused solve: row counts whose 128-row workgroups would leave the last round over the CUs half empty run 192-row
-    workgroups (twelve wavefronts; tri.hip::tf_launch_hpr).  A row of X depends on its own row of B only and both instantiations do the
+    workgroups (twelve wavefronts; tri.hip::tf_launch).  A row of X depends on its own row of B only and both instantiations do the
     same arithmetic in the same order, so the head and the tail of the tall solve must equal, BIT FOR BIT, the same rows solved as two
     20000-row problems (128-row workgroups); residual checked in fp64 on both ends (ragged last workgroup and ragged last wavefront)."""
     import torch
