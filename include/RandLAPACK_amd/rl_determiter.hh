@@ -1,0 +1,258 @@
+// Block / lockstep preconditioned conjugate gradients on the device (RandLAPACK/comps/rl_determiter.hh:140-526): StatefulFrobeniusNorm,
+// posm_square and pcg.  pcg_saddle (:23-137) is not built.
+//
+// Everything n x s and s x s lives in device memory on G.q; the loop is the reference's, statement by statement (line numbers at the right),
+// with these differences:
+//   - H, X and the block handed to `seminorm` are DEVICE arrays;
+//   - posm_square runs the Cholesky attempt in one device kernel (rlhip_posm_square_*) and, when that reports a failed pivot, the reference's
+//     eigenvalue fallback on the HOST (rl_determiter_host.hh: the product links no host LAPACK, and s <= 64 in practice).  LHS is not
+//     destroyed.  In lockstep mode the kernel applies zero_off_diagonal to both of its operands itself, so RNR and ableft are never
+//     rewritten on the device; the values that reach alpha and beta are the same;
+//   - X += P alpha, R -= GP alpha and ||R|| are one kernel (rlhip_pcg_update_xr_*), P <- NR + P beta another (rlhip_pcg_update_p_*);
+//   - when the seminorm is StatefulFrobeniusNorm<T>, the two norms of an iteration are taken from the squared column norms (sums in double,
+//     fixed order) that the update kernel and the preconditioner return, and the beta solve is enqueued BEFORE the stop test so that its status
+//     comes back with them: two host reads per iteration (the status of the alpha solve; the two norms + the status of the beta solve), and
+//     s x s copies only when a Cholesky attempt fails.  What the speculative work overwrites (RNR, alpha, beta, ableft) is not read after a stop.
+//     Any other callable is called as in the reference, after one more read per solve;
+//   - a trailing `int64_t* iters` (optional) returns k, the number of iterations started.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <iostream>
+#include <limits>
+#include <type_traits>
+#include <vector>
+#include "rl_exceptions.hh"
+#include "rl_blaspp.hh"
+#include "rl_lapackpp.hh"
+#include "rl_determiter_host.hh"
+
+namespace RandLAPACK {
+
+/// The Frobenius norm of a DEVICE block, every value kept (rl_determiter.hh:139-151).  pcg recognises this type and fills `history` from the
+/// sums its kernels return instead of calling it.
+template <typename T>
+struct StatefulFrobeniusNorm {
+    std::vector<T> history;
+    blas::Queue* q = nullptr;              // the queue operator() reads through; null: the default queue
+    StatefulFrobeniusNorm() : history() {}
+    explicit StatefulFrobeniusNorm(blas::Queue& queue) : history(), q(&queue) {}
+    StatefulFrobeniusNorm(StatefulFrobeniusNorm<T>&& other) noexcept : history(std::move(other.history)), q(other.q) {}
+    inline T operator()(int64_t n, int64_t s, const T* NR) {
+        const T nrm = lapack::lange(Norm::Fro, n, s, NR, n > 0 ? n : 1, q ? *q : blas::default_queue());
+        this->history.push_back(nrm);
+        return nrm;
+    }
+};
+
+namespace _pcg_impl {
+
+inline int posm_enqueue(blas::Queue& q, int64_t s, const double* L, double* R, int diag_only, int64_t* st) { return rlhip_posm_square_f64(q.ctx(), s, L, R, diag_only, st); }
+inline int posm_enqueue(blas::Queue& q, int64_t s, const float* L, float* R, int diag_only, int64_t* st) { return rlhip_posm_square_f32(q.ctx(), s, L, R, diag_only, st); }
+inline int update_xr(blas::Queue& q, int64_t n, int64_t s, const double* a, const double* P, const double* GP, double* X, double* R, double* cn) {
+    return rlhip_pcg_update_xr_f64(q.ctx(), n, s, a, P, n, GP, n, X, n, R, n, cn);
+}
+inline int update_xr(blas::Queue& q, int64_t n, int64_t s, const float* a, const float* P, const float* GP, float* X, float* R, double* cn) {
+    return rlhip_pcg_update_xr_f32(q.ctx(), n, s, a, P, n, GP, n, X, n, R, n, cn);
+}
+inline int update_p(blas::Queue& q, int64_t n, int64_t s, const double* b, const double* NR, double* P) { return rlhip_pcg_update_p_f64(q.ctx(), n, s, b, NR, n, P, n); }
+inline int update_p(blas::Queue& q, int64_t n, int64_t s, const float* b, const float* NR, float* P) { return rlhip_pcg_update_p_f32(q.ctx(), n, s, b, NR, n, P, n); }
+inline int colnorm2(blas::Queue& q, int64_t n, int64_t s, const double* A, double* cn) { return rlhip_pcg_colnorm2_f64(q.ctx(), n, s, A, n, cn); }
+inline int colnorm2(blas::Queue& q, int64_t n, int64_t s, const float* A, double* cn) { return rlhip_pcg_colnorm2_f32(q.ctx(), n, s, A, n, cn); }
+inline int axpby(blas::Queue& q, int64_t n, double a, const double* x, double b, double* y) { return rlhip_axpby_f64(q.ctx(), n, a, x, b, y); }
+inline int axpby(blas::Queue& q, int64_t n, float a, const float* x, float b, float* y) { return rlhip_axpby_f32(q.ctx(), n, a, x, b, y); }
+
+// N(R) -> C with the squared column norms of C: the preconditioner's own fused form when it has one, a pass over C otherwise
+template <typename FN, typename T, typename = void>
+struct has_apply_norms : std::false_type {};
+template <typename FN, typename T>
+struct has_apply_norms<FN, T, std::void_t<decltype(std::declval<FN&>().apply(Layout::ColMajor, int64_t(0), T(1), (const T*)nullptr, int64_t(0), T(0), (T*)nullptr,
+                                                                            int64_t(0), (double*)nullptr))>> : std::true_type {};
+template <typename T, typename FN>
+void apply_with_norms(FN& N, blas::Queue& q, int64_t n, int64_t s, T* R, T* C, double* cn) {
+    if constexpr (has_apply_norms<FN, T>::value) {
+        N.apply(Layout::ColMajor, s, (T)1.0, R, n, (T)0.0, C, n, cn);
+    } else {
+        N(Layout::ColMajor, s, (T)1.0, R, n, (T)0.0, C, n);
+        blas::check(colnorm2(q, n, s, C, cn), "pcg_colnorm2");
+    }
+}
+
+inline double root_of_sum(const double* cn, int64_t s) {
+    double t = 0;
+    for (int64_t j = 0; j < s; ++j) t += cn[j];
+    return std::sqrt(t);
+}
+
+/// what posm_square does once the status of the device attempt is known: s on success; on -1 the s x s pair comes down, the fallback
+/// (rl_determiter.hh:258-281) runs on the host and, if it produced a solution, RHS goes back up
+template <typename T>
+int64_t posm_finish(int64_t s, const T* LHS, T* RHS, bool diag_only, int64_t status, blas::Queue& q) {
+    if (status >= 0) return status;
+    const int64_t ss = s * s;
+    std::vector<T> L((size_t)ss), B((size_t)ss), work((size_t)ss);
+    blas::copy_to_host(ss, LHS, L.data(), q);
+    blas::copy_to_host(ss, RHS, B.data(), q);
+    if (diag_only) {
+        zero_off_diagonal(L.data(), s);
+        zero_off_diagonal(B.data(), s);
+    }
+    const int64_t r = posm_square_fallback(s, L.data(), B.data(), work.data());
+    if (r >= 0) blas::copy_to_device(ss, B.data(), RHS, q);
+    return r;
+}
+
+}  // namespace _pcg_impl
+
+/// RHS <- pinv(LHS) RHS for the PSD s x s matrix LHS (DEVICE, ld s, lower triangle read, left as it is; RHS DEVICE, ld s).  `work`: DEVICE,
+/// at least s * s entries and at least 8 bytes, 8-byte aligned (its first word receives the kernel's status).  Returns rank(LHS), or
+/// -(s + 1) when LHS is not positive semidefinite, -(s + 2) when it is zero up to rounding.                      rl_determiter.hh:231-282
+/// diag_only: the lockstep form, zero_off_diagonal applied to both matrices first.
+template <typename T>
+int64_t posm_square(int64_t s, const T* LHS, T* RHS, T* work, blas::Queue& q = blas::default_queue(), bool diag_only = false) {
+    int64_t* st = reinterpret_cast<int64_t*>(work);
+    blas::check(_pcg_impl::posm_enqueue(q, s, LHS, RHS, diag_only ? 1 : 0, st), "posm_square");
+    int64_t status = 0;
+    blas::copy_to_host(1, st, &status, q);
+    return _pcg_impl::posm_finish(s, LHS, RHS, diag_only, status, q);
+}
+
+/// Solves G_i x_i = h_i, i = 1..s, with preconditioners N_i.  G.num_ops == 1: block PCG with block size s; G.num_ops == s: s single-vector
+/// iterations kept in lockstep.  G and N are called as G(Layout::ColMajor, s, alpha, B, ldb, beta, C, ldc) on DEVICE blocks; G.dim, G.num_ops
+/// and G.q (the queue everything runs on) are read.  H (in) and X (in: the starting point, out: the solution) are DEVICE dim x s arrays with
+/// stride dim.  seminorm(dim, s, R_dev) is called on the residual (even calls) and the preconditioned residual (odd calls); iterations stop
+/// when normNR < tol (1 + normNR0) or after max_iters.                                                           rl_determiter.hh:371-493
+template <typename T, typename FG, typename FSeminorm, typename FN>
+void pcg(FG& G, const T* H, int64_t s, FSeminorm& seminorm, T tol, int64_t max_iters, FN& N, T* X, bool verbose, int64_t* iters = nullptr) {
+    constexpr bool fused_norms = std::is_same_v<FSeminorm, StatefulFrobeniusNorm<T>>;
+    int64_t n = G.dim;                                                                                                              // :383
+    int64_t ns = n * s;
+    int64_t ss = s * s;
+    bool treat_as_separable = G.num_ops > 1;                                                                                        // :386
+    if (treat_as_separable) { randlapack_require(s == G.num_ops) << "with separable treatment, s=" << s << " must equal G.num_ops=" << G.num_ops; }
+    randlapack_require(s >= 1 && n >= 1) << "pcg needs s=" << s << " >= 1 and dim=" << n << " >= 1";
+    blas::Queue& q = G.q;
+    if (iters) *iters = 0;
+
+    // all work space is zero-initialised; only R is overwritten                                                                    :389-403
+    blas::Scratch ws(q);
+    T* allwork = ws.alloc<T>(4 * ns + 4 * ss);
+    blas::device_memset(allwork, 0, 4 * ns + 4 * ss, q);
+    T* R = allwork;
+    blas::device_copy_vector(ns, H, R, q);
+    T* P = R + ns;
+    T* GP = P + ns;
+    T* NR = GP + ns;
+    T* RNR = NR + ns;
+    T* alpha = RNR + ss;
+    T* beta = alpha + ss;
+    T* ableft = beta + ss;                       // (the reference's `scratch` block backs up LHS for its potrf; the kernel leaves LHS alone)
+    // what comes back from the device: the status words of the two solves, then the squared column norms of R and of N R
+    int64_t* mail = ws.alloc<int64_t>(2 + 2 * s);
+    double* cnR = reinterpret_cast<double*>(mail + 2);
+    double* cnNR = cnR + s;
+    std::vector<int64_t> mail_host((size_t)(2 + 2 * s));
+    const double* cnR_host = reinterpret_cast<const double*>(mail_host.data() + 2);
+    const double* cnNR_host = cnR_host + s;
+    const int diag_only = treat_as_separable ? 1 : 0;
+
+    T normNR = INFINITY;                                                                                                            // :405
+    auto layout = Layout::ColMajor;
+
+    G(layout, s, (T)1.0, X, n, (T)0.0, GP, n);                                           // GP <- G X                               :410
+    blas::check(_pcg_impl::axpby(q, ns, (T)-1.0, GP, (T)1.0, R), "axpby");               // R <- R - GP                             :412
+    if constexpr (fused_norms) {
+        blas::check(_pcg_impl::colnorm2(q, n, s, R, cnR), "pcg_colnorm2");
+        _pcg_impl::apply_with_norms<T>(N, q, n, s, R, P, cnNR);                          // P <- N R                                :414
+    } else {
+        N(layout, s, (T)1.0, R, n, (T)0.0, P, n);
+    }
+    blas::gemm(layout, Op::Trans, Op::NoTrans, s, s, n, (T)1.0, R, n, P, n, (T)0.0, RNR, s, q);   // RNR <- R^T N R                 :416
+    // (zero_off_diagonal(RNR), :418: applied by the solve kernel to its operands)
+    blas::device_copy_vector(ss, RNR, alpha, q);                                         // alpha <- RNR                            :420
+
+    int64_t k = 0;
+    T normR0, normNR0;
+    if constexpr (fused_norms) {
+        blas::copy_to_host(2 + 2 * s, mail, mail_host.data(), q);
+        normR0 = (T)_pcg_impl::root_of_sum(cnR_host, s);                                                                            // :424-425
+        normNR0 = (T)_pcg_impl::root_of_sum(cnNR_host, s);
+        seminorm.history.push_back(normR0);
+        seminorm.history.push_back(normNR0);
+    } else {
+        normR0 = seminorm(n, s, R);
+        normNR0 = seminorm(n, s, P);
+    }
+    T stop_abstol = tol * ((T)1.0 + normNR0);                                                                                       // :426
+    int64_t subspace_dim = 0;
+    if (verbose) std::cout << "normNR : " << normNR0 << "\tnormR : " << normR0 << "\tk: 0\tdim : 0\n";
+    while (subspace_dim < n && k < max_iters) {                                                                                     // :430
+        k++;
+        if (iters) *iters = k;
+        G(layout, s, (T)1.0, P, n, (T)0.0, GP, n);                                       // GP <- G P                               :436
+        blas::gemm(layout, Op::Trans, Op::NoTrans, s, s, n, (T)1.0, P, n, GP, n, (T)0.0, ableft, s, q);   // ableft <- P^T G P      :438
+        blas::check(_pcg_impl::posm_enqueue(q, s, ableft, alpha, diag_only, mail), "posm_square");   // alpha <- ableft^-1 alpha    :440-441
+        blas::copy_to_host(1, mail, mail_host.data(), q);
+        int64_t subspace_incr = _pcg_impl::posm_finish(s, ableft, alpha, treat_as_separable, mail_host[0], q);
+        if (treat_as_separable && subspace_incr > 0) subspace_incr = 1;                                                             // :443-444
+        if (subspace_incr < -((int64_t)s)) break;                                                                                   // :446-447
+        subspace_dim = subspace_dim + subspace_incr;
+
+        T normR;
+        if constexpr (fused_norms) {
+            blas::check(_pcg_impl::update_xr(q, n, s, alpha, P, GP, X, R, cnR), "pcg_update_xr");   // X += P alpha, R -= GP alpha  :450-453
+            _pcg_impl::apply_with_norms<T>(N, q, n, s, R, NR, cnNR);                     // NR <- N R                               :462
+            // enqueued ahead of the stop test, so that one read brings the norms and the status of the beta solve
+            blas::device_copy_vector(ss, RNR, ableft, q);                                // ableft <- RNR                           :472
+            blas::gemm(layout, Op::Trans, Op::NoTrans, s, s, n, (T)1.0, R, n, NR, n, (T)0.0, RNR, s, q);   // RNR <- R^T NR         :474
+            blas::device_copy_vector(ss, RNR, alpha, q);                                 // alpha <- RNR                            :477
+            blas::device_copy_vector(ss, alpha, beta, q);                                // beta <- alpha                           :479
+            blas::check(_pcg_impl::posm_enqueue(q, s, ableft, beta, diag_only, mail + 1), "posm_square");   //                      :481
+            blas::copy_to_host(1 + 2 * s, mail + 1, mail_host.data() + 1, q);
+            normR = (T)_pcg_impl::root_of_sum(cnR_host, s);                                                                         // :460
+            normNR = (T)_pcg_impl::root_of_sum(cnNR_host, s);                                                                       // :464
+            seminorm.history.push_back(normR);
+            seminorm.history.push_back(normNR);
+        } else {
+            blas::check(_pcg_impl::update_xr(q, n, s, alpha, P, GP, X, R, (double*)nullptr), "pcg_update_xr");
+            normR = seminorm(n, s, R);                                                                                              // :460
+            N(layout, s, (T)1.0, R, n, (T)0.0, NR, n);                                                                              // :462
+            normNR = seminorm(n, s, NR);                                                                                            // :464
+        }
+        if (verbose) std::cout << "normNR : " << normNR << "\tnormR : " << normR << "\tk: " << k << "\tdim : " << subspace_dim << '\n';
+        if (normNR < stop_abstol) break;                                                                                            // :467-468
+        int64_t err;
+        if constexpr (fused_norms) {
+            err = _pcg_impl::posm_finish(s, ableft, beta, treat_as_separable, mail_host[1], q);   // beta <- ableft^-1 beta         :481
+        } else {
+            blas::device_copy_vector(ss, RNR, ableft, q);                                                                           // :472
+            blas::gemm(layout, Op::Trans, Op::NoTrans, s, s, n, (T)1.0, R, n, NR, n, (T)0.0, RNR, s, q);                            // :474
+            blas::device_copy_vector(ss, RNR, alpha, q);                                                                            // :477
+            blas::device_copy_vector(ss, alpha, beta, q);                                                                           // :479
+            blas::check(_pcg_impl::posm_enqueue(q, s, ableft, beta, diag_only, mail + 1), "posm_square");                           // :481
+            blas::copy_to_host(1, mail + 1, mail_host.data() + 1, q);
+            err = _pcg_impl::posm_finish(s, ableft, beta, treat_as_separable, mail_host[1], q);
+        }
+        if (err < -((int64_t)s)) break;                                                                                             // :483-484
+        blas::check(_pcg_impl::update_p(q, n, s, beta, NR, P), "pcg_update_p");          // P <- NR + P beta                        :485-488
+    }
+    q.sync();                                    // (the work space goes back to the arena)
+}
+
+/// The reference's std::vector wrapper (:512-526) for HOST vectors: H and X go to the device, the solution comes back into X.
+template <typename T, typename FG, typename FN, typename FSeminorm = StatefulFrobeniusNorm<T>>
+FSeminorm pcg(FG& G, const std::vector<T>& H, T tol, int64_t max_iters, FN& N, std::vector<T>& X, bool verbose) {
+    FSeminorm seminorm{};
+    int64_t s = ((int64_t)H.size()) / G.dim;
+    blas::Queue& q = G.q;
+    blas::Scratch ws(q);
+    T* Hd = ws.alloc<T>(G.dim * s);
+    T* Xd = ws.alloc<T>(G.dim * s);
+    blas::copy_to_device(G.dim * s, H.data(), Hd, q);
+    blas::copy_to_device(G.dim * s, X.data(), Xd, q);
+    pcg(G, (const T*)Hd, s, seminorm, tol, max_iters, N, Xd, verbose);
+    blas::copy_to_host(G.dim * s, Xd, X.data(), q);
+    return seminorm;
+}
+
+}  // namespace RandLAPACK

@@ -1,5 +1,6 @@
 // The symmetric (Nystrom) analogue of the sketch-and-factor path, device flavour: one header for
 //   linops::ExplicitSymLinOp  RandLAPACK/linops/rl_sym_linops.hh:55-118   symmetric matrix given by one stored triangle
+//   linops::RegExplicitSymLinOp, linops::SpectralPrecond  rl_sym_linops.hh:134-379   A + mu_i I and the preconditioner PCG pairs it with
 //   SYPS                      RandLAPACK/comps/rl_syps.hh:42-145           power sketch  S <- (A^p) Omega with QR stabilisation
 //   SYRF                      RandLAPACK/comps/rl_syrf.hh:18-95            range finder  Q = orth(A S)
 //   power_error_est, REVD2    RandLAPACK/drivers/rl_revd2.hh:34-246        A ~ V diag(eigvals) V^T, rank doubled until the
@@ -130,6 +131,121 @@ private:
     ExplicitSymLinOp<T> sym_;
     void axpby_(int64_t n, double a, const double* x, double b, double* y) { blas::check(rlhip_axpby_f64(q.ctx(), n, a, x, b, y), "axpby"); }
     void axpby_(int64_t n, float a, const float* x, float b, float* y) { blas::check(rlhip_axpby_f32(q.ctx(), n, a, x, b, y), "axpby"); }
+};
+
+/// The spectral preconditioner P_r = V diag(D_r) V^T + I (rl_sym_linops.hh:204-379), D_r[i] = (eigvals[dim_pre-1] + mu_r) / (eigvals[i] + mu_r) - 1,
+/// for one regularisation parameter or one per column.  V (dim x dim_pre, ldv), D (dim_pre x num_ops) and the work space W (dim_pre x num_rhs)
+/// are DEVICE arrays; operator() is rlhip_spectral_precond_apply_* (two products of the library's GEMM around two element-wise kernels).
+/// Deviations: a blas::Queue& as every operator here has; prep from device V / eigvals BORROWS V (rpchol_pc_data's output
+/// never visits the host; the caller keeps it alive) and reads the dim_pre eigenvalues once to build D; step 3 indexes the columns of C
+/// with ldc (the reference uses ldb, :361) and step 4 carries alpha as the reference's comment says (its call passes 1.0, :376).
+template <typename T>
+struct SpectralPrecond {
+    using scalar_t = T;
+    const int64_t m;
+    const int64_t dim;
+    int64_t dim_pre = 0;
+    int64_t num_rhs = 0;
+    T* V = nullptr;
+    T* D = nullptr;
+    T* W = nullptr;
+    int64_t num_ops = 0;
+    int64_t ldv = 0;
+    blas::Queue& q;
+
+    explicit SpectralPrecond(int64_t d, blas::Queue& queue = blas::default_queue()) : m(d), dim(d), ldv(d), q(queue) {}                    // :256
+    SpectralPrecond(SpectralPrecond const&) = delete;
+    SpectralPrecond& operator=(SpectralPrecond const&) = delete;
+    ~SpectralPrecond() {
+        if (D) blas::device_free(D, q);
+        if (V && owns_V_) blas::device_free(V, q);
+        if (W) blas::device_free(W, q);
+    }
+
+    void reset_owned_buffers(int64_t arg_dim_pre, int64_t arg_num_rhs, int64_t arg_num_ops, bool own_V = true) {                             // :285-304
+        randlapack_require(arg_num_rhs == arg_num_ops || arg_num_ops == 1) << "arg_num_rhs=" << arg_num_rhs << " must equal arg_num_ops=" << arg_num_ops << ", or arg_num_ops must be 1";
+        if (arg_dim_pre * arg_num_ops > dim_pre * num_ops || !D) {
+            if (D) blas::device_free(D, q);
+            D = blas::device_malloc<T>(arg_dim_pre * arg_num_ops, q);
+        }
+        if (arg_dim_pre > dim_pre || !V || !owns_V_ || !own_V) {
+            if (V && owns_V_) blas::device_free(V, q);
+            V = own_V ? blas::device_malloc<T>(dim * arg_dim_pre, q) : nullptr;
+            owns_V_ = own_V;
+            ldv = dim;
+        }
+        if (arg_dim_pre * arg_num_rhs > dim_pre * num_rhs || !W) {
+            if (W) blas::device_free(W, q);
+            W = blas::device_malloc<T>(arg_dim_pre * arg_num_rhs, q);
+        }
+        dim_pre = arg_dim_pre;
+        num_rhs = arg_num_rhs;
+        num_ops = arg_num_ops;
+    }
+
+    /// eigvals, mus: HOST arrays (dim_pre and num_ops entries); D goes to the device                                                    (:306-316)
+    void set_D_from_eigs_and_regs(const T* eigvals, const T* mus) {
+        std::vector<T> Dh((size_t)std::max<int64_t>(dim_pre * num_ops, 1));
+        for (int64_t r = 0; r < num_ops; ++r) {
+            const T mu_r = mus[r];
+            T* D_r = Dh.data() + r * dim_pre;
+            const T numerator = eigvals[dim_pre - 1] + mu_r;
+            for (int64_t i = 0; i < dim_pre; ++i) D_r[i] = (numerator / (eigvals[i] + mu_r)) - (T)1.0;
+        }
+        if (dim_pre * num_ops > 0) blas::copy_to_device(dim_pre * num_ops, Dh.data(), D, q);
+        q.sync();                                // (Dh goes away)
+    }
+
+    /// host eigenvectors (dim x dim_pre, ld dim) and eigenvalues (positive, decreasing), copied up                                    (:318-326)
+    void prep(std::vector<T>& eigvecs, std::vector<T>& eigvals, std::vector<T>& mus, int64_t arg_num_rhs) {
+        const int64_t arg_num_ops = (int64_t)mus.size(), arg_dim_pre = (int64_t)eigvals.size();
+        randlapack_require(arg_num_ops >= 1 && arg_dim_pre >= 1) << "SpectralPrecond::prep needs at least one eigenpair and one regularization parameter";
+        randlapack_require((int64_t)eigvecs.size() >= dim * arg_dim_pre) << "eigvecs holds " << eigvecs.size() << " entries, dim * dim_pre=" << dim * arg_dim_pre;
+        reset_owned_buffers(arg_dim_pre, arg_num_rhs, arg_num_ops);
+        blas::copy_to_device(dim * arg_dim_pre, eigvecs.data(), V, q);
+        set_D_from_eigs_and_regs(eigvals.data(), mus.data());
+    }
+    /// DEVICE eigenvectors (dim x arg_dim_pre, ld arg_ldv; borrowed, not copied) and DEVICE eigenvalues, as rpchol_pc_data returns them: one
+    /// host read of arg_dim_pre entries builds D
+    void prep(const T* V_dev, int64_t arg_ldv, const T* eigvals_dev, int64_t arg_dim_pre, std::vector<T>& mus, int64_t arg_num_rhs) {
+        const int64_t arg_num_ops = (int64_t)mus.size();
+        randlapack_require(arg_num_ops >= 1 && arg_dim_pre >= 1) << "SpectralPrecond::prep needs at least one eigenpair and one regularization parameter";
+        randlapack_require(arg_ldv >= dim) << "ldv=" << arg_ldv << " < dim=" << dim;
+        reset_owned_buffers(arg_dim_pre, arg_num_rhs, arg_num_ops, false);
+        V = const_cast<T*>(V_dev);
+        ldv = arg_ldv;
+        std::vector<T> ev((size_t)arg_dim_pre);
+        blas::copy_to_host(arg_dim_pre, eigvals_dev, ev.data(), q);
+        set_D_from_eigs_and_regs(ev.data(), mus.data());
+    }
+
+    /// C (dim x n) = alpha * P * B + beta * C                                                                                          (:328-378)
+    void operator()(Layout layout, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc) { apply(layout, n, alpha, B, ldb, beta, C, ldc, nullptr); }
+    /// the same, and colnorm2_dev[j] (DEVICE, double, n entries; may be null) <- the squared norm of column j of the new C: what pcg reads
+    /// instead of a separate pass over N R
+    void apply(Layout layout, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc, double* colnorm2_dev) {
+        randlapack_require(layout == Layout::ColMajor) << "this operator only supports ColMajor layout";
+        randlapack_require(ldb >= dim) << "ldb=" << ldb << " < dim=" << dim << " (ldb must be >= operator dimension)";
+        randlapack_require(ldc >= dim) << "ldc=" << ldc << " < dim=" << dim << " (ldc must be >= operator dimension)";
+        randlapack_require(V != nullptr && D != nullptr) << "SpectralPrecond: prep() has not been called";
+        if (num_ops != 1) {
+            randlapack_require(n == num_ops) << "with num_ops>1, n=" << n << " must equal num_ops=" << num_ops << " so each column gets its own regularization";
+        } else {
+            randlapack_require(num_rhs >= n) << "this->num_rhs=" << num_rhs << " must be >= n=" << n;
+        }
+        blas::check(apply_(n, alpha, B, ldb, beta, C, ldc, colnorm2_dev), "spectral_precond_apply");
+    }
+
+private:
+    bool owns_V_ = false;
+    int apply_(int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc, double* cn) {
+        if constexpr (sizeof(T) == 8)
+            return rlhip_spectral_precond_apply_f64(q.ctx(), dim, dim_pre, (const double*)V, ldv, (const double*)D, num_ops, n, alpha, (const double*)B, ldb,
+                                                    beta, (double*)C, ldc, (double*)W, cn);
+        else
+            return rlhip_spectral_precond_apply_f32(q.ctx(), dim, dim_pre, (const float*)V, ldv, (const float*)D, num_ops, n, alpha, (const float*)B, ldb,
+                                                    beta, (float*)C, ldc, (float*)W, cn);
+    }
 };
 
 }  // namespace linops

@@ -466,6 +466,47 @@ int rlhip_gather_rows_f32(rlhip_ctx* ctx, int64_t cnt, const int64_t* idx_dev, i
 int rlhip_gather_cols_f64(rlhip_ctx* ctx, int64_t m, int64_t cnt, const int64_t* idx_dev, const double* A, int64_t lda, double* out, int64_t ldo);
 int rlhip_gather_cols_f32(rlhip_ctx* ctx, int64_t m, int64_t cnt, const int64_t* idx_dev, const float* A, int64_t lda, float* out, int64_t ldo);
 
+/* ---- block / lockstep PCG and the spectral preconditioner (pcg.hip; reference RandLAPACK/comps/rl_determiter.hh:181-493,
+ *      linops/rl_sym_linops.hh:204-379; the loop is include/RandLAPACK_amd/rl_determiter.hh).  All arrays are DEVICE, column-major; rows n .. ld-1
+ *      are never touched.  Sums over rows are returned in DOUBLE for both precisions: one partial per workgroup of 256 rows and column, the
+ *      partials added in a fixed order by one workgroup -- no atomics, bitwise reproducible.  Everything is asynchronous. ---- */
+/* rlhip_posm_square_*: the Cholesky half of posm_square (rl_determiter.hh:244-257).  LHS, RHS: s x s, ld s; the LOWER triangle of LHS is read
+ * and LHS is never written.  Success: RHS <- LHS^-1 RHS, *status_dev = s.  A pivot <= 0 or NaN (dpotrf's test): RHS untouched, *status_dev = -1
+ * (the caller runs the eigenvalue fallback, rl_determiter.hh posm_square).  diag_only != 0: zero_off_diagonal (:154-161) is applied to both
+ * matrices first -- s independent pivots, x = (b / sqrt(p)) / sqrt(p) as the two solves give it, off-diagonal entries of RHS written as exact zeros.
+ * s <= 64: one workgroup with both matrices in LDS.  s > 64: potrf, one triangular solve that forms U^-1, and two products on a scratch copy
+ * (one host read); diag_only keeps one element-wise workgroup. */
+int rlhip_posm_square_f64(rlhip_ctx* ctx, int64_t s, const double* LHS, double* RHS, int diag_only, int64_t* status_dev);
+int rlhip_posm_square_f32(rlhip_ctx* ctx, int64_t s, const float* LHS, float* RHS, int diag_only, int64_t* status_dev);
+/* rlhip_pcg_update_xr_*: X += P alpha and R -= GP alpha (the two products at rl_determiter.hh:450-453; alpha s x s, ld s; the rest n x s), and
+ * colnorm2_dev[j] = sum_i R(i,j)^2 of the UPDATED R (may be NULL).  s <= 64: one kernel, a thread owns a row, alpha staged once in LDS; P, GP, X
+ * and R are read once, X and R written once.  s > 64: rlhip_gemm twice and a column-norm pass. */
+int rlhip_pcg_update_xr_f64(rlhip_ctx* ctx, int64_t n, int64_t s, const double* alpha_dev, const double* P, int64_t ldp, const double* GP, int64_t ldgp,
+                            double* X, int64_t ldx, double* R, int64_t ldr, double* colnorm2_dev);
+int rlhip_pcg_update_xr_f32(rlhip_ctx* ctx, int64_t n, int64_t s, const float* alpha_dev, const float* P, int64_t ldp, const float* GP, int64_t ldgp,
+                            float* X, int64_t ldx, float* R, int64_t ldr, double* colnorm2_dev);
+/* rlhip_pcg_update_p_*: P <- NR + P beta in place (rl_determiter.hh:485-488).  s <= 64: a thread owns a row, NR is not copied.  s > 64: NR is
+ * copied to scratch, rlhip_gemm adds P beta, the copy moves into P. */
+int rlhip_pcg_update_p_f64(rlhip_ctx* ctx, int64_t n, int64_t s, const double* beta_dev, const double* NR, int64_t ldnr, double* P, int64_t ldp);
+int rlhip_pcg_update_p_f32(rlhip_ctx* ctx, int64_t n, int64_t s, const float* beta_dev, const float* NR, int64_t ldnr, float* P, int64_t ldp);
+/* colnorm2_dev[j] = sum_i A(i,j)^2 (A n x s), the same fixed-order sum the two kernels around it return (PCG's first residual) */
+int rlhip_pcg_colnorm2_f64(rlhip_ctx* ctx, int64_t n, int64_t s, const double* A, int64_t lda, double* colnorm2_dev);
+int rlhip_pcg_colnorm2_f32(rlhip_ctx* ctx, int64_t n, int64_t s, const float* A, int64_t lda, double* colnorm2_dev);
+/* rlhip_spectral_precond_apply_*: SpectralPrecond::operator() (rl_sym_linops.hh:328-378): C = alpha (V diag(D_j) V^T + I) B + beta C in four steps,
+ * W = V^T B (rlhip_gemm), W(i,j) *= D(i, num_ops == 1 ? 0 : j), C = beta C + alpha B (beta == 0 does not read C), C += alpha V W (rlhip_gemm).
+ * V: dim x dim_pre (ldv); D_dev: dim_pre x num_ops; B, C: dim x n; W_dev: dim_pre x n work space; num_ops is 1 or n.  colnorm2_dev (may be
+ * NULL) receives the squared column norms of the new C. */
+int rlhip_spectral_precond_apply_f64(rlhip_ctx* ctx, int64_t dim, int64_t dim_pre, const double* V, int64_t ldv, const double* D_dev, int64_t num_ops,
+                                     int64_t n, double alpha, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, double* W_dev,
+                                     double* colnorm2_dev);
+int rlhip_spectral_precond_apply_f32(rlhip_ctx* ctx, int64_t dim, int64_t dim_pre, const float* V, int64_t ldv, const float* D_dev, int64_t num_ops,
+                                     int64_t n, float alpha, const float* B, int64_t ldb, float beta, float* C, int64_t ldc, float* W_dev,
+                                     double* colnorm2_dev);
+/* The routes of the two update kernels, one count per call: 43 a fused rlhip_pcg_update_xr, 44 a fused rlhip_pcg_update_p, 45 either one on
+ * the composed route (s > 64).  They continue the numbering of rlhip_path_count below but are read here: that function's range ends at 42
+ * and answers -1 beyond it.  -1 for any other index. */
+int64_t rlhip_pcg_path_count(rlhip_ctx* ctx, int which);
+
 /* ---- row-block sharding across the GPUs of a node (new design; the reference has no
  *      distributed code).  One process per GPU.  Sum all-reduces run on the context's stream through RCCL
  *      (bound at run time), or through a host-installed hook.  With no communicator every call is a no-op,

@@ -226,6 +226,41 @@ int rlhip_drv_rpchol_pc_data_rbf_f64(rlhip_ctx* ctx, const double* X, int64_t ld
 int rlhip_drv_rpchol_pc_data_rbf_f32(rlhip_ctx* ctx, const float* X, int64_t ldx, int64_t rows_x, int64_t n, float bandwidth, float reg,
                                      int64_t* k, int64_t b, float* V, float* eigvals, uint32_t state[6]);
 
+/* pcg (comps/rl_determiter.hh:371-493; include/RandLAPACK_amd/rl_determiter.hh) on (A + mu_i I) x_i = h_i with the spectral preconditioner
+ * (linops/rl_sym_linops.hh:204-379) built from V (n x dim_pre, ldv, DEVICE) and eigvals (dim_pre, DEVICE, positive and decreasing) with
+ * A ~ V diag(eigvals) V^T.  A: linops::RegExplicitSymLinOp over the UPPER triangle of a DEVICE n x n matrix (lda).  regs_host: num_ops
+ * regularization parameters on the HOST; num_ops == 1 is block PCG with block size s, num_ops == s keeps s single-vector iterations in lockstep,
+ * anything else is refused (-100).  H (n x s, ld n, DEVICE) holds the right-hand sides, X (n x s, ld n, DEVICE) the starting point on entry and
+ * the solution on return.  Iterations stop when ||N R||_F < tol (1 + ||N R_0||_F) or after max_iters.  *iters = iterations started;
+ * hist (HOST, 2 (max_iters + 1) entries) receives ||R||_F and ||N R||_F per iteration, iteration 0 first: hist[2 i], hist[2 i + 1]; the entries
+ * of iterations not run stay as they were. */
+int rlhip_drv_pcg_dense_f64(rlhip_ctx* ctx, int64_t n, const double* A, int64_t lda, const double* regs_host, int64_t num_ops, const double* V,
+                            int64_t ldv, const double* eigvals, int64_t dim_pre, const double* H, double* X, int64_t s, double tol, int64_t max_iters,
+                            int64_t* iters, double* hist);
+int rlhip_drv_pcg_dense_f32(rlhip_ctx* ctx, int64_t n, const float* A, int64_t lda, const float* regs_host, int64_t num_ops, const float* V,
+                            int64_t ldv, const float* eigvals, int64_t dim_pre, const float* H, float* X, int64_t s, float tol, int64_t max_iters,
+                            int64_t* iters, float* hist);
+/* the same over linops::RBFKernelMatrix: the n points are the columns of X_pts (rows_x x n, ldx, DEVICE), K(i,j) = exp(-|x_i - x_j|^2 / (2 bandwidth^2)) */
+int rlhip_drv_pcg_rbf_f64(rlhip_ctx* ctx, const double* X_pts, int64_t ldx, int64_t rows_x, int64_t n, double bandwidth, const double* regs_host,
+                          int64_t num_ops, const double* V, int64_t ldv, const double* eigvals, int64_t dim_pre, const double* H, double* X, int64_t s,
+                          double tol, int64_t max_iters, int64_t* iters, double* hist);
+int rlhip_drv_pcg_rbf_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t n, float bandwidth, const float* regs_host,
+                          int64_t num_ops, const float* V, int64_t ldv, const float* eigvals, int64_t dim_pre, const float* H, float* X, int64_t s,
+                          float tol, int64_t max_iters, int64_t* iters, float* hist);
+/* krill_full_rpchol (drivers/rl_krill.hh:20-55; include/RandLAPACK_amd/rl_krill.hh) on the RBF matrix above: rpchol_pc_data of the unregularized
+ * kernel with rank *k (in: target, < 0: sqrt(n); out: achieved) and block size b (< 0: min(64, n / 4)), then pcg as above with s right-hand sides.
+ * state[6] is advanced as rlhip_drv_rpchol_pc_data_rbf_* advances it. */
+int rlhip_drv_krill_full_rpchol_rbf_f64(rlhip_ctx* ctx, const double* X_pts, int64_t ldx, int64_t rows_x, int64_t n, double bandwidth,
+                                        const double* regs_host, int64_t num_ops, const double* H, double* X, int64_t s, double tol, int64_t max_iters,
+                                        int64_t* k, int64_t b, uint32_t state[6], int64_t* iters, double* hist);
+int rlhip_drv_krill_full_rpchol_rbf_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t n, float bandwidth,
+                                        const float* regs_host, int64_t num_ops, const float* H, float* X, int64_t s, float tol, int64_t max_iters,
+                                        int64_t* k, int64_t b, uint32_t state[6], int64_t* iters, float* hist);
+/* posm_square (comps/rl_determiter.hh:231-282) as the C++ layer runs it: rlhip_posm_square_* and, after a failed pivot, the eigenvalue fallback on
+ * the host.  LHS, RHS: s x s DEVICE, ld s.  *code = rank(LHS), -(s + 1) not positive semidefinite, -(s + 2) zero up to rounding. */
+int rlhip_drv_posm_square_f64(rlhip_ctx* ctx, int64_t s, const double* LHS, double* RHS, int diag_only, int64_t* code);
+int rlhip_drv_posm_square_f32(rlhip_ctx* ctx, int64_t s, const float* LHS, float* RHS, int diag_only, int64_t* code);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,26 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # squared-exponential ker
         f"rlhip_drv_rpchol_pc_data_rbf_{_suf}": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, _T, _T, i64p, c_i64, c_vp, c_vp, u32p]),
     })
 
+f64p = C.POINTER(c_dbl)
+SIGNATURES["rlhip_pcg_path_count"] = (c_i64, [c_vp, c_int])
+for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # block / lockstep PCG, the spectral preconditioner and KRILL (pcg.hip, rl_determiter.hh, rl_krill.hh)
+    _Tp = C.POINTER(_T)
+    SIGNATURES.update({
+        f"rlhip_posm_square_{_suf}": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, c_vp]),
+        f"rlhip_pcg_update_xr_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+        f"rlhip_pcg_update_p_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64]),
+        f"rlhip_pcg_colnorm2_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
+        f"rlhip_spectral_precond_apply_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, _T, c_vp, c_i64, _T, c_vp, c_i64, c_vp,
+                                                         c_vp]),
+        f"rlhip_drv_pcg_dense_{_suf}": (c_int, [c_vp, c_i64, c_vp, c_i64, _Tp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, _T, c_i64, i64p,
+                                                _Tp]),
+        f"rlhip_drv_pcg_rbf_{_suf}": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, _T, _Tp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, _T, c_i64,
+                                              i64p, _Tp]),
+        f"rlhip_drv_krill_full_rpchol_rbf_{_suf}": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, _T, _Tp, c_i64, c_vp, c_vp, c_i64, _T, c_i64, i64p, c_i64,
+                                                            u32p, i64p, _Tp]),
+        f"rlhip_drv_posm_square_{_suf}": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, i64p]),
+    })
+
 _lib = None
 
 

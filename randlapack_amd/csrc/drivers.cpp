@@ -792,3 +792,108 @@ int rlhip_drv_rpchol_pc_data_rbf_f32(rlhip_ctx* ctx, const float* X, int64_t ldx
                                      int64_t* k, int64_t b, float* V, float* eigvals, uint32_t state[6]) {
     return drv_rpchol_pc_data_rbf<float>(ctx, X, ldx, rows_x, n, bandwidth, reg, k, b, V, eigvals, state);
 }
+
+// ---- PCG with the spectral preconditioner and KRILL (include/RandLAPACK_amd/rl_determiter.hh, rl_krill.hh)
+namespace {
+template <typename T>
+void store_hist(RandLAPACK::StatefulFrobeniusNorm<T> const& sn, int64_t max_iters, T* hist) {
+    if (!hist) return;
+    const size_t cap = (size_t)(2 * (max_iters + 1));
+    for (size_t i = 0; i < sn.history.size() && i < cap; ++i) hist[i] = sn.history[i];
+}
+template <typename T, typename GOP>
+int drv_pcg(blas::Queue& q, GOP& G, int64_t n, const T* V, int64_t ldv, const T* eigvals, int64_t dim_pre, std::vector<T>& mus, const T* H, T* X,
+            int64_t s, T tol, int64_t max_iters, int64_t* iters, T* hist) {
+    if (!H || !X || !V || !eigvals) throw RandLAPACK::Error("pcg: H, X, V and eigvals must not be null");
+    if (s < 1 || max_iters < 1 || !(tol >= (T)0)) throw RandLAPACK::Error("pcg: s and max_iters must be >= 1 and tol >= 0");
+    if ((int64_t)mus.size() != 1 && (int64_t)mus.size() != s) throw RandLAPACK::Error("pcg: num_ops must be 1 (block mode) or s (lockstep mode)");
+    lo::SpectralPrecond<T> N(n, q);
+    N.prep(V, ldv, eigvals, dim_pre, mus, s);
+    G.set_eval_includes_reg(true);
+    RandLAPACK::StatefulFrobeniusNorm<T> sn(q);
+    int64_t k = 0;
+    RandLAPACK::pcg(G, H, s, sn, tol, max_iters, N, X, false, &k);
+    if (iters) *iters = k;
+    store_hist(sn, max_iters, hist);
+    return 0;
+}
+template <typename T>
+int drv_pcg_dense(rlhip_ctx* ctx, int64_t n, const T* A, int64_t lda, const T* regs_host, int64_t num_ops, const T* V, int64_t ldv, const T* eigvals,
+                  int64_t dim_pre, const T* H, T* X, int64_t s, T tol, int64_t max_iters, int64_t* iters, T* hist) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (!regs_host || num_ops < 1) throw RandLAPACK::Error("pcg: regs_host must hold num_ops >= 1 regularization parameters");
+        std::vector<T> mus(regs_host, regs_host + num_ops);
+        lo::RegExplicitSymLinOp<T> G(n, A, lda, regs_host, num_ops, q);
+        return drv_pcg<T>(q, G, n, V, ldv, eigvals, dim_pre, mus, H, X, s, tol, max_iters, iters, hist);
+    });
+}
+template <typename T>
+int drv_pcg_rbf(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, T bandwidth, const T* regs_host, int64_t num_ops, const T* V,
+                int64_t ldv, const T* eigvals, int64_t dim_pre, const T* H, T* X, int64_t s, T tol, int64_t max_iters, int64_t* iters, T* hist) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (!regs_host || num_ops < 1) throw RandLAPACK::Error("pcg: regs_host must hold num_ops >= 1 regularization parameters");
+        std::vector<T> mus(regs_host, regs_host + num_ops);
+        lo::RBFKernelMatrix<T> G(n, X_pts, rows_x, bandwidth, mus, q, ldx);
+        return drv_pcg<T>(q, G, n, V, ldv, eigvals, dim_pre, mus, H, X, s, tol, max_iters, iters, hist);
+    });
+}
+template <typename T>
+int drv_krill_rbf(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, T bandwidth, const T* regs_host, int64_t num_ops, const T* H,
+                  T* X, int64_t s, T tol, int64_t max_iters, int64_t* k, int64_t b, uint32_t state[6], int64_t* iters, T* hist) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (!regs_host || num_ops < 1) throw RandLAPACK::Error("krill: regs_host must hold num_ops >= 1 regularization parameters");
+        if (!k || !state) throw RandLAPACK::Error("krill: k and state must not be null");
+        std::vector<T> mus(regs_host, regs_host + num_ops);
+        lo::RBFKernelMatrix<T> G(n, X_pts, rows_x, bandwidth, mus, q, ldx);
+        RandLAPACK::StatefulFrobeniusNorm<T> sn(q);
+        State st = load_state(state);
+        int64_t it = 0, kk = *k;
+        st = RandLAPACK::krill_full_rpchol(n, G, s, H, X, tol, st, sn, b, max_iters, *k, false, &it, &kk);
+        store_state(st, state);
+        *k = kk;
+        if (iters) *iters = it;
+        store_hist(sn, max_iters, hist);
+        return 0;
+    });
+}
+template <typename T>
+int drv_posm_square(rlhip_ctx* ctx, int64_t s, const T* LHS, T* RHS, int diag_only, int64_t* code) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (s < 1 || !LHS || !RHS || !code) throw RandLAPACK::Error("posm_square: s must be >= 1 and LHS, RHS, code not null");
+        blas::Scratch ws(q);
+        T* work = ws.alloc<T>(s * s + 2);
+        *code = RandLAPACK::posm_square(s, LHS, RHS, work, q, diag_only != 0);
+        q.sync();
+        return 0;
+    });
+}
+}  // namespace
+
+extern "C" {
+#define RLHIP_DEFINE_PCG_DRIVERS(SUF, T)                                                                                                          \
+    int rlhip_drv_pcg_dense_##SUF(rlhip_ctx* ctx, int64_t n, const T* A, int64_t lda, const T* regs_host, int64_t num_ops, const T* V, int64_t ldv, \
+                                  const T* eigvals, int64_t dim_pre, const T* H, T* X, int64_t s, T tol, int64_t max_iters, int64_t* iters,       \
+                                  T* hist) {                                                                                                      \
+        return drv_pcg_dense<T>(ctx, n, A, lda, regs_host, num_ops, V, ldv, eigvals, dim_pre, H, X, s, tol, max_iters, iters, hist);              \
+    }                                                                                                                                             \
+    int rlhip_drv_pcg_rbf_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, T bandwidth, const T* regs_host,          \
+                                int64_t num_ops, const T* V, int64_t ldv, const T* eigvals, int64_t dim_pre, const T* H, T* X, int64_t s, T tol,  \
+                                int64_t max_iters, int64_t* iters, T* hist) {                                                                     \
+        return drv_pcg_rbf<T>(ctx, X_pts, ldx, rows_x, n, bandwidth, regs_host, num_ops, V, ldv, eigvals, dim_pre, H, X, s, tol, max_iters,       \
+                              iters, hist);                                                                                                       \
+    }                                                                                                                                             \
+    int rlhip_drv_krill_full_rpchol_rbf_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, T bandwidth,                \
+                                              const T* regs_host, int64_t num_ops, const T* H, T* X, int64_t s, T tol, int64_t max_iters,         \
+                                              int64_t* k, int64_t b, uint32_t state[6], int64_t* iters, T* hist) {                                \
+        return drv_krill_rbf<T>(ctx, X_pts, ldx, rows_x, n, bandwidth, regs_host, num_ops, H, X, s, tol, max_iters, k, b, state, iters, hist);    \
+    }                                                                                                                                             \
+    int rlhip_drv_posm_square_##SUF(rlhip_ctx* ctx, int64_t s, const T* LHS, T* RHS, int diag_only, int64_t* code) {                              \
+        return drv_posm_square<T>(ctx, s, LHS, RHS, diag_only, code);                                                                             \
+    }
+RLHIP_DEFINE_PCG_DRIVERS(f64, double)
+RLHIP_DEFINE_PCG_DRIVERS(f32, float)
+}  // extern "C"

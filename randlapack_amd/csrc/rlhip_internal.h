@@ -162,6 +162,9 @@ struct rlhip_ctx {
     //   0 stream-K f64 GEMM, 1 stream-K f32 GEMM, 2 fused trsm block kernel, 3 substitution trsm sub-block, 4 fused out-of-place trsm
     //   (rlhip_trsm_gather), 5 sketch-preconditioned Cholesky-QR panel inside geqrf -- the list in include/rlhip.h is the contract
     int64_t path_count[RLHIP_NPATH] = {};
+    // the routes of the PCG update kernels (pcg.hip), read through rlhip_pcg_path_count: [0] = 43 fused update_xr, [1] = 44 fused update_p,
+    // [2] = 45 either one composed from products
+    int64_t pcg_path_count[3] = {};
 };
 
 // every host wait of the library goes through here: the epoch lets deferred read-backs know that an earlier wait already covered them

@@ -190,6 +190,10 @@ class Context:
     def path_count(self, which: int) -> int:
         return int(self.lib.rlhip_path_count(self.h, which))
 
+    def pcg_path_count(self, which: int) -> int:
+        """routes of the PCG update kernels: 43 fused update_xr, 44 fused update_p, 45 composed (include/rlhip.h rlhip_pcg_path_count)"""
+        return int(self.lib.rlhip_pcg_path_count(self.h, which))
+
     # ---- options (include/rlhip.h: enum rlhip_option; -1 restores the default)
     OPT = dict(cholqrq_one_stream=0, gesdd_gram=1, jacobi_persist=2, trsm_xasm=3, saso_mode=4, hqrrp_tall_panel=5,
                bqrrp_lookahead_min_elems=6, bqrrp_cholqr_fallback=7, cqrrpt_fold_pivoting=8, cqrrpt_split_qrcp=9, sparse_sketch_densify=10, jacobi_clock_holders=11)
@@ -854,3 +858,110 @@ def rpchol_pc_data(ctx: Context, X, rows_x, n, bandwidth, k, b, reg=0.0, ctr=(0,
     _drv_check(ctx, rc, "rpchol_pc_data")
     kf = int(kk.value)
     return dict(V=V[:kf], eigvals=ev[:kf], k=kf, next_ctr=tuple(int(x) for x in st[:4]))
+
+
+# ---- block / lockstep PCG, the spectral preconditioner and KRILL (pcg.hip; include/RandLAPACK_amd/rl_determiter.hh, rl_krill.hh).
+#      Blocks are column-major tensors (s, ld) as everywhere in this module; s x s matrices are (s, s) tensors with ld s.
+def _ldc(t):
+    """leading dimension of a column-major block (cols, ld): a one-column block says nothing through its strides, its row length does"""
+    return int(t.shape[1]) if t.dim() == 2 and t.shape[0] == 1 else _ld(t)
+
+
+def posm_square(ctx: Context, LHS, RHS, diag_only=False, host_fallback=False):
+    """RHS <- LHS^-1 RHS in place for the s x s pair.  host_fallback False: the device attempt alone, returns its status (s, or -1 with both
+    matrices untouched).  True: the C++ posm_square (eigenvalue fallback on the host after a failed pivot), returns the rank or -(s+1) / -(s+2)."""
+    torch = _torch()
+    suf, _ = _suf(LHS)
+    s = int(LHS.shape[0])
+    if host_fallback:
+        code = C.c_int64(0)
+        rc = getattr(ctx.lib, f"rlhip_drv_posm_square_{suf}")(ctx.h, s, LHS.data_ptr(), RHS.data_ptr(), 1 if diag_only else 0, C.byref(code))
+        _drv_check(ctx, rc, "posm_square")
+        return int(code.value)
+    st = torch.zeros(1, dtype=torch.int64, device=LHS.device)
+    _lib.check(getattr(ctx.lib, f"rlhip_posm_square_{suf}")(ctx.h, s, LHS.data_ptr(), RHS.data_ptr(), 1 if diag_only else 0, st.data_ptr()),
+               "posm_square")
+    return int(st.item())
+
+
+def pcg_update_xr(ctx: Context, n, s, alpha, P, GP, X, R, want_norms=True):
+    """X += P alpha, R -= GP alpha in place; returns the squared column norms of the new R (float64 tensor, s) or None"""
+    torch = _torch()
+    suf, _ = _suf(P)
+    cn = torch.zeros(s, dtype=torch.float64, device=P.device) if want_norms else None
+    rc = getattr(ctx.lib, f"rlhip_pcg_update_xr_{suf}")(ctx.h, n, s, alpha.data_ptr(), P.data_ptr(), _ldc(P), GP.data_ptr(), _ldc(GP), X.data_ptr(), _ldc(X),
+                                                       R.data_ptr(), _ldc(R), None if cn is None else cn.data_ptr())
+    _lib.check(rc, "pcg_update_xr")
+    return cn
+
+
+def pcg_update_p(ctx: Context, n, s, beta, NR, P):
+    """P <- NR + P beta in place"""
+    suf, _ = _suf(P)
+    _lib.check(getattr(ctx.lib, f"rlhip_pcg_update_p_{suf}")(ctx.h, n, s, beta.data_ptr(), NR.data_ptr(), _ldc(NR), P.data_ptr(), _ldc(P)), "pcg_update_p")
+    return P
+
+
+def spectral_precond_apply(ctx: Context, V, D, B, dim, n, alpha=1.0, beta=0.0, C_=None, want_norms=True):
+    """C = alpha (V diag(D_j) V^T + I) B + beta C.  V (dim_pre, ldv), D (num_ops, dim_pre), B (n, ldb), C_ (n, ldc) column-major.
+    Returns (C, squared column norms of C as a float64 tensor or None)."""
+    torch = _torch()
+    suf, _ = _suf(V)
+    dim_pre, num_ops = int(V.shape[0]), int(D.shape[0])
+    if C_ is None:
+        C_ = torch.zeros((n, dim), dtype=V.dtype, device=V.device)
+    W = torch.empty((n, max(dim_pre, 1)), dtype=V.dtype, device=V.device)
+    cn = torch.zeros(n, dtype=torch.float64, device=V.device) if want_norms else None
+    rc = getattr(ctx.lib, f"rlhip_spectral_precond_apply_{suf}")(ctx.h, dim, dim_pre, V.data_ptr(), _ldc(V), D.data_ptr(), num_ops, n, alpha, B.data_ptr(),
+                                                                _ldc(B), beta, C_.data_ptr(), _ldc(C_), W.data_ptr(), None if cn is None else cn.data_ptr())
+    _lib.check(rc, "spectral_precond_apply")
+    return C_, cn
+
+
+def _pcg_out(X, iters, hist):
+    it = int(iters.value)
+    h = np.array(hist[: 2 * (it + 1)], dtype=np.float64).reshape(-1, 2)
+    h = h[~np.isnan(h[:, 0])]              # (an iteration that ended at its alpha solve recorded no norms)
+    return dict(X=X, iters=it, normR=h[:, 0].copy(), normNR=h[:, 1].copy())
+
+
+def _pcg_args(T, regs, max_iters):
+    rg = (T * len(regs))(*regs)
+    hist = (T * (2 * (max_iters + 1)))(*([float("nan")] * (2 * (max_iters + 1))))
+    return rg, hist, C.c_int64(0)
+
+
+def pcg_dense(ctx: Context, A, n, regs, V, eigvals, H, X, s, tol, max_iters):
+    """pcg on (A + mu_i I) X = H with the spectral preconditioner from (V, eigvals); A (n, lda) column-major, its upper triangle is read.  X is the
+    starting point and is overwritten.  Returns dict(X, iters, normR, normNR): the norms of iterations 0 .. iters that were recorded."""
+    suf, T = _suf(A)
+    rg, hist, iters = _pcg_args(T, regs, max_iters)
+    rc = getattr(ctx.lib, f"rlhip_drv_pcg_dense_{suf}")(ctx.h, n, A.data_ptr(), _ldc(A), rg, len(regs), V.data_ptr(), _ldc(V), eigvals.data_ptr(),
+                                                       int(eigvals.numel()), H.data_ptr(), X.data_ptr(), s, tol, max_iters, C.byref(iters), hist)
+    _drv_check(ctx, rc, "pcg_dense")
+    return _pcg_out(X, iters, hist)
+
+
+def pcg_rbf(ctx: Context, Xp, rows_x, n, bandwidth, regs, V, eigvals, H, X, s, tol, max_iters):
+    """pcg_dense over the RBF kernel matrix of the points Xp (column-major (n, rows_x))"""
+    suf, T = _suf(Xp)
+    rg, hist, iters = _pcg_args(T, regs, max_iters)
+    rc = getattr(ctx.lib, f"rlhip_drv_pcg_rbf_{suf}")(ctx.h, Xp.data_ptr(), _ldc(Xp), rows_x, n, bandwidth, rg, len(regs), V.data_ptr(), _ldc(V),
+                                                     eigvals.data_ptr(), int(eigvals.numel()), H.data_ptr(), X.data_ptr(), s, tol, max_iters,
+                                                     C.byref(iters), hist)
+    _drv_check(ctx, rc, "pcg_rbf")
+    return _pcg_out(X, iters, hist)
+
+
+def krill_full_rpchol_rbf(ctx: Context, Xp, rows_x, n, bandwidth, regs, H, X, s, tol, max_iters, k=-1, b=-1, ctr=(0, 0, 0, 0), key=(0, 0)):
+    """krill_full_rpchol on the RBF kernel matrix: dict(X, iters, normR, normNR, k, next_ctr)"""
+    suf, T = _suf(Xp)
+    rg, hist, iters = _pcg_args(T, regs, max_iters)
+    kk = C.c_int64(k)
+    st = _state_arr(ctr, key)
+    rc = getattr(ctx.lib, f"rlhip_drv_krill_full_rpchol_rbf_{suf}")(ctx.h, Xp.data_ptr(), _ldc(Xp), rows_x, n, bandwidth, rg, len(regs), H.data_ptr(),
+                                                                   X.data_ptr(), s, tol, max_iters, C.byref(kk), b, st, C.byref(iters), hist)
+    _drv_check(ctx, rc, "krill_full_rpchol_rbf")
+    out = _pcg_out(X, iters, hist)
+    out.update(k=int(kk.value), next_ctr=tuple(int(x) for x in st[:4]))
+    return out
