@@ -1,6 +1,17 @@
-// Block / lockstep preconditioned conjugate gradients on the device (RandLAPACK/comps/rl_determiter.hh:140-526): StatefulFrobeniusNorm,
-// posm_square and pcg.  pcg_saddle (:23-137) is not built.
+// The deterministic iterative solvers on the device (RandLAPACK/comps/rl_determiter.hh): pcg_saddle (:18-134), and block / lockstep
+// preconditioned conjugate gradients (:140-526): StatefulFrobeniusNorm, posm_square and pcg.
 //
+// pcg_saddle: the loop is the reference's, statement by statement (line numbers at the right), with these differences:
+//   - every vector (b, c, resid_vec, x0, x, y) and both matrices are DEVICE arrays on q; alpha, beta and delta_1 never leave the device;
+//   - one host read per iteration: the sizeof(T) bytes of resid_vec[iter], for the stop test delta_1 > (delta_1^0 tol) tol;
+//   - q = A^T (A d) + delta d and d^T q come from rlhip_normal_matvec_* (one pass over A for n within its limit), M^T r, M (.), A^T b and
+//     y = b - A x from rlhip_gemv_*, the n-length updates from rlhip_pcg_saddle_step_*;
+//   - the residual refresh on iter % 25 == 1 runs the normal matvec on x;
+//   - resid_vec must hold iter_lim + 1 entries: the reference writes resid_vec[iter] after the loop (:127), one past its documented
+//     length (:28) when the limit is reached;
+//   - a trailing `int64_t* iters` (optional) returns the number of iterations run.
+//
+// pcg:
 // Everything n x s and s x s lives in device memory on G.q; the loop is the reference's, statement by statement (line numbers at the right),
 // with these differences:
 //   - H, X and the block handed to `seminorm` are DEVICE arrays;
@@ -28,6 +39,99 @@
 #include "rl_determiter_host.hh"
 
 namespace RandLAPACK {
+
+namespace _saddle_impl {
+
+inline int gemv(blas::Queue& q, Op t, int64_t m, int64_t n, double al, const double* A, int64_t lda, const double* x, double be, double* y) { return rlhip_gemv_f64(q.ctx(), (char)t, m, n, al, A, lda, x, be, y); }
+inline int gemv(blas::Queue& q, Op t, int64_t m, int64_t n, float al, const float* A, int64_t lda, const float* x, float be, float* y) { return rlhip_gemv_f32(q.ctx(), (char)t, m, n, al, A, lda, x, be, y); }
+inline int normal_matvec(blas::Queue& q, int64_t m, int64_t n, const double* A, int64_t lda, const double* d, double delta, double* out, double* t, double* dq) {
+    return rlhip_normal_matvec_f64(q.ctx(), m, n, A, lda, d, delta, out, t, dq, 0);
+}
+inline int normal_matvec(blas::Queue& q, int64_t m, int64_t n, const float* A, int64_t lda, const float* d, float delta, float* out, float* t, float* dq) {
+    return rlhip_normal_matvec_f32(q.ctx(), m, n, A, lda, d, delta, out, t, dq, 0);
+}
+inline int step_xr(blas::Queue& q, int64_t n, const double* d, const double* qv, const double* dq, const double* d1, double* x, double* r) { return rlhip_pcg_saddle_step_xr_f64(q.ctx(), n, d, qv, dq, d1, x, r); }
+inline int step_xr(blas::Queue& q, int64_t n, const float* d, const float* qv, const float* dq, const float* d1, float* x, float* r) { return rlhip_pcg_saddle_step_xr_f32(q.ctx(), n, d, qv, dq, d1, x, r); }
+inline int step_refresh(blas::Queue& q, int64_t n, const double* b1, const double* qx, double delta, const double* x, double* r) { return rlhip_pcg_saddle_step_refresh_f64(q.ctx(), n, b1, qx, delta, x, r); }
+inline int step_refresh(blas::Queue& q, int64_t n, const float* b1, const float* qx, float delta, const float* x, float* r) { return rlhip_pcg_saddle_step_refresh_f32(q.ctx(), n, b1, qx, delta, x, r); }
+inline int step_d(blas::Queue& q, int64_t n, const double* r, const double* s, const double* d1o, double* d1n, double* d) { return rlhip_pcg_saddle_step_d_f64(q.ctx(), n, r, s, d1o, d1n, d); }
+inline int step_d(blas::Queue& q, int64_t n, const float* r, const float* s, const float* d1o, float* d1n, float* d) { return rlhip_pcg_saddle_step_d_f32(q.ctx(), n, r, s, d1o, d1n, d); }
+inline int axpby(blas::Queue& q, int64_t n, double a, const double* x, double b, double* y) { return rlhip_axpby_f64(q.ctx(), n, a, x, b, y); }
+inline int axpby(blas::Queue& q, int64_t n, float a, const float* x, float b, float* y) { return rlhip_axpby_f32(q.ctx(), n, a, x, b, y); }
+
+}  // namespace _saddle_impl
+
+/// Solves the saddle point problem (A'A + delta I) x = A'b - c by conjugate gradients preconditioned with M M' (M: n x k, ldm), then
+/// y = b - A x.  A: m x n (lda); b, y: m; c, x0, x: n; resid_vec: iter_lim + 1 -- all DEVICE, column-major.  resid_vec[i] receives
+/// delta_1 = r' M M' r at the start of iteration i and, after the loop, of the iteration that was not run; iterations stop when
+/// delta_1 <= (delta_1^0 tol) tol or after iter_lim.                                                                rl_determiter.hh:18-134
+template <typename T>
+void pcg_saddle(int64_t m, int64_t n, const T* A, int64_t lda, const T* b, const T* c, T delta, int64_t iter_lim, T* resid_vec, T tol, int64_t k,
+                const T* M, int64_t ldm, const T* x0, T* x, T* y, blas::Queue& q = blas::default_queue(), int64_t* iters = nullptr) {
+    namespace si = _saddle_impl;
+    randlapack_require(m >= 1 && n >= 1 && k >= 1) << "pcg_saddle needs m=" << m << ", n=" << n << ", k=" << k << " >= 1";
+    randlapack_require(iter_lim >= 0) << "iter_lim=" << iter_lim << " must be >= 0";
+    if (iters) *iters = 0;
+
+    blas::Scratch ws(q);                                                                                                            // :38-46
+    T* allwork = ws.alloc<T>(m + 5 * n + k + 1);
+    T* out_a1 = allwork;
+    T* out_at1 = out_a1 + m;
+    T* r = out_at1 + n;
+    T* d = r + n;
+    T* b1 = d + n;
+    T* out_m1 = b1 + n;
+    T* out_mt1 = out_m1 + n;
+    T* dq = out_mt1 + k;                                                         // d' q of the current iteration
+
+    //  b1 = A'b - c
+    blas::copy(n, c, 1, b1, 1, q);                                                                                                  // :49
+    blas::check(si::gemv(q, Op::Trans, m, n, (T)1.0, A, lda, b, (T)-1.0, b1), "gemv");                                              // :50
+
+    // r = b1 - (A'(A x0) + delta x0)
+    blas::copy(n, b1, 1, r, 1, q);                                                                                                  // :57
+    blas::check(si::normal_matvec(q, m, n, A, lda, x0, delta, out_at1, (T*)nullptr, (T*)nullptr), "normal_matvec");                 // :58-60
+    blas::check(si::axpby(q, n, (T)-1.0, out_at1, (T)1.0, r), "axpby");                                                             // :61
+
+    // d = M (M' r)
+    blas::check(si::gemv(q, Op::Trans, n, k, (T)1.0, M, ldm, r, (T)0.0, out_mt1), "gemv");                                          // :64
+    blas::check(si::gemv(q, Op::NoTrans, n, k, (T)1.0, M, ldm, out_mt1, (T)0.0, d), "gemv");                                        // :65
+
+    blas::copy(n, x0, 1, x, 1, q);                                                                                                  // :68
+    blas::check(si::step_d(q, n, r, d, (const T*)nullptr, resid_vec, (T*)nullptr), "pcg_saddle_step_d");   // resid_vec[0] = d' r       :69
+    T delta1_new = 0;
+    blas::copy_to_host(1, resid_vec, &delta1_new, q);
+    T rel_sq_tol = (delta1_new * tol) * tol;                                                                                        // :71
+
+    int64_t iter = 0;
+    while (iter < iter_lim && delta1_new > rel_sq_tol) {                                                                            // :76
+        // (resid_vec[iter] = delta1_new: written by the step that computed it)                                                     :77
+        // q = A'(A d) + delta d, and d' q
+        blas::check(si::normal_matvec(q, m, n, A, lda, d, delta, out_at1, (T*)nullptr, dq), "normal_matvec");                       // :81-83, 86
+        const bool refresh = iter % 25 == 1;                                                                                        // :92
+        // alpha = delta1_new / (d' q); x += alpha d; r -= alpha q unless r is recomputed
+        blas::check(si::step_xr(q, n, d, refresh ? (const T*)nullptr : out_at1, dq, resid_vec + iter, x, r), "pcg_saddle_step_xr"); // :86, 89, 106
+        if (refresh) {
+            // r = b1 - (A'(A x) + delta x)
+            blas::check(si::normal_matvec(q, m, n, A, lda, x, (T)0.0, out_at1, (T*)nullptr, (T*)nullptr), "normal_matvec");         // :99-100
+            blas::check(si::step_refresh(q, n, b1, out_at1, delta, x, r), "pcg_saddle_step_refresh");                               // :101-103
+        }
+        // s = M (M' r)
+        blas::check(si::gemv(q, Op::Trans, n, k, (T)1.0, M, ldm, r, (T)0.0, out_mt1), "gemv");                                      // :113
+        blas::check(si::gemv(q, Op::NoTrans, n, k, (T)1.0, M, ldm, out_mt1, (T)0.0, out_m1), "gemv");                               // :114
+        // scalars and update d: resid_vec[iter + 1] = r' s, beta = that / resid_vec[iter], d = beta d + s
+        blas::check(si::step_d(q, n, r, out_m1, resid_vec + iter, resid_vec + iter + 1, d), "pcg_saddle_step_d");                   // :117-122
+        ++iter;                                                                                                                     // :124
+        blas::copy_to_host(1, resid_vec + iter, &delta1_new, q);                 // the iteration's one host read
+    }
+    // (resid_vec[iter] = delta1_new, :127: already there)
+    if (iters) *iters = iter;
+
+    // recover y = b - Ax
+    blas::copy(m, b, 1, y, 1, q);                                                                                                   // :130
+    blas::check(si::gemv(q, Op::NoTrans, m, n, (T)-1.0, A, lda, x, (T)1.0, y), "gemv");                                             // :131
+    q.sync();                                    // (the work space goes back to the arena)
+}
 
 /// The Frobenius norm of a DEVICE block, every value kept (rl_determiter.hh:139-151).  pcg recognises this type and fills `history` from the
 /// sums its kernels return instead of calling it.

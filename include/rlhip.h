@@ -61,7 +61,8 @@ enum rlhip_option {
     RLHIP_OPT_DRV_CQRRPT_SPLIT_QRCP = 9,           /* CQRRPT::split_qrcp (default 1) */
     RLHIP_OPT_DRV_SPARSE_SKETCH_DENSIFY = 10,      /* linops::SparseLinOp::force_densified_sketch (default 0) */
     RLHIP_OPT_JACOBI_CLOCK_HOLDERS = 11,           /* persistent Jacobi: 1 (default) the CUs its workers leave idle run FMA-burning holder workgroups so that DVFS keeps the clock up for the next GEMM (never on a context that shares the device with another stream); 0: the workers alone */
-    RLHIP_OPT_COUNT = 12
+    RLHIP_OPT_LSQ_NORMAL_FUSED = 12,               /* rlhip_normal_matvec_*: 1 the one-pass kernel wherever n is within its limit, 0 always the two rlhip_gemv calls; default: one pass up to the widths at which it measured faster */
+    RLHIP_OPT_COUNT = 13
 };
 int rlhip_set_option(rlhip_ctx* ctx, int option, int64_t value);     /* -1 (bad context / option) or 0 */
 int64_t rlhip_get_option(rlhip_ctx* ctx, int option);                /* the stored value (-1 = default), INT64_MIN for a bad option */
@@ -506,6 +507,68 @@ int rlhip_spectral_precond_apply_f32(rlhip_ctx* ctx, int64_t dim, int64_t dim_pr
  * the composed route (s > 64).  They continue the numbering of rlhip_path_count below but are read here: that function's range ends at 42
  * and answers -1 beyond it.  -1 for any other index. */
 int64_t rlhip_pcg_path_count(rlhip_ctx* ctx, int which);
+
+/* ---- matrix-vector layer and the vector steps of pcg_saddle (lsq.hip; reference RandLAPACK/comps/rl_determiter.hh:18-134; the loop is
+ *      include/RandLAPACK_amd/rl_determiter.hh).  Column-major, all arrays DEVICE, everything asynchronous.  No kernel waits for another
+ *      workgroup and none uses a floating-point atomic: a sum over rows goes through one partial per workgroup and column in the scratch
+ *      arena (G x n values for a grid of G workgroups, never proportional to m) and a final pass that adds the partials in a fixed order, so
+ *      results are bitwise reproducible from run to run on one device.  Sums are taken in the precision of the data.  Rows m .. lda-1 of A
+ *      are never read, and nothing beyond the stated length of an output vector is written. ---- */
+/* rlhip_gemv_*: y = alpha op(A) x + beta y, A m x n, trans 'N' or 'T' (blas::gemv(ColMajor, ...) with unit strides, rl_determiter.hh:50,
+ * 58-59, 64-65, 81-82, 99-100, 113-114, 131).  beta == 0 does not read y.  m == 0 or n == 0 returns 0 and writes nothing (BLAS's quick return);
+ * alpha == 0 scales y without reading A or x.  'N': a workgroup owns 64 rows, its four waves a quarter of the columns each, added in wave
+ * order.  'T': a fixed grid whose workgroups walk 512-row slabs s, s + G, ...; a wave owns every fourth column and keeps the running sums
+ * of its columns in LDS; one partial per workgroup and column, then the final pass.
+ * Argument codes, checked before anything is enqueued: -2 trans, -3 m < 0, -4 n < 0, -6 A NULL, -7 lda < max(1, m), -8 x NULL, -10 y NULL
+ * (the pointer codes only when m > 0 and n > 0). */
+int rlhip_gemv_f64(rlhip_ctx* ctx, char trans, int64_t m, int64_t n, double alpha, const double* A, int64_t lda, const double* x, double beta,
+                   double* y);
+int rlhip_gemv_f32(rlhip_ctx* ctx, char trans, int64_t m, int64_t n, float alpha, const float* A, int64_t lda, const float* x, float beta,
+                   float* y);
+/* rlhip_normal_matvec_*: q = A^T (A d) + delta d (the two gemv calls and the axpy at rl_determiter.hh:58-60, 81-83, 99-100).  Optional
+ * outputs, each may be NULL: t = A d (m values) and *dq_dev = d^T q (rl_determiter.hh:86's dot, taken in a fixed order by one workgroup).
+ * Fused route, n <= RLHIP_NORMAL_FUSED_MAX_N_F64 / _F32: A is read from memory ONCE.  A fixed grid of G = min(max_wg, slabs) workgroups of
+ * 1024 threads (max_wg <= 0: one per CU); workgroup s walks the R-row slabs s, s + G, ...: the slab (R x n) is staged in LDS (columns padded
+ * to R + 1 against bank conflicts) while t is formed for its R rows, then the workgroup's partial q is advanced from the staged copy while
+ * the next slab is already on its way into registers; after its last slab the workgroup writes its n partial sums, and the final pass adds
+ * the G partials in order and adds delta d.  R is the largest power of two between 16 and 256 rows with R n sizeof(T) <= 128 KiB, which
+ * sets the limits below (16 rows: a 128-B column segment in fp64).  Composed route (wider n): rlhip_gemv 'N' into t (or scratch) and
+ * rlhip_gemv 'T'; two passes over A.
+ * The route: unasked, the one-pass kernel serves n <= RLHIP_NORMAL_FUSED_DEFAULT_MAX_N_F64 / _F32 -- the widths at which it measured faster
+ * than the composed route (in fp32 a 16-row column segment is half a 128-B line and the one-pass kernel loses from n = 1024 on);
+ * RLHIP_OPT_LSQ_NORMAL_FUSED = 1 takes it wherever n is within the kernel's limit, 0 never.
+ * m == 0: q = delta d.  n == 0: returns 0 and writes nothing.
+ * Argument codes: -2 m < 0, -3 n < 0, -4 A NULL (m, n > 0), -5 lda < max(1, m), -6 d NULL, -8 q NULL (both n > 0). */
+#define RLHIP_NORMAL_FUSED_MAX_N_F64 1024
+#define RLHIP_NORMAL_FUSED_MAX_N_F32 2048
+#define RLHIP_NORMAL_FUSED_DEFAULT_MAX_N_F64 1024
+#define RLHIP_NORMAL_FUSED_DEFAULT_MAX_N_F32 256
+int rlhip_normal_matvec_f64(rlhip_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda, const double* d, double delta, double* q,
+                            double* t, double* dq_dev, int64_t max_wg);
+int rlhip_normal_matvec_f32(rlhip_ctx* ctx, int64_t m, int64_t n, const float* A, int64_t lda, const float* d, float delta, float* q, float* t,
+                            float* dq_dev, int64_t max_wg);
+/* The n-length vector steps of one pcg_saddle iteration, every scalar kept on the device (one workgroup each).
+ * rlhip_pcg_saddle_step_xr_*: alpha = *delta1_dev / *dq_dev, x += alpha d, r -= alpha q (rl_determiter.hh:86, 89, 106); q == NULL leaves r
+ *   alone (the iterations whose residual is recomputed).  Codes: -2 n < 0, -3 d, -5 dq_dev, -6 delta1_dev, -7 x NULL; -8 r NULL with q given.
+ * rlhip_pcg_saddle_step_refresh_*: r = (b1 - qx) - delta x, the last term only when delta > 0 (rl_determiter.hh:101-103).
+ *   Codes: -2 n < 0, -3 b1, -4 qx, -6 x, -7 r NULL.
+ * rlhip_pcg_saddle_step_d_*: *delta1_new_dev = r^T s (fixed order), beta = that / *delta1_old_dev, d = beta d + s (rl_determiter.hh:117-122);
+ *   delta1_old_dev == NULL: the dot alone (rl_determiter.hh:69), d is not touched.  The loop passes resid_vec + iter and resid_vec + iter + 1.
+ *   Codes: -2 n < 0, -3 r, -4 s, -6 delta1_new_dev NULL; -7 d NULL with delta1_old_dev given.
+ * n == 0: each returns 0 and enqueues nothing. */
+int rlhip_pcg_saddle_step_xr_f64(rlhip_ctx* ctx, int64_t n, const double* d, const double* q, const double* dq_dev, const double* delta1_dev,
+                                 double* x, double* r);
+int rlhip_pcg_saddle_step_xr_f32(rlhip_ctx* ctx, int64_t n, const float* d, const float* q, const float* dq_dev, const float* delta1_dev, float* x,
+                                 float* r);
+int rlhip_pcg_saddle_step_refresh_f64(rlhip_ctx* ctx, int64_t n, const double* b1, const double* qx, double delta, const double* x, double* r);
+int rlhip_pcg_saddle_step_refresh_f32(rlhip_ctx* ctx, int64_t n, const float* b1, const float* qx, float delta, const float* x, float* r);
+int rlhip_pcg_saddle_step_d_f64(rlhip_ctx* ctx, int64_t n, const double* r, const double* s, const double* delta1_old_dev, double* delta1_new_dev,
+                                double* d);
+int rlhip_pcg_saddle_step_d_f32(rlhip_ctx* ctx, int64_t n, const float* r, const float* s, const float* delta1_old_dev, float* delta1_new_dev,
+                                float* d);
+/* The routes of this layer, one count per call: 46 a fused rlhip_normal_matvec, 47 a composed one (its two rlhip_gemv calls count as
+ * well), 48 rlhip_gemv 'N', 49 rlhip_gemv 'T' (calls that launch nothing are not counted).  -1 for any other index. */
+int64_t rlhip_lsq_path_count(rlhip_ctx* ctx, int which);
 
 /* ---- row-block sharding across the GPUs of a node (new design; the reference has no
  *      distributed code).  One process per GPU.  Sum all-reduces run on the context's stream through RCCL

@@ -261,6 +261,36 @@ int rlhip_drv_krill_full_rpchol_rbf_f32(rlhip_ctx* ctx, const float* X_pts, int6
 int rlhip_drv_posm_square_f64(rlhip_ctx* ctx, int64_t s, const double* LHS, double* RHS, int diag_only, int64_t* code);
 int rlhip_drv_posm_square_f32(rlhip_ctx* ctx, int64_t s, const float* LHS, float* RHS, int diag_only, int64_t* code);
 
+/* pcg_saddle (comps/rl_determiter.hh:18-134; include/RandLAPACK_amd/rl_determiter.hh): (A'A + delta I) x = A'b - c by conjugate gradients
+ * preconditioned with M M', then y = b - A x.  A: m x n (lda); M: n x k (ldm); b, y: m; c, x0, x: n; resid_vec: iter_lim + 1 -- all DEVICE.
+ * *iters (may be NULL) = iterations run; resid_vec[0 .. *iters] are written.  -100 with rlhip_last_error() on a refused argument. */
+int rlhip_drv_pcg_saddle_f64(rlhip_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda, const double* b, const double* c, double delta,
+                             int64_t iter_lim, double* resid_vec, double tol, int64_t k, const double* M, int64_t ldm, const double* x0, double* x,
+                             double* y, int64_t* iters);
+int rlhip_drv_pcg_saddle_f32(rlhip_ctx* ctx, int64_t m, int64_t n, const float* A, int64_t lda, const float* b, const float* c, float delta,
+                             int64_t iter_lim, float* resid_vec, float tol, int64_t k, const float* M, int64_t ldm, const float* x0, float* x,
+                             float* y, int64_t* iters);
+/* rpc_data_svd_saso (comps/rl_preconditioners.hh:135-153; include/RandLAPACK_amd/rl_preconditioners.hh): V_sk (DEVICE, at least d * n entries;
+ * on return its leading n x n, ld n, holds the right singular vectors) and sigma_sk (DEVICE, n) from the SVD of a d x m sparse sign sketch
+ * (nnz nonzeros per column) of A (m x n, lda, DEVICE).  state[6] (counter, key) in, the next state out. */
+int rlhip_drv_rpc_data_svd_saso_f64(rlhip_ctx* ctx, int64_t m, int64_t n, int64_t d, int64_t nnz, const double* A, int64_t lda, double* V_sk,
+                                    double* sigma_sk, uint32_t state[6]);
+int rlhip_drv_rpc_data_svd_saso_f32(rlhip_ctx* ctx, int64_t m, int64_t n, int64_t d, int64_t nnz, const float* A, int64_t lda, float* V_sk,
+                                    float* sigma_sk, uint32_t state[6]);
+/* make_right_orthogonalizer (comps/rl_preconditioners.hh:193-224): scales the first *rank columns of V (n x n, ld n, DEVICE) by
+ * 1 / sqrt(sigma_i^2 + mu); sigma: DEVICE; cols_V < 0 means n.  *rank receives the number of columns that define the orthogonalizer. */
+int rlhip_drv_make_right_orthogonalizer_f64(rlhip_ctx* ctx, int64_t n, double* V, const double* sigma, double mu, int64_t cols_V, int64_t* rank);
+int rlhip_drv_make_right_orthogonalizer_f32(rlhip_ctx* ctx, int64_t n, float* V, const float* sigma, float mu, int64_t cols_V, int64_t* rank);
+/* sap_lstsq (include/RandLAPACK_amd/rl_lstsq.hh; no reference counterpart): the two calls above with d = ceil(d_factor n) and mu = delta, then
+ * pcg_saddle from x0 = 0.  x (n), y (m), resid_vec (iter_lim + 1, may be NULL): DEVICE.  state[6] is advanced as rlhip_drv_rpc_data_svd_saso_*
+ * advances it.  *rank and *iters (each may be NULL) receive the orthogonalizer's column count and the iterations run. */
+int rlhip_drv_sap_lstsq_f64(rlhip_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda, const double* b, const double* c, double delta,
+                            double d_factor, int64_t nnz, double tol, int64_t iter_lim, double* x, double* y, double* resid_vec, uint32_t state[6],
+                            int64_t* rank, int64_t* iters);
+int rlhip_drv_sap_lstsq_f32(rlhip_ctx* ctx, int64_t m, int64_t n, const float* A, int64_t lda, const float* b, const float* c, float delta,
+                            float d_factor, int64_t nnz, float tol, int64_t iter_lim, float* x, float* y, float* resid_vec, uint32_t state[6],
+                            int64_t* rank, int64_t* iters);
+
 #ifdef __cplusplus
 }
 #endif

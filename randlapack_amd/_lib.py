@@ -241,6 +241,22 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # block / lockstep PCG, t
         f"rlhip_drv_posm_square_{_suf}": (c_int, [c_vp, c_i64, c_vp, c_vp, c_int, i64p]),
     })
 
+SIGNATURES["rlhip_lsq_path_count"] = (c_i64, [c_vp, c_int])
+for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # matrix-vector layer, pcg_saddle and the sketched least-squares preconditioners (lsq.hip, rl_determiter.hh, rl_preconditioners.hh, rl_lstsq.hh)
+    SIGNATURES.update({
+        f"rlhip_gemv_{_suf}": (c_int, [c_vp, c_char, c_i64, c_i64, _T, c_vp, c_i64, c_vp, _T, c_vp]),
+        f"rlhip_normal_matvec_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, _T, c_vp, c_vp, c_vp, c_i64]),
+        f"rlhip_pcg_saddle_step_xr_{_suf}": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+        f"rlhip_pcg_saddle_step_refresh_{_suf}": (c_int, [c_vp, c_i64, c_vp, c_vp, _T, c_vp, c_vp]),
+        f"rlhip_pcg_saddle_step_d_{_suf}": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+        f"rlhip_drv_pcg_saddle_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, _T, c_i64, c_vp, _T, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                                 i64p]),
+        f"rlhip_drv_rpc_data_svd_saso_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, u32p]),
+        f"rlhip_drv_make_right_orthogonalizer_{_suf}": (c_int, [c_vp, c_i64, c_vp, c_vp, _T, c_i64, i64p]),
+        f"rlhip_drv_sap_lstsq_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, _T, _T, c_i64, _T, c_i64, c_vp, c_vp, c_vp, u32p, i64p,
+                                                i64p]),
+    })
+
 _lib = None
 
 

@@ -897,3 +897,81 @@ extern "C" {
 RLHIP_DEFINE_PCG_DRIVERS(f64, double)
 RLHIP_DEFINE_PCG_DRIVERS(f32, float)
 }  // extern "C"
+
+// ---- sketch-and-precondition least squares (include/RandLAPACK_amd/rl_determiter.hh pcg_saddle, rl_preconditioners.hh, rl_lstsq.hh)
+namespace {
+template <typename T>
+int drv_pcg_saddle(rlhip_ctx* ctx, int64_t m, int64_t n, const T* A, int64_t lda, const T* b, const T* c, T delta, int64_t iter_lim, T* resid_vec,
+                   T tol, int64_t k, const T* M, int64_t ldm, const T* x0, T* x, T* y, int64_t* iters) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (!A || !b || !c || !resid_vec || !M || !x0 || !x || !y) throw RandLAPACK::Error("pcg_saddle: A, b, c, resid_vec, M, x0, x and y must not be null");
+        if (lda < m || ldm < n) throw RandLAPACK::Error("pcg_saddle: lda must be >= m and ldm >= n");
+        if (!(tol > (T)0) || !(delta >= (T)0)) throw RandLAPACK::Error("pcg_saddle: tol must be > 0 and delta >= 0");
+        int64_t it = 0;
+        RandLAPACK::pcg_saddle(m, n, A, lda, b, c, delta, iter_lim, resid_vec, tol, k, M, ldm, x0, x, y, q, &it);
+        if (iters) *iters = it;
+        return 0;
+    });
+}
+template <typename T>
+int drv_rpc_data_svd_saso(rlhip_ctx* ctx, int64_t m, int64_t n, int64_t d, int64_t nnz, const T* A, int64_t lda, T* V_sk, T* sigma_sk, uint32_t state[6]) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (!A || !V_sk || !sigma_sk || !state) throw RandLAPACK::Error("rpc_data_svd_saso: A, V_sk, sigma_sk and state must not be null");
+        if (n < 1 || nnz < 1) throw RandLAPACK::Error("rpc_data_svd_saso: n and nnz must be >= 1");
+        State st = load_state(state);
+        st = RandLAPACK::rpc_data_svd_saso(RandLAPACK::Layout::ColMajor, m, n, d, nnz, A, lda, V_sk, sigma_sk, st, q);
+        store_state(st, state);
+        return 0;
+    });
+}
+template <typename T>
+int drv_make_right_orthogonalizer(rlhip_ctx* ctx, int64_t n, T* V, const T* sigma, T mu, int64_t cols_V, int64_t* rank) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (!V || !sigma || !rank) throw RandLAPACK::Error("make_right_orthogonalizer: V, sigma and rank must not be null");
+        if (!(mu >= (T)0)) throw RandLAPACK::Error("make_right_orthogonalizer: mu must be >= 0");
+        *rank = RandLAPACK::make_right_orthogonalizer(RandLAPACK::Layout::ColMajor, n, V, sigma, mu, cols_V, q);
+        return 0;
+    });
+}
+template <typename T>
+int drv_sap_lstsq(rlhip_ctx* ctx, int64_t m, int64_t n, const T* A, int64_t lda, const T* b, const T* c, T delta, T d_factor, int64_t nnz, T tol,
+                  int64_t iter_lim, T* x, T* y, T* resid_vec, uint32_t state[6], int64_t* rank, int64_t* iters) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (!A || !b || !c || !x || !y || !state) throw RandLAPACK::Error("sap_lstsq: A, b, c, x, y and state must not be null");
+        if (lda < m) throw RandLAPACK::Error("sap_lstsq: lda must be >= m");
+        if (!(tol > (T)0) || !(delta >= (T)0) || nnz < 1) throw RandLAPACK::Error("sap_lstsq: tol must be > 0, delta >= 0 and nnz >= 1");
+        State st = load_state(state);
+        const auto r = RandLAPACK::sap_lstsq(m, n, A, lda, b, c, delta, d_factor, nnz, tol, iter_lim, x, y, st, q, resid_vec);
+        store_state(st, state);
+        if (rank) *rank = r.rank;
+        if (iters) *iters = r.iters;
+        return 0;
+    });
+}
+}  // namespace
+
+extern "C" {
+#define RLHIP_DEFINE_LSQ_DRIVERS(SUF, T)                                                                                                          \
+    int rlhip_drv_pcg_saddle_##SUF(rlhip_ctx* ctx, int64_t m, int64_t n, const T* A, int64_t lda, const T* b, const T* c, T delta, int64_t iter_lim, \
+                                   T* resid_vec, T tol, int64_t k, const T* M, int64_t ldm, const T* x0, T* x, T* y, int64_t* iters) {            \
+        return drv_pcg_saddle<T>(ctx, m, n, A, lda, b, c, delta, iter_lim, resid_vec, tol, k, M, ldm, x0, x, y, iters);                           \
+    }                                                                                                                                             \
+    int rlhip_drv_rpc_data_svd_saso_##SUF(rlhip_ctx* ctx, int64_t m, int64_t n, int64_t d, int64_t nnz, const T* A, int64_t lda, T* V_sk,         \
+                                          T* sigma_sk, uint32_t state[6]) {                                                                       \
+        return drv_rpc_data_svd_saso<T>(ctx, m, n, d, nnz, A, lda, V_sk, sigma_sk, state);                                                        \
+    }                                                                                                                                             \
+    int rlhip_drv_make_right_orthogonalizer_##SUF(rlhip_ctx* ctx, int64_t n, T* V, const T* sigma, T mu, int64_t cols_V, int64_t* rank) {         \
+        return drv_make_right_orthogonalizer<T>(ctx, n, V, sigma, mu, cols_V, rank);                                                              \
+    }                                                                                                                                             \
+    int rlhip_drv_sap_lstsq_##SUF(rlhip_ctx* ctx, int64_t m, int64_t n, const T* A, int64_t lda, const T* b, const T* c, T delta, T d_factor,     \
+                                  int64_t nnz, T tol, int64_t iter_lim, T* x, T* y, T* resid_vec, uint32_t state[6], int64_t* rank,               \
+                                  int64_t* iters) {                                                                                               \
+        return drv_sap_lstsq<T>(ctx, m, n, A, lda, b, c, delta, d_factor, nnz, tol, iter_lim, x, y, resid_vec, state, rank, iters);               \
+    }
+RLHIP_DEFINE_LSQ_DRIVERS(f64, double)
+RLHIP_DEFINE_LSQ_DRIVERS(f32, float)
+}  // extern "C"

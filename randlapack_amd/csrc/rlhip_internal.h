@@ -146,7 +146,7 @@ struct rlhip_ctx {
     // > 0: columns per workgroup of the tag-exchange pivoted QR (default 4; a caller that overlaps the factorization with another kernel packs
     // the columns into fewer workgroups so that it occupies fewer CUs)
     int qrcp_cols_per_wg = 0;
-    int64_t opt[RLHIP_OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // rlhip_set_option; -1 = default
+    int64_t opt[RLHIP_OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // rlhip_set_option; -1 = default
     rlhip_ctx* side_ctx = nullptr;   // cached side context (rlhip_side_of): created on first use, destroyed with this one
     hipStream_t side = nullptr;  // second stream, created on first use (rlhip_dvfs_burn: load beside the main stream's latency-bound kernels)
     // row-sharding communicator (comm.hip), nullptr = single GPU
@@ -165,6 +165,9 @@ struct rlhip_ctx {
     // the routes of the PCG update kernels (pcg.hip), read through rlhip_pcg_path_count: [0] = 43 fused update_xr, [1] = 44 fused update_p,
     // [2] = 45 either one composed from products
     int64_t pcg_path_count[3] = {};
+    // the routes of the matrix-vector layer (lsq.hip), read through rlhip_lsq_path_count: [0] = 46 fused normal matvec, [1] = 47 composed
+    // normal matvec, [2] = 48 gemv 'N', [3] = 49 gemv 'T'
+    int64_t lsq_path_count[4] = {};
 };
 
 // every host wait of the library goes through here: the epoch lets deferred read-backs know that an earlier wait already covered them
@@ -418,5 +421,10 @@ template <typename T>
 int laswp(rlhip_ctx* c, int64_t n, T* A, int64_t lda, int64_t k1, int64_t k2, const int64_t* ipiv_dev);
 // the pivot post-processing of BQRRP's LU-based qrcp_wide
 int luqrcp_piv(rlhip_ctx* c, int64_t sd, int64_t cols, const int64_t* ipiv_dev, int64_t* J_dev);
+
+// ---- lsq.hip
+// y = alpha op(A) x + beta y (trans: NoTrans / Trans); the contract is rlhip_gemv_* in include/rlhip.h
+template <typename T>
+int gemv(rlhip_ctx* c, int trans, int64_t m, int64_t n, T alpha, const T* A, int64_t lda, const T* x, T beta, T* y);
 
 }  // namespace rlhip

@@ -194,9 +194,14 @@ class Context:
         """routes of the PCG update kernels: 43 fused update_xr, 44 fused update_p, 45 composed (include/rlhip.h rlhip_pcg_path_count)"""
         return int(self.lib.rlhip_pcg_path_count(self.h, which))
 
+    def lsq_path_count(self, which: int) -> int:
+        """routes of the matrix-vector layer: 46 fused normal matvec, 47 composed, 48 gemv 'N', 49 gemv 'T' (include/rlhip.h rlhip_lsq_path_count)"""
+        return int(self.lib.rlhip_lsq_path_count(self.h, which))
+
     # ---- options (include/rlhip.h: enum rlhip_option; -1 restores the default)
     OPT = dict(cholqrq_one_stream=0, gesdd_gram=1, jacobi_persist=2, trsm_xasm=3, saso_mode=4, hqrrp_tall_panel=5,
-               bqrrp_lookahead_min_elems=6, bqrrp_cholqr_fallback=7, cqrrpt_fold_pivoting=8, cqrrpt_split_qrcp=9, sparse_sketch_densify=10, jacobi_clock_holders=11)
+               bqrrp_lookahead_min_elems=6, bqrrp_cholqr_fallback=7, cqrrpt_fold_pivoting=8, cqrrpt_split_qrcp=9, sparse_sketch_densify=10, jacobi_clock_holders=11,
+               lsq_normal_fused=12)
 
     def set_option(self, name: str, value: int) -> None:
         _lib.check(self.lib.rlhip_set_option(self.h, self.OPT[name], int(value)), "set_option")
@@ -965,3 +970,86 @@ def krill_full_rpchol_rbf(ctx: Context, Xp, rows_x, n, bandwidth, regs, H, X, s,
     out = _pcg_out(X, iters, hist)
     out.update(k=int(kk.value), next_ctr=tuple(int(x) for x in st[:4]))
     return out
+
+
+# ---- matrix-vector layer, pcg_saddle and the sketched least-squares preconditioners (lsq.hip; include/RandLAPACK_amd/rl_determiter.hh,
+#      rl_preconditioners.hh, rl_lstsq.hh).  A matrix is a column-major tensor (cols, ld) as everywhere in this module, a vector a 1-D tensor
+#      that may be longer than the length in use.
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def gemv(ctx: Context, trans, m, n, alpha, A, x, beta, y, lda=None):
+    """y = alpha op(A) x + beta y in place (rlhip_gemv_*); A (n, lda) column-major"""
+    suf, _ = _suf(y)
+    rc = getattr(ctx.lib, f"rlhip_gemv_{suf}")(ctx.h, trans.encode(), m, n, alpha, _ptr(A), _ldc(A) if lda is None else lda, _ptr(x), beta, _ptr(y))
+    _lib.check(rc, "gemv")
+    return y
+
+
+def normal_matvec(ctx: Context, m, n, A, d, delta, q, t=None, want_dq=False, max_wg=0, lda=None):
+    """q = A^T (A d) + delta d (rlhip_normal_matvec_*); t (optional, m values) receives A d.  Returns d^T q as a one-element device tensor when
+    want_dq, else None."""
+    torch = _torch()
+    suf, _ = _suf(q)
+    dq = torch.zeros(1, dtype=q.dtype, device=q.device) if want_dq else None
+    rc = getattr(ctx.lib, f"rlhip_normal_matvec_{suf}")(ctx.h, m, n, _ptr(A), _ldc(A) if lda is None else lda, _ptr(d), delta, _ptr(q), _ptr(t), _ptr(dq),
+                                                       max_wg)
+    _lib.check(rc, "normal_matvec")
+    return dq
+
+
+def pcg_saddle(ctx: Context, A, m, n, b, c, delta, iter_lim, tol, M, k, x0, lda=None, ldm=None):
+    """pcg_saddle on DEVICE operands: (A'A + delta I) x = A'b - c preconditioned with M M' (M (k, ldm) column-major).
+    Returns dict(x, y, iters, resid (numpy, iters + 1 entries))."""
+    torch = _torch()
+    suf, _ = _suf(A)
+    x = torch.zeros(n, dtype=A.dtype, device=A.device)
+    y = torch.zeros(m, dtype=A.dtype, device=A.device)
+    resid = torch.full((iter_lim + 1,), float("nan"), dtype=A.dtype, device=A.device)
+    iters = C.c_int64(0)
+    rc = getattr(ctx.lib, f"rlhip_drv_pcg_saddle_{suf}")(ctx.h, m, n, A.data_ptr(), _ldc(A) if lda is None else lda, b.data_ptr(), c.data_ptr(), delta,
+                                                        iter_lim, resid.data_ptr(), tol, k, M.data_ptr(), _ldc(M) if ldm is None else ldm,
+                                                        x0.data_ptr(), x.data_ptr(), y.data_ptr(), C.byref(iters))
+    _drv_check(ctx, rc, "pcg_saddle")
+    it = int(iters.value)
+    return dict(x=x, y=y, iters=it, resid=resid[: it + 1].cpu().numpy())
+
+
+def rpc_data_svd_saso(ctx: Context, A, m, n, d, nnz, ctr=(0, 0, 0, 0), key=(0, 0), lda=None):
+    """rpc_data_svd_saso: dict(V (n, n) column-major right singular vectors of the sketch, sigma (n), next_ctr)"""
+    torch = _torch()
+    suf, _ = _suf(A)
+    V_sk = torch.zeros(max(d * n, 1), dtype=A.dtype, device=A.device)
+    sigma = torch.zeros(n, dtype=A.dtype, device=A.device)
+    st = _state_arr(ctr, key)
+    rc = getattr(ctx.lib, f"rlhip_drv_rpc_data_svd_saso_{suf}")(ctx.h, m, n, d, nnz, A.data_ptr(), _ldc(A) if lda is None else lda, V_sk.data_ptr(),
+                                                               sigma.data_ptr(), st)
+    _drv_check(ctx, rc, "rpc_data_svd_saso")
+    return dict(V=V_sk[: n * n].view(n, n), sigma=sigma, next_ctr=tuple(int(v) for v in st[:4]))
+
+
+def make_right_orthogonalizer(ctx: Context, V, sigma, mu, cols_V=-1):
+    """scales the leading columns of V (n, n) in place; returns the rank"""
+    suf, _ = _suf(V)
+    rank = C.c_int64(0)
+    rc = getattr(ctx.lib, f"rlhip_drv_make_right_orthogonalizer_{suf}")(ctx.h, int(V.shape[1]), V.data_ptr(), sigma.data_ptr(), mu, cols_V, C.byref(rank))
+    _drv_check(ctx, rc, "make_right_orthogonalizer")
+    return int(rank.value)
+
+
+def sap_lstsq(ctx: Context, A, m, n, b, c, delta, d_factor, nnz, tol, iter_lim, ctr=(0, 0, 0, 0), key=(0, 0), lda=None):
+    """sap_lstsq: dict(x, y, rank, iters, resid (numpy), next_ctr)"""
+    torch = _torch()
+    suf, _ = _suf(A)
+    x = torch.zeros(n, dtype=A.dtype, device=A.device)
+    y = torch.zeros(m, dtype=A.dtype, device=A.device)
+    resid = torch.full((iter_lim + 1,), float("nan"), dtype=A.dtype, device=A.device)
+    st = _state_arr(ctr, key)
+    rank, iters = C.c_int64(0), C.c_int64(0)
+    rc = getattr(ctx.lib, f"rlhip_drv_sap_lstsq_{suf}")(ctx.h, m, n, A.data_ptr(), _ldc(A) if lda is None else lda, b.data_ptr(), c.data_ptr(), delta,
+                                                       d_factor, nnz, tol, iter_lim, x.data_ptr(), y.data_ptr(), resid.data_ptr(), st,
+                                                       C.byref(rank), C.byref(iters))
+    _drv_check(ctx, rc, "sap_lstsq")
+    it = int(iters.value)
+    return dict(x=x, y=y, rank=int(rank.value), iters=it, resid=resid[: it + 1].cpu().numpy(), next_ctr=tuple(int(v) for v in st[:4]))
