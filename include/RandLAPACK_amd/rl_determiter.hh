@@ -4,8 +4,11 @@
 // pcg_saddle: the loop is the reference's, statement by statement (line numbers at the right), with these differences:
 //   - every vector (b, c, resid_vec, x0, x, y) and both matrices are DEVICE arrays on q; alpha, beta and delta_1 never leave the device;
 //   - one host read per iteration: the sizeof(T) bytes of resid_vec[iter], for the stop test delta_1 > (delta_1^0 tol) tol;
-//   - q = A^T (A d) + delta d and d^T q come from rlhip_normal_matvec_* (one pass over A for n within its limit), M^T r, M (.), A^T b and
-//     y = b - A x from rlhip_gemv_*, the n-length updates from rlhip_pcg_saddle_step_*;
+//   - the loop is written once, over an operator with the members matvec and normal_matvec (linops::DenseLinOp, linops::SparseLinOp); the
+//     reference's pointer signature wraps its A in a DenseLinOp;
+//   - q = A^T (A d) + delta d and d^T q come from the operator's normal_matvec (dense: rlhip_normal_matvec_*, one pass over A for n within
+//     its limit; sparse: rlhip_csr_normal_matvec_*), A^T b and y = b - A x from its matvec, M^T r and M (.) from rlhip_gemv_*,
+//     the n-length updates from rlhip_pcg_saddle_step_*;
 //   - the residual refresh on iter % 25 == 1 runs the normal matvec on x;
 //   - resid_vec must hold iter_lim + 1 entries: the reference writes resid_vec[iter] after the loop (:127), one past its documented
 //     length (:28) when the limit is reached;
@@ -36,6 +39,7 @@
 #include "rl_exceptions.hh"
 #include "rl_blaspp.hh"
 #include "rl_lapackpp.hh"
+#include "rl_linops.hh"
 #include "rl_determiter_host.hh"
 
 namespace RandLAPACK {
@@ -44,12 +48,6 @@ namespace _saddle_impl {
 
 inline int gemv(blas::Queue& q, Op t, int64_t m, int64_t n, double al, const double* A, int64_t lda, const double* x, double be, double* y) { return rlhip_gemv_f64(q.ctx(), (char)t, m, n, al, A, lda, x, be, y); }
 inline int gemv(blas::Queue& q, Op t, int64_t m, int64_t n, float al, const float* A, int64_t lda, const float* x, float be, float* y) { return rlhip_gemv_f32(q.ctx(), (char)t, m, n, al, A, lda, x, be, y); }
-inline int normal_matvec(blas::Queue& q, int64_t m, int64_t n, const double* A, int64_t lda, const double* d, double delta, double* out, double* t, double* dq) {
-    return rlhip_normal_matvec_f64(q.ctx(), m, n, A, lda, d, delta, out, t, dq, 0);
-}
-inline int normal_matvec(blas::Queue& q, int64_t m, int64_t n, const float* A, int64_t lda, const float* d, float delta, float* out, float* t, float* dq) {
-    return rlhip_normal_matvec_f32(q.ctx(), m, n, A, lda, d, delta, out, t, dq, 0);
-}
 inline int step_xr(blas::Queue& q, int64_t n, const double* d, const double* qv, const double* dq, const double* d1, double* x, double* r) { return rlhip_pcg_saddle_step_xr_f64(q.ctx(), n, d, qv, dq, d1, x, r); }
 inline int step_xr(blas::Queue& q, int64_t n, const float* d, const float* qv, const float* dq, const float* d1, float* x, float* r) { return rlhip_pcg_saddle_step_xr_f32(q.ctx(), n, d, qv, dq, d1, x, r); }
 inline int step_refresh(blas::Queue& q, int64_t n, const double* b1, const double* qx, double delta, const double* x, double* r) { return rlhip_pcg_saddle_step_refresh_f64(q.ctx(), n, b1, qx, delta, x, r); }
@@ -65,10 +63,14 @@ inline int axpby(blas::Queue& q, int64_t n, float a, const float* x, float b, fl
 /// y = b - A x.  A: m x n (lda); b, y: m; c, x0, x: n; resid_vec: iter_lim + 1 -- all DEVICE, column-major.  resid_vec[i] receives
 /// delta_1 = r' M M' r at the start of iteration i and, after the loop, of the iteration that was not run; iterations stop when
 /// delta_1 <= (delta_1^0 tol) tol or after iter_lim.                                                                rl_determiter.hh:18-134
-template <typename T>
-void pcg_saddle(int64_t m, int64_t n, const T* A, int64_t lda, const T* b, const T* c, T delta, int64_t iter_lim, T* resid_vec, T tol, int64_t k,
-                const T* M, int64_t ldm, const T* x0, T* x, T* y, blas::Queue& q = blas::default_queue(), int64_t* iters = nullptr) {
+/// The loop is written once, over an operator: A is anything with n_rows, n_cols, the queue q and the two members
+/// matvec(trans, alpha, x, beta, y) and normal_matvec(d, delta, q, t, dq) -- linops::DenseLinOp and linops::SparseLinOp (rl_linops.hh).
+template <typename T, typename LinOp>
+void pcg_saddle(LinOp& A, const T* b, const T* c, T delta, int64_t iter_lim, T* resid_vec, T tol, int64_t k, const T* M, int64_t ldm, const T* x0, T* x,
+                T* y, int64_t* iters = nullptr) {
     namespace si = _saddle_impl;
+    const int64_t m = A.n_rows, n = A.n_cols;
+    blas::Queue& q = A.q;
     randlapack_require(m >= 1 && n >= 1 && k >= 1) << "pcg_saddle needs m=" << m << ", n=" << n << ", k=" << k << " >= 1";
     randlapack_require(iter_lim >= 0) << "iter_lim=" << iter_lim << " must be >= 0";
     if (iters) *iters = 0;
@@ -86,11 +88,11 @@ void pcg_saddle(int64_t m, int64_t n, const T* A, int64_t lda, const T* b, const
 
     //  b1 = A'b - c
     blas::copy(n, c, 1, b1, 1, q);                                                                                                  // :49
-    blas::check(si::gemv(q, Op::Trans, m, n, (T)1.0, A, lda, b, (T)-1.0, b1), "gemv");                                              // :50
+    A.matvec(Op::Trans, (T)1.0, b, (T)-1.0, b1);                                                                                    // :50
 
     // r = b1 - (A'(A x0) + delta x0)
     blas::copy(n, b1, 1, r, 1, q);                                                                                                  // :57
-    blas::check(si::normal_matvec(q, m, n, A, lda, x0, delta, out_at1, (T*)nullptr, (T*)nullptr), "normal_matvec");                 // :58-60
+    A.normal_matvec(x0, delta, out_at1, (T*)nullptr, (T*)nullptr);                                                                  // :58-60
     blas::check(si::axpby(q, n, (T)-1.0, out_at1, (T)1.0, r), "axpby");                                                             // :61
 
     // d = M (M' r)
@@ -107,13 +109,13 @@ void pcg_saddle(int64_t m, int64_t n, const T* A, int64_t lda, const T* b, const
     while (iter < iter_lim && delta1_new > rel_sq_tol) {                                                                            // :76
         // (resid_vec[iter] = delta1_new: written by the step that computed it)                                                     :77
         // q = A'(A d) + delta d, and d' q
-        blas::check(si::normal_matvec(q, m, n, A, lda, d, delta, out_at1, (T*)nullptr, dq), "normal_matvec");                       // :81-83, 86
+        A.normal_matvec(d, delta, out_at1, (T*)nullptr, dq);                                                                        // :81-83, 86
         const bool refresh = iter % 25 == 1;                                                                                        // :92
         // alpha = delta1_new / (d' q); x += alpha d; r -= alpha q unless r is recomputed
         blas::check(si::step_xr(q, n, d, refresh ? (const T*)nullptr : out_at1, dq, resid_vec + iter, x, r), "pcg_saddle_step_xr"); // :86, 89, 106
         if (refresh) {
             // r = b1 - (A'(A x) + delta x)
-            blas::check(si::normal_matvec(q, m, n, A, lda, x, (T)0.0, out_at1, (T*)nullptr, (T*)nullptr), "normal_matvec");         // :99-100
+            A.normal_matvec(x, (T)0.0, out_at1, (T*)nullptr, (T*)nullptr);                                                          // :99-100
             blas::check(si::step_refresh(q, n, b1, out_at1, delta, x, r), "pcg_saddle_step_refresh");                               // :101-103
         }
         // s = M (M' r)
@@ -129,8 +131,17 @@ void pcg_saddle(int64_t m, int64_t n, const T* A, int64_t lda, const T* b, const
 
     // recover y = b - Ax
     blas::copy(m, b, 1, y, 1, q);                                                                                                   // :130
-    blas::check(si::gemv(q, Op::NoTrans, m, n, (T)-1.0, A, lda, x, (T)1.0, y), "gemv");                                             // :131
+    A.matvec(Op::NoTrans, (T)-1.0, x, (T)1.0, y);                                                                                   // :131
     q.sync();                                    // (the work space goes back to the arena)
+}
+
+/// The same for a dense column-major A (m x n, lda, DEVICE): the reference's signature.
+template <typename T>
+void pcg_saddle(int64_t m, int64_t n, const T* A, int64_t lda, const T* b, const T* c, T delta, int64_t iter_lim, T* resid_vec, T tol, int64_t k,
+                const T* M, int64_t ldm, const T* x0, T* x, T* y, blas::Queue& q = blas::default_queue(), int64_t* iters = nullptr) {
+    randlapack_require(m >= 1 && n >= 1 && k >= 1) << "pcg_saddle needs m=" << m << ", n=" << n << ", k=" << k << " >= 1";
+    linops::DenseLinOp<T> op(m, n, A, lda, Layout::ColMajor, q);
+    pcg_saddle(op, b, c, delta, iter_lim, resid_vec, tol, k, M, ldm, x0, x, y, iters);
 }
 
 /// The Frobenius norm of a DEVICE block, every value kept (rl_determiter.hh:139-151).  pcg recognises this type and fills `history` from the

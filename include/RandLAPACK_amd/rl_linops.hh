@@ -6,7 +6,8 @@
 // (Side::Left: C = alpha op(A) op(B) + beta C;  Side::Right: C = alpha op(B) op(A) + beta C), plus the overload taking a RandBLAS
 // sketching operator in place of B (Side::Right: C = alpha S op(A) + beta C -- how CQRRT_linops sketches, rl_cqrrt_linops.hh:200,207).
 // ABRIK (rl_abrik.hh:311,364,494) and the linop QR drivers (rl_qr_linops.hh) are templated over it.  All B / C are DEVICE pointers
-// and every operator carries the queue it runs on (member `q`).
+// and every operator carries the queue it runs on (member `q`).  DenseLinOp and SparseLinOp also have the two matrix-VECTOR members
+// pcg_saddle runs on (rl_determiter.hh): matvec (y = alpha op(A) x + beta y) and normal_matvec (q = A^T (A d) + delta d).
 //
 //   DenseLinOp        column-major device matrix; MFMA GEMM.  `row_sharded`: one row block per rank, A^T X and S A all-reduced.
 //   SparseLinOp       device CSR (+ the CSR of the transpose, built on first use); gather SpMM, csrc/sparse.hip.  Also built from CSC
@@ -61,6 +62,48 @@ inline void saso_apply_csr(rlhip_saso* S, int64_t n, double alpha, const int64_t
 inline void saso_apply_csr(rlhip_saso* S, int64_t n, float alpha, const int64_t* rpt, const int64_t* cit, const float* vt, float beta, float* C,
                            int64_t ldc, int64_t row0, blas::Queue& q = blas::default_queue()) {
     blas::check(rlhip_saso_apply_csr_f32(q.ctx(), S, n, alpha, rpt, cit, vt, beta, C, ldc, row0), "saso_apply_csr");
+}
+// S A for a sparse A with the sums of the dense sketch (csrc/sketch.hip saso_apply_csr_ordered); false: not served for this operator
+inline bool saso_apply_csr_ordered(rlhip_saso* S, int64_t n, double alpha, const int64_t* rpt, const int64_t* cit, const double* vt, double beta, double* C,
+                                   int64_t ldc, blas::Queue& q) {
+    const int rc = rlhip_saso_apply_csr_ordered_f64(q.ctx(), S, n, alpha, rpt, cit, vt, beta, C, ldc);
+    if (rc != 1) blas::check(rc, "saso_apply_csr_ordered");
+    return rc != 1;
+}
+inline bool saso_apply_csr_ordered(rlhip_saso* S, int64_t n, float alpha, const int64_t* rpt, const int64_t* cit, const float* vt, float beta, float* C,
+                                   int64_t ldc, blas::Queue& q) {
+    const int rc = rlhip_saso_apply_csr_ordered_f32(q.ctx(), S, n, alpha, rpt, cit, vt, beta, C, ldc);
+    if (rc != 1) blas::check(rc, "saso_apply_csr_ordered");
+    return rc != 1;
+}
+// matrix-vector products (csrc/lsq.hip dense, csrc/spmv.hip sparse): what pcg_saddle runs on an operator
+inline void gemv(Op t, int64_t m, int64_t n, double al, const double* A, int64_t lda, const double* x, double be, double* y, blas::Queue& q) {
+    blas::check(rlhip_gemv_f64(q.ctx(), (char)t, m, n, al, A, lda, x, be, y), "gemv");
+}
+inline void gemv(Op t, int64_t m, int64_t n, float al, const float* A, int64_t lda, const float* x, float be, float* y, blas::Queue& q) {
+    blas::check(rlhip_gemv_f32(q.ctx(), (char)t, m, n, al, A, lda, x, be, y), "gemv");
+}
+inline void normal_matvec(int64_t m, int64_t n, const double* A, int64_t lda, const double* d, double delta, double* out, double* t, double* dq, blas::Queue& q) {
+    blas::check(rlhip_normal_matvec_f64(q.ctx(), m, n, A, lda, d, delta, out, t, dq, 0), "normal_matvec");
+}
+inline void normal_matvec(int64_t m, int64_t n, const float* A, int64_t lda, const float* d, float delta, float* out, float* t, float* dq, blas::Queue& q) {
+    blas::check(rlhip_normal_matvec_f32(q.ctx(), m, n, A, lda, d, delta, out, t, dq, 0), "normal_matvec");
+}
+inline void csr_spmv(int64_t nrows, int64_t ncols, int64_t nnz, const int64_t* rp, const int64_t* ci, const double* v, double al, const double* x, double be,
+                     double* y, blas::Queue& q) {
+    blas::check(rlhip_csr_spmv_f64(q.ctx(), nrows, ncols, nnz, rp, ci, v, al, x, be, y), "csr_spmv");
+}
+inline void csr_spmv(int64_t nrows, int64_t ncols, int64_t nnz, const int64_t* rp, const int64_t* ci, const float* v, float al, const float* x, float be,
+                     float* y, blas::Queue& q) {
+    blas::check(rlhip_csr_spmv_f32(q.ctx(), nrows, ncols, nnz, rp, ci, v, al, x, be, y), "csr_spmv");
+}
+inline void csr_normal_matvec(int64_t m, int64_t n, int64_t nnz, const int64_t* rp, const int64_t* ci, const double* v, const int64_t* rpt, const int64_t* cit,
+                              const double* vt, const double* d, double delta, double* out, double* t, double* dq, blas::Queue& q) {
+    blas::check(rlhip_csr_normal_matvec_f64(q.ctx(), m, n, nnz, rp, ci, v, rpt, cit, vt, d, delta, out, t, dq, 0), "csr_normal_matvec");
+}
+inline void csr_normal_matvec(int64_t m, int64_t n, int64_t nnz, const int64_t* rp, const int64_t* ci, const float* v, const int64_t* rpt, const int64_t* cit,
+                              const float* vt, const float* d, float delta, float* out, float* t, float* dq, blas::Queue& q) {
+    blas::check(rlhip_csr_normal_matvec_f32(q.ctx(), m, n, nnz, rp, ci, v, rpt, cit, vt, d, delta, out, t, dq, 0), "csr_normal_matvec");
 }
 }  // namespace detail
 
@@ -141,6 +184,17 @@ struct DenseLinOp {
         randlapack_require(!(row_sharded && q.world() > 1)) << "dense sketching operators are not sharded: use the sparse one";
         RandBLAS::fill_dense(S);
         blas::gemm(layout, Op::NoTrans, Op::NoTrans, d, n, m, alpha, S.buff, d, A_buff, lda, beta, C, ldc, q);
+    }
+
+    /// y = alpha op(A) x + beta y and q = A^T (A d) + delta d (t = A d and *dq = d^T q optional, DEVICE): the two calls pcg_saddle makes
+    /// (rl_determiter.hh).  Least squares over a row-sharded operator is not built.
+    void matvec(Op trans, T alpha, const T* x, T beta, T* y) {
+        randlapack_require(!(row_sharded && q.world() > 1)) << "matvec is not defined for a row-sharded operator";
+        detail::gemv(trans, n_rows, n_cols, alpha, A_buff, lda, x, beta, y, q);
+    }
+    void normal_matvec(const T* d, T delta, T* out, T* t, T* dq) {
+        randlapack_require(!(row_sharded && q.world() > 1)) << "normal_matvec is not defined for a row-sharded operator";
+        detail::normal_matvec(n_rows, n_cols, A_buff, lda, d, delta, out, t, dq, q);
     }
 
     // ---- block views (rl_dense_linop.hh:295-330): non-owning, same storage, same queue
@@ -347,6 +401,20 @@ struct SparseLinOp {
         (*this)(Side::Left, layout, trans_A, trans_B, m, n, k, alpha, B, ldb, beta, C, ldc);
     }
 
+    /// y = alpha op(A) x + beta y and q = A^T (A d) + delta d (t = A d and *dq = d^T q optional, DEVICE) by the sparse matrix-vector
+    /// kernels (csrc/spmv.hip): the two calls pcg_saddle makes (rl_determiter.hh).  Least squares over a row-sharded operator is not built.
+    void matvec(Op trans, T alpha, const T* x, T beta, T* y) {
+        randlapack_require(!(row_sharded && q.world() > 1)) << "matvec is not defined for a row-sharded operator";
+        if (trans == Op::NoTrans) { ensure_forward(); detail::csr_spmv(n_rows, n_cols, nnz, rowptr, colidx, vals, alpha, x, beta, y, q); }
+        else { ensure_transpose(); detail::csr_spmv(n_cols, n_rows, nnz, rowptr_t, colidx_t, vals_t, alpha, x, beta, y, q); }
+    }
+    void normal_matvec(const T* d, T delta, T* out, T* t, T* dq) {
+        randlapack_require(!(row_sharded && q.world() > 1)) << "normal_matvec is not defined for a row-sharded operator";
+        ensure_forward();
+        ensure_transpose();
+        detail::csr_normal_matvec(n_rows, n_cols, nnz, rowptr, colidx, vals, rowptr_t, colidx_t, vals_t, d, delta, out, t, dq, q);
+    }
+
     /// sketching operands, Side::Right: C (d x n) = alpha * S * A + beta * C                                     (:292-330)
     /// Sparse S: a scatter over the nonzeros of A with fixed-point integer LDS atomics (bitwise reproducible, csrc/sketch.hip) --
     /// nnz(S column) * nnz(A) updates instead of a pass over m x n.  Sketches too tall for LDS (d > 19200) fall back to expanding
@@ -381,6 +449,17 @@ struct SparseLinOp {
             detail::csr_densify_cols(m, rowptr_t, colidx_t, vals_t, j, bj, blk, m, q);
             RandBLAS::sketch_general(layout, Op::NoTrans, Op::NoTrans, d, bj, m, alpha, S, 0, 0, blk, m, beta, C + j * ldc, ldc, q);
         }
+    }
+    /// C (d x n, ld d) = S * A with the sums, and so the bits, of the dense sketch of the same matrix (detail::saso_apply_csr_ordered): what
+    /// rpc_data_svd uses, so that the preconditioner of a sparse operator is the one of its dense copy.  Where that route does not serve
+    /// the operator (and for a row shard) the call above runs.
+    template <typename RNG>
+    void sketch_as_dense(int64_t d, RandBLAS::SparseSkOp<T, RNG>& S, T* C) {
+        if (!(row_sharded && q.world() > 1) && n_cols > 0 && d > 0 && S.dist.n_rows == d && S.dist.n_cols == n_rows) {
+            ensure_transpose();
+            if (detail::saso_apply_csr_ordered(S.handle, n_cols, (T)1, rowptr_t, colidx_t, vals_t, (T)0, C, d, q)) return;
+        }
+        (*this)(Side::Right, Layout::ColMajor, Op::NoTrans, Op::NoTrans, d, n_cols, n_rows, (T)1, S, (T)0, C, d);
     }
     /// Dense S (d x m column-major = S^T row-major): C^T (n x d, row-major) = A^T * S^T is a single gather SpMM.
     template <typename RNG>

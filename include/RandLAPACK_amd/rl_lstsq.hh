@@ -7,6 +7,7 @@
 #include "rl_exceptions.hh"
 #include "rl_blaspp.hh"
 #include "rl_randblas.hh"
+#include "rl_linops.hh"
 #include "rl_preconditioners.hh"
 #include "rl_determiter.hh"
 
@@ -39,6 +40,32 @@ SapLstsqResult sap_lstsq(int64_t m, int64_t n, const T* A, int64_t lda, const T*
     randlapack_require(out.rank >= 1) << "sap_lstsq: the sketch of A has numerical rank 0";
     blas::device_memset(x0, 0, n, q);
     pcg_saddle(m, n, A, lda, b, c, delta, iter_lim, resid, tol, out.rank, V_sk, n, x0, x, y, q, &out.iters);
+    return out;
+}
+
+/// The same chain for a sparse operator A (m x n, m >= n; linops::SparseLinOp over CSR, CSC or COO storage): the sketch is the operator's
+/// own scatter, every product of the iteration a sparse matrix-vector product (csrc/spmv.hip).  A is never densified.
+template <typename T, typename RNG>
+SapLstsqResult sap_lstsq(linops::SparseLinOp<T>& A, const T* b, const T* c, T delta, T d_factor, int64_t nnz, T tol, int64_t iter_lim, T* x, T* y,
+                         RandBLAS::RNGState<RNG>& state, T* resid_vec = nullptr) {
+    const int64_t m = A.n_rows, n = A.n_cols;
+    blas::Queue& q = A.q;
+    randlapack_require(!(A.row_sharded && q.world() > 1)) << "sap_lstsq is not defined for a row-sharded operator";
+    randlapack_require(m >= n && n >= 1) << "sap_lstsq needs m=" << m << " >= n=" << n << " >= 1";
+    randlapack_require(d_factor >= (T)1.0) << "d_factor=" << d_factor << " must be >= 1";
+    randlapack_require(iter_lim >= 0) << "iter_lim=" << iter_lim << " must be >= 0";
+    int64_t d = (int64_t)std::ceil((double)d_factor * (double)n);
+    blas::Scratch ws(q);
+    T* V_sk = ws.alloc<T>(d * n);
+    T* sigma_sk = ws.alloc<T>(n);
+    T* x0 = ws.alloc<T>(n);
+    T* resid = resid_vec ? resid_vec : ws.alloc<T>(iter_lim + 1);
+    state = rpc_data_svd_saso(Layout::ColMajor, A, d, nnz, V_sk, sigma_sk, state);
+    SapLstsqResult out;
+    out.rank = make_right_orthogonalizer(Layout::ColMajor, n, V_sk, sigma_sk, delta, n, q);
+    randlapack_require(out.rank >= 1) << "sap_lstsq: the sketch of A has numerical rank 0";
+    blas::device_memset(x0, 0, n, q);
+    pcg_saddle(A, (const T*)b, (const T*)c, delta, iter_lim, resid, tol, out.rank, (const T*)V_sk, n, (const T*)x0, x, y, &out.iters);
     return out;
 }
 

@@ -20,12 +20,22 @@
 #include "rl_lapackpp.hh"
 #include "rl_randblas.hh"
 #include "rl_util.hh"
+#include "rl_linops.hh"
 
 namespace RandLAPACK {
 
 namespace _precond_impl {
 inline void scal_cols(int64_t m, int64_t n, double* A, int64_t lda, const double* s, blas::Queue& q) { blas::check(rlhip_scal_cols_f64(q.ctx(), m, n, A, lda, s), "scal_cols"); }
 inline void scal_cols(int64_t m, int64_t n, float* A, int64_t lda, const float* s, blas::Queue& q) { blas::check(rlhip_scal_cols_f32(q.ctx(), m, n, A, lda, s), "scal_cols"); }
+// steps 2 and 3 of rpc_data_svd: the SVD of the d x n sketch held in V_sk (ld d); only sigma and VT are wanted
+template <typename T>
+void svd_of_sketch(int64_t d, int64_t n, T* V_sk, T* sigma_sk, blas::Queue& q) {
+    blas::Scratch ws(q);
+    T* VT = ws.alloc<T>(n * n);
+    lapack::gesvdj(d, n, V_sk, d, sigma_sk, VT, n, q);                                                                              // :70
+    util::transposition(n, n, VT, n, V_sk, n, 0, q);                                                                                // :71, 84
+    q.sync();                                    // (VT goes back to the arena)
+}
 }  // namespace _precond_impl
 
 /// V_sk (leading n x n, ld n) <- right singular vectors, sigma_sk (n) <- singular values of the sketch S A.  A: m x n (lda), m >= n;
@@ -41,12 +51,19 @@ void rpc_data_svd(Layout layout, int64_t m, int64_t n, const T* A, int64_t lda, 
     T* A_sk = V_sk;                                                                                                                 // :42
     // step 1: A_sk = S A (beta = 0: A_sk is not read)
     RandBLAS::sketch_general(layout, Op::NoTrans, Op::NoTrans, d, n, m, (T)1.0, S, 0, 0, A, lda, (T)0.0, A_sk, d, q);               // :55-64
-    // step 2: the SVD of the sketch; only sigma and VT are wanted
-    blas::Scratch ws(q);
-    T* VT = ws.alloc<T>(n * n);
-    lapack::gesvdj(d, n, A_sk, d, sigma_sk, VT, n, q);                                                                              // :70
-    util::transposition(n, n, VT, n, V_sk, n, 0, q);                                                                                // :71, 84
-    q.sync();                                    // (VT goes back to the arena)
+    _precond_impl::svd_of_sketch(d, n, A_sk, sigma_sk, q);
+}
+
+/// The same for a sparse operator (m x n, m >= n): the sketch S A is the operator's (linops::SparseLinOp::sketch_as_dense: over the nonzeros
+/// of A, with the sums of the dense sketch, so that V_sk and sigma_sk are those of the dense copy of A), the SVD is the dense one.
+template <typename T, typename SKOP>
+void rpc_data_svd(Layout layout, linops::SparseLinOp<T>& A, SKOP& S, T* V_sk, T* sigma_sk) {
+    randlapack_require(layout == Layout::ColMajor) << "rpc_data_svd: only Layout::ColMajor is built";
+    const int64_t m = A.n_rows, n = A.n_cols, d = S.dist.n_rows;
+    randlapack_require(d >= n) << "sketching dimension d=" << d << " must be >= n=" << n;
+    randlapack_require(m >= n) << "Input matrix A must have at least as many rows as columns.";
+    A.sketch_as_dense(d, S, V_sk);
+    _precond_impl::svd_of_sketch(d, n, V_sk, sigma_sk, A.q);
 }
 
 /// rpc_data_svd with a sparse sign operator of d rows and k nonzeros per column drawn from `state`; returns the state to use next.
@@ -59,6 +76,16 @@ RandBLAS::RNGState<RNG> rpc_data_svd_saso(Layout layout, int64_t m, int64_t n, i
     RandBLAS::SparseSkOp<T, RNG> S(D, state, q);                                                                                    // :149-150
     rpc_data_svd(layout, m, n, A, lda, S, V_sk, sigma_sk, q);                                                                       // :151
     return S.next_state;                                                                                                            // :152
+}
+
+/// The same for a sparse operator: the sign operator, and therefore the returned state, are those of a dense A of the same shape.
+template <typename T, typename RNG>
+RandBLAS::RNGState<RNG> rpc_data_svd_saso(Layout layout, linops::SparseLinOp<T>& A, int64_t d, int64_t k, T* V_sk, T* sigma_sk, RandBLAS::RNGState<RNG> state) {
+    randlapack_require(layout == Layout::ColMajor) << "rpc_data_svd_saso: only Layout::ColMajor is built";
+    RandBLAS::SparseDist D(d, A.n_rows, k);
+    RandBLAS::SparseSkOp<T, RNG> S(D, state, A.q);
+    rpc_data_svd(layout, A, S, V_sk, sigma_sk);
+    return S.next_state;
 }
 
 /// V (n x n DEVICE, ld n: right singular vectors of some tall H) and sigma (DEVICE, its singular values) -> the first `rank` columns of V

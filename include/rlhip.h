@@ -62,7 +62,8 @@ enum rlhip_option {
     RLHIP_OPT_DRV_SPARSE_SKETCH_DENSIFY = 10,      /* linops::SparseLinOp::force_densified_sketch (default 0) */
     RLHIP_OPT_JACOBI_CLOCK_HOLDERS = 11,           /* persistent Jacobi: 1 (default) the CUs its workers leave idle run FMA-burning holder workgroups so that DVFS keeps the clock up for the next GEMM (never on a context that shares the device with another stream); 0: the workers alone */
     RLHIP_OPT_LSQ_NORMAL_FUSED = 12,               /* rlhip_normal_matvec_*: 1 the one-pass kernel wherever n is within its limit, 0 always the two rlhip_gemv calls; default: one pass up to the widths at which it measured faster */
-    RLHIP_OPT_COUNT = 13
+    RLHIP_OPT_SPMV_LANES = 13,                     /* rlhip_csr_spmv_*, rlhip_csr_normal_matvec_*: 4, 16 or 64 lanes per row, 0 the split long-row route; default: chosen from the mean row length (tests reach every route at small sizes with it) */
+    RLHIP_OPT_COUNT = 14
 };
 int rlhip_set_option(rlhip_ctx* ctx, int option, int64_t value);     /* -1 (bad context / option) or 0 */
 int64_t rlhip_get_option(rlhip_ctx* ctx, int option);                /* the stored value (-1 = default), INT64_MIN for a bad option */
@@ -266,6 +267,16 @@ int rlhip_saso_apply_csr_f64(rlhip_ctx* ctx, const rlhip_saso* S, int64_t n, dou
                              const double* valsT, double beta, double* B, int64_t ldb, int64_t row0);
 int rlhip_saso_apply_csr_f32(rlhip_ctx* ctx, const rlhip_saso* S, int64_t n, float alpha, const int64_t* rowptrT, const int64_t* colidxT,
                              const float* valsT, float beta, float* B, int64_t ldb, int64_t row0);
+/* The same product with the SUMS of rlhip_saso_apply_* on the same matrix stored densely (lda = m, 16-byte aligned): every output adds
+ * sign * a over its source rows in ascending order, cut into the same partial groups, so the result is bit for bit the dense one (zero
+ * terms change no running sum) -- what makes the sketched preconditioner of a sparse operator identical to that of its dense copy
+ * (rpc_data_svd on a linops::SparseLinOp).  The entries of a row of the transpose's CSR must be in ascending source row without
+ * duplicates (what rlhip_csr_transpose_* builds).  One workgroup per column, no atomics.  Returns 1 and does nothing when the operator is
+ * not served (block-affine mode, or (d + 1024) * sizeof(T) + 4 KiB beyond 160 KiB of LDS): the caller then uses rlhip_saso_apply_csr_*. */
+int rlhip_saso_apply_csr_ordered_f64(rlhip_ctx* ctx, const rlhip_saso* S, int64_t n, double alpha, const int64_t* rowptrT, const int64_t* colidxT,
+                                     const double* valsT, double beta, double* B, int64_t ldb);
+int rlhip_saso_apply_csr_ordered_f32(rlhip_ctx* ctx, const rlhip_saso* S, int64_t n, float alpha, const int64_t* rowptrT, const int64_t* colidxT,
+                                     const float* valsT, float beta, float* B, int64_t ldb);
 int rlhip_saso_dense_f64(rlhip_ctx* ctx, const rlhip_saso* S, double* dense_d_by_m);   /* tests / debugging */
 int rlhip_saso_dense_f32(rlhip_ctx* ctx, const rlhip_saso* S, float* dense_d_by_m);
 /* util::col_swap (misc/rl_util.hh:151-164 == lapmt forward): on exit column i holds former column idx[i]-1.
@@ -569,6 +580,40 @@ int rlhip_pcg_saddle_step_d_f32(rlhip_ctx* ctx, int64_t n, const float* r, const
 /* The routes of this layer, one count per call: 46 a fused rlhip_normal_matvec, 47 a composed one (its two rlhip_gemv calls count as
  * well), 48 rlhip_gemv 'N', 49 rlhip_gemv 'T' (calls that launch nothing are not counted).  -1 for any other index. */
 int64_t rlhip_lsq_path_count(rlhip_ctx* ctx, int which);
+
+/* ---- sparse matrix-vector layer (spmv.hip): the hot path of pcg_saddle on a linops::SparseLinOp.  CSR with int64 indices,
+ *      all arrays DEVICE, everything asynchronous, no host read: nnz (= rowptr[nrows]) is an ARGUMENT.  The rules are those of the dense
+ *      layer above: no workgroup waits for another, no floating-point atomic, results bitwise reproducible and independent of the grid and
+ *      of the device, sums in the precision of the data, nothing written beyond an output's length.  Row pointers are clamped to
+ *      [0, nnz]; column indices are trusted. ---- */
+/* rlhip_csr_spmv_*: y = alpha A x + beta y for the nrows x ncols CSR A; the transposed product is the same call on the transpose's CSR
+ * (rlhip_csr_transpose_*).  beta == 0 does not read y.  nrows == 0 returns 0; nnz == 0 scales y.
+ * Rows route: W = 4, 16 or 64 lanes own a row and walk its entries p, p + W, ... in storage order, the W sums added in a fixed tree; x is
+ * staged in LDS once per workgroup when ncols * sizeof(T) <= RLHIP_SPMV_X_LDS_BYTES.  Split route: rows cut into chunks of RLHIP_SPMV_CHUNK
+ * entries, one wave per chunk, chunk sums in the scratch arena (at most nnz / RLHIP_SPMV_CHUNK + nrows values), a final pass per row.
+ * The route: unasked, the split route for at most 512 rows of mean length nnz / nrows >= 2 RLHIP_SPMV_CHUNK, else W = 4 up to a mean row
+ * length of 64, W = 16 up to 1023, W = 64 beyond (what was measured, what was not); RLHIP_OPT_SPMV_LANES = 4, 16, 64 or 0
+ * (split) forces one.
+ * Argument code: -2 for a NULL context, a negative size, or a NULL array that the sizes say is read or written. */
+#define RLHIP_SPMV_X_LDS_BYTES 32768
+#define RLHIP_SPMV_CHUNK 512
+int rlhip_csr_spmv_f64(rlhip_ctx* ctx, int64_t nrows, int64_t ncols, int64_t nnz, const int64_t* rowptr, const int64_t* colidx, const double* vals,
+                       double alpha, const double* x, double beta, double* y);
+int rlhip_csr_spmv_f32(rlhip_ctx* ctx, int64_t nrows, int64_t ncols, int64_t nnz, const int64_t* rowptr, const int64_t* colidx, const float* vals,
+                       float alpha, const float* x, float beta, float* y);
+/* rlhip_csr_normal_matvec_*: q = A^T (A d) + delta d for the m x n CSR A (rowptr, colidx, vals) and the CSR of its transpose (rowptrT,
+ * colidxT, valsT): two products as above, + delta d in the pass that writes q.  Optional outputs as in rlhip_normal_matvec_*: t = A d
+ * (m values) and *dq_dev = d^T q (the same fixed-order dot).  max_wg > 0 caps the grids; the results do not depend on it.
+ * m == 0: q = delta d.  n == 0: returns 0 and writes nothing.  Argument code: -2 as above. */
+int rlhip_csr_normal_matvec_f64(rlhip_ctx* ctx, int64_t m, int64_t n, int64_t nnz, const int64_t* rowptr, const int64_t* colidx, const double* vals,
+                                const int64_t* rowptrT, const int64_t* colidxT, const double* valsT, const double* d, double delta, double* q,
+                                double* t, double* dq_dev, int64_t max_wg);
+int rlhip_csr_normal_matvec_f32(rlhip_ctx* ctx, int64_t m, int64_t n, int64_t nnz, const int64_t* rowptr, const int64_t* colidx, const float* vals,
+                                const int64_t* rowptrT, const int64_t* colidxT, const float* valsT, const float* d, float delta, float* q, float* t,
+                                float* dq_dev, int64_t max_wg);
+/* The routes of this layer, one count per product: 50 four lanes per row, 51 sixteen, 52 sixty-four, 53 the split route; 54 counts
+ * rlhip_csr_normal_matvec calls (whose two products count as well).  -1 for any other index. */
+int64_t rlhip_spmv_path_count(rlhip_ctx* ctx, int which);
 
 /* ---- row-block sharding across the GPUs of a node (new design; the reference has no
  *      distributed code).  One process per GPU.  Sum all-reduces run on the context's stream through RCCL

@@ -290,6 +290,27 @@ int rlhip_drv_sap_lstsq_f64(rlhip_ctx* ctx, int64_t m, int64_t n, const double* 
 int rlhip_drv_sap_lstsq_f32(rlhip_ctx* ctx, int64_t m, int64_t n, const float* A, int64_t lda, const float* b, const float* c, float delta,
                             float d_factor, int64_t nnz, float tol, int64_t iter_lim, float* x, float* y, float* resid_vec, uint32_t state[6],
                             int64_t* rank, int64_t* iters);
+/* The three entries above over an operator descriptor (rlhip_linop_desc, above) in place of (A, lda); m = left->rows, n = left->cols.  Kind 0
+ * runs the dense entry; kinds 1, 2, 3 (CSR, CSC, COO) a linops::SparseLinOp: the sketch is the operator's scatter over its nonzeros, every product
+ * of the iteration a sparse matrix-vector product (rlhip_csr_spmv_*, rlhip_csr_normal_matvec_*), and A is never densified.  The sign operator, and
+ * so state[6] afterwards, are those of a dense A of the same shape.  right must be NULL: a composite operator is refused (-100 and a message), and
+ * so is a row-sharded one. */
+int rlhip_drv_pcg_saddle_linop_f64(rlhip_ctx* ctx, const rlhip_linop_desc* left, const rlhip_linop_desc* right, const double* b, const double* c,
+                                   double delta, int64_t iter_lim, double* resid_vec, double tol, int64_t k, const double* M, int64_t ldm,
+                                   const double* x0, double* x, double* y, int64_t* iters);
+int rlhip_drv_pcg_saddle_linop_f32(rlhip_ctx* ctx, const rlhip_linop_desc* left, const rlhip_linop_desc* right, const float* b, const float* c,
+                                   float delta, int64_t iter_lim, float* resid_vec, float tol, int64_t k, const float* M, int64_t ldm, const float* x0,
+                                   float* x, float* y, int64_t* iters);
+int rlhip_drv_rpc_data_svd_saso_linop_f64(rlhip_ctx* ctx, const rlhip_linop_desc* left, const rlhip_linop_desc* right, int64_t d, int64_t nnz,
+                                          double* V_sk, double* sigma_sk, uint32_t state[6]);
+int rlhip_drv_rpc_data_svd_saso_linop_f32(rlhip_ctx* ctx, const rlhip_linop_desc* left, const rlhip_linop_desc* right, int64_t d, int64_t nnz,
+                                          float* V_sk, float* sigma_sk, uint32_t state[6]);
+int rlhip_drv_sap_lstsq_linop_f64(rlhip_ctx* ctx, const rlhip_linop_desc* left, const rlhip_linop_desc* right, const double* b, const double* c,
+                                  double delta, double d_factor, int64_t nnz, double tol, int64_t iter_lim, double* x, double* y, double* resid_vec,
+                                  uint32_t state[6], int64_t* rank, int64_t* iters);
+int rlhip_drv_sap_lstsq_linop_f32(rlhip_ctx* ctx, const rlhip_linop_desc* left, const rlhip_linop_desc* right, const float* b, const float* c,
+                                  float delta, float d_factor, int64_t nnz, float tol, int64_t iter_lim, float* x, float* y, float* resid_vec,
+                                  uint32_t state[6], int64_t* rank, int64_t* iters);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,7 @@ def _blas3(T):
         "saso_apply_rows": [c_vp, c_vp, c_i64, T, c_vp, c_i64, c_i64, c_i64, T, c_vp, c_i64],
         "saso_dense": [c_vp, c_vp, c_vp],
         "saso_apply_csr": [c_vp, c_vp, c_i64, T, c_vp, c_vp, c_vp, T, c_vp, c_i64, c_i64],
+        "saso_apply_csr_ordered": [c_vp, c_vp, c_i64, T, c_vp, c_vp, c_vp, T, c_vp, c_i64],
         "col_swap": [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp],
         "geqp3": [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp],
         "get_diag": [c_vp, c_i64, c_vp, c_i64, C.POINTER(T)],
@@ -255,6 +256,16 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # matrix-vector layer, pc
         f"rlhip_drv_make_right_orthogonalizer_{_suf}": (c_int, [c_vp, c_i64, c_vp, c_vp, _T, c_i64, i64p]),
         f"rlhip_drv_sap_lstsq_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, _T, _T, c_i64, _T, c_i64, c_vp, c_vp, c_vp, u32p, i64p,
                                                 i64p]),
+    })
+
+SIGNATURES["rlhip_spmv_path_count"] = (c_i64, [c_vp, c_int])
+for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # sparse matrix-vector layer (spmv.hip) and least squares over an operator descriptor
+    SIGNATURES.update({
+        f"rlhip_csr_spmv_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, _T, c_vp, _T, c_vp]),
+        f"rlhip_csr_normal_matvec_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _T, c_vp, c_vp, c_vp, c_i64]),
+        f"rlhip_drv_pcg_saddle_linop_{_suf}": (c_int, [c_vp, _ldp, _ldp, c_vp, c_vp, _T, c_i64, c_vp, _T, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, i64p]),
+        f"rlhip_drv_rpc_data_svd_saso_linop_{_suf}": (c_int, [c_vp, _ldp, _ldp, c_i64, c_i64, c_vp, c_vp, u32p]),
+        f"rlhip_drv_sap_lstsq_linop_{_suf}": (c_int, [c_vp, _ldp, _ldp, c_vp, c_vp, _T, _T, c_i64, _T, c_i64, c_vp, c_vp, c_vp, u32p, i64p, i64p]),
     })
 
 _lib = None

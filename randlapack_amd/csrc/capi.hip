@@ -489,6 +489,11 @@ static inline int op_flag(char t, int* out) {
                                    const T* valsT, T beta, T* B, int64_t ldb, int64_t row0) {                   \
         return rlhip::saso_apply_csr<T>(c, (const rlhip::SasoOp*)S, n, alpha, rowptrT, colidxT, valsT, beta, B, ldb, row0); \
     }                                                                                                           \
+    int rlhip_saso_apply_csr_ordered_##SUF(rlhip_ctx* c, const rlhip_saso* S, int64_t n, T alpha, const int64_t* rowptrT,         \
+                                           const int64_t* colidxT, const T* valsT, T beta, T* B, int64_t ldb) {  \
+        if (!c || !S) return -2;                                                                                \
+        return rlhip::saso_apply_csr_ordered<T>(c, (const rlhip::SasoOp*)S, n, alpha, rowptrT, colidxT, valsT, beta, B, ldb); \
+    }                                                                                                           \
     int rlhip_saso_dense_##SUF(rlhip_ctx* c, const rlhip_saso* S, T* dense) {                                   \
         return rlhip::saso_dense<T>(c, (const rlhip::SasoOp*)S, dense);                                          \
     }                                                                                                           \

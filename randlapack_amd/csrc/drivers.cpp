@@ -952,6 +952,70 @@ int drv_sap_lstsq(rlhip_ctx* ctx, int64_t m, int64_t n, const T* A, int64_t lda,
         return 0;
     });
 }
+
+// the same three over an operator descriptor: kind 0 runs the dense entry above, kinds 1, 2, 3 a linops::SparseLinOp; a composite is refused
+inline void check_lsq_operator(const rlhip_linop_desc* left, const rlhip_linop_desc* right, const char* who) {
+    if (!left) throw RandLAPACK::Error(std::string(who) + ": operator descriptor is null");
+    if (right) throw RandLAPACK::Error(std::string(who) + ": a composite operator (right != NULL) is not supported");
+    if (left->kind < 0 || left->kind > 3) throw RandLAPACK::Error(std::string(who) + ": operator kind must be 0 (dense), 1 (CSR), 2 (CSC) or 3 (COO)");
+    if (left->rows < 0 || left->cols < 0 || (left->kind != 0 && left->nnz < 0)) throw RandLAPACK::Error(std::string(who) + ": negative dimension");
+    if (left->kind == 0 ? !left->dense : (!left->rowptr || (left->nnz > 0 && (!left->colidx || !left->vals))))
+        throw RandLAPACK::Error(std::string(who) + ": the operator's arrays must not be null");
+}
+template <typename T>
+int drv_pcg_saddle_linop(rlhip_ctx* ctx, const rlhip_linop_desc* left, const rlhip_linop_desc* right, const T* b, const T* c, T delta, int64_t iter_lim,
+                         T* resid_vec, T tol, int64_t k, const T* M, int64_t ldm, const T* x0, T* x, T* y, int64_t* iters) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        check_lsq_operator(left, right, "pcg_saddle");
+        if (left->kind == 0)
+            return drv_pcg_saddle<T>(ctx, left->rows, left->cols, (const T*)left->dense, left->ld, b, c, delta, iter_lim, resid_vec, tol, k, M, ldm, x0, x, y, iters);
+        if (!b || !c || !resid_vec || !M || !x0 || !x || !y) throw RandLAPACK::Error("pcg_saddle: b, c, resid_vec, M, x0, x and y must not be null");
+        if (ldm < left->cols) throw RandLAPACK::Error("pcg_saddle: ldm must be >= n");
+        if (!(tol > (T)0) || !(delta >= (T)0)) throw RandLAPACK::Error("pcg_saddle: tol must be > 0 and delta >= 0");
+        auto A = make_sparse<T>(q, *left);
+        int64_t it = 0;
+        RandLAPACK::pcg_saddle(*A, b, c, delta, iter_lim, resid_vec, tol, k, M, ldm, x0, x, y, &it);
+        if (iters) *iters = it;
+        return 0;
+    });
+}
+template <typename T>
+int drv_rpc_data_svd_saso_linop(rlhip_ctx* ctx, const rlhip_linop_desc* left, const rlhip_linop_desc* right, int64_t d, int64_t nnz, T* V_sk, T* sigma_sk,
+                                uint32_t state[6]) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        check_lsq_operator(left, right, "rpc_data_svd_saso");
+        if (left->kind == 0) return drv_rpc_data_svd_saso<T>(ctx, left->rows, left->cols, d, nnz, (const T*)left->dense, left->ld, V_sk, sigma_sk, state);
+        if (!V_sk || !sigma_sk || !state) throw RandLAPACK::Error("rpc_data_svd_saso: V_sk, sigma_sk and state must not be null");
+        if (left->cols < 1 || nnz < 1) throw RandLAPACK::Error("rpc_data_svd_saso: n and nnz must be >= 1");
+        auto A = make_sparse<T>(q, *left);
+        State st = load_state(state);
+        st = RandLAPACK::rpc_data_svd_saso(RandLAPACK::Layout::ColMajor, *A, d, nnz, V_sk, sigma_sk, st);
+        store_state(st, state);
+        return 0;
+    });
+}
+template <typename T>
+int drv_sap_lstsq_linop(rlhip_ctx* ctx, const rlhip_linop_desc* left, const rlhip_linop_desc* right, const T* b, const T* c, T delta, T d_factor, int64_t nnz,
+                        T tol, int64_t iter_lim, T* x, T* y, T* resid_vec, uint32_t state[6], int64_t* rank, int64_t* iters) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        check_lsq_operator(left, right, "sap_lstsq");
+        if (left->kind == 0)
+            return drv_sap_lstsq<T>(ctx, left->rows, left->cols, (const T*)left->dense, left->ld, b, c, delta, d_factor, nnz, tol, iter_lim, x, y, resid_vec, state,
+                                    rank, iters);
+        if (!b || !c || !x || !y || !state) throw RandLAPACK::Error("sap_lstsq: b, c, x, y and state must not be null");
+        if (!(tol > (T)0) || !(delta >= (T)0) || nnz < 1) throw RandLAPACK::Error("sap_lstsq: tol must be > 0, delta >= 0 and nnz >= 1");
+        auto A = make_sparse<T>(q, *left);
+        State st = load_state(state);
+        const auto r = RandLAPACK::sap_lstsq(*A, b, c, delta, d_factor, nnz, tol, iter_lim, x, y, st, resid_vec);
+        store_state(st, state);
+        if (rank) *rank = r.rank;
+        if (iters) *iters = r.iters;
+        return 0;
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -971,6 +1035,20 @@ extern "C" {
                                   int64_t nnz, T tol, int64_t iter_lim, T* x, T* y, T* resid_vec, uint32_t state[6], int64_t* rank,               \
                                   int64_t* iters) {                                                                                               \
         return drv_sap_lstsq<T>(ctx, m, n, A, lda, b, c, delta, d_factor, nnz, tol, iter_lim, x, y, resid_vec, state, rank, iters);               \
+    }                                                                                                                                             \
+    int rlhip_drv_pcg_saddle_linop_##SUF(rlhip_ctx* ctx, const rlhip_linop_desc* left, const rlhip_linop_desc* right, const T* b, const T* c,     \
+                                         T delta, int64_t iter_lim, T* resid_vec, T tol, int64_t k, const T* M, int64_t ldm, const T* x0, T* x,   \
+                                         T* y, int64_t* iters) {                                                                                  \
+        return drv_pcg_saddle_linop<T>(ctx, left, right, b, c, delta, iter_lim, resid_vec, tol, k, M, ldm, x0, x, y, iters);                      \
+    }                                                                                                                                             \
+    int rlhip_drv_rpc_data_svd_saso_linop_##SUF(rlhip_ctx* ctx, const rlhip_linop_desc* left, const rlhip_linop_desc* right, int64_t d,           \
+                                                int64_t nnz, T* V_sk, T* sigma_sk, uint32_t state[6]) {                                           \
+        return drv_rpc_data_svd_saso_linop<T>(ctx, left, right, d, nnz, V_sk, sigma_sk, state);                                                   \
+    }                                                                                                                                             \
+    int rlhip_drv_sap_lstsq_linop_##SUF(rlhip_ctx* ctx, const rlhip_linop_desc* left, const rlhip_linop_desc* right, const T* b, const T* c,      \
+                                        T delta, T d_factor, int64_t nnz, T tol, int64_t iter_lim, T* x, T* y, T* resid_vec, uint32_t state[6],   \
+                                        int64_t* rank, int64_t* iters) {                                                                          \
+        return drv_sap_lstsq_linop<T>(ctx, left, right, b, c, delta, d_factor, nnz, tol, iter_lim, x, y, resid_vec, state, rank, iters);          \
     }
 RLHIP_DEFINE_LSQ_DRIVERS(f64, double)
 RLHIP_DEFINE_LSQ_DRIVERS(f32, float)

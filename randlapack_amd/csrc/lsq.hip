@@ -441,6 +441,15 @@ int gemv(rlhip_ctx* c, int trans, int64_t m, int64_t n, T alpha, const T* A, int
 template int gemv<double>(rlhip_ctx*, int, int64_t, int64_t, double, const double*, int64_t, const double*, double, double*);
 template int gemv<float>(rlhip_ctx*, int, int64_t, int64_t, float, const float*, int64_t, const float*, float, float*);
 
+template <typename T>
+int dot_dev(rlhip_ctx* c, int64_t n, const T* x, const T* y, T* out_dev) {
+    hipLaunchKernelGGL(dot_kernel<T>, dim3(1), dim3(256), 0, c->stream, n, x, y, out_dev);
+    RLHIP_LAUNCH_CHECK();
+    return 0;
+}
+template int dot_dev<double>(rlhip_ctx*, int64_t, const double*, const double*, double*);
+template int dot_dev<float>(rlhip_ctx*, int64_t, const float*, const float*, float*);
+
 }  // namespace rlhip
 
 extern "C" {

@@ -146,7 +146,7 @@ struct rlhip_ctx {
     // > 0: columns per workgroup of the tag-exchange pivoted QR (default 4; a caller that overlaps the factorization with another kernel packs
     // the columns into fewer workgroups so that it occupies fewer CUs)
     int qrcp_cols_per_wg = 0;
-    int64_t opt[RLHIP_OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // rlhip_set_option; -1 = default
+    int64_t opt[RLHIP_OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // rlhip_set_option; -1 = default
     rlhip_ctx* side_ctx = nullptr;   // cached side context (rlhip_side_of): created on first use, destroyed with this one
     hipStream_t side = nullptr;  // second stream, created on first use (rlhip_dvfs_burn: load beside the main stream's latency-bound kernels)
     // row-sharding communicator (comm.hip), nullptr = single GPU
@@ -168,6 +168,9 @@ struct rlhip_ctx {
     // the routes of the matrix-vector layer (lsq.hip), read through rlhip_lsq_path_count: [0] = 46 fused normal matvec, [1] = 47 composed
     // normal matvec, [2] = 48 gemv 'N', [3] = 49 gemv 'T'
     int64_t lsq_path_count[4] = {};
+    // the routes of the sparse matrix-vector layer (spmv.hip), read through rlhip_spmv_path_count: [0] = 50 four lanes per row, [1] = 51
+    // sixteen, [2] = 52 sixty-four, [3] = 53 split long rows, [4] = 54 csr_normal_matvec calls
+    int64_t spmv_path_count[5] = {};
 };
 
 // every host wait of the library goes through here: the epoch lets deferred read-backs know that an earlier wait already covered them
@@ -344,6 +347,10 @@ int saso_apply(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T* A, i
 template <typename T>
 int saso_apply_csr(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const int64_t* rowptrT, const int64_t* colidxT, const T* valsT, T beta,
                    T* B, int64_t ldb, int64_t row0);
+// the same product with the sums of saso_apply on the densified operand (lda = m), bit for bit; 1: not served, take saso_apply_csr
+template <typename T>
+int saso_apply_csr_ordered(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const int64_t* rowptrT, const int64_t* colidxT, const T* valsT, T beta,
+                           T* B, int64_t ldb);
 template <typename T>
 int col_swap(rlhip_ctx* c, int64_t m, int64_t n, int64_t k, T* A, int64_t lda, const int64_t* idx_dev);
 int col_swap_i64(rlhip_ctx* c, int64_t n, int64_t k, int64_t* A, const int64_t* idx_dev);
@@ -426,5 +433,8 @@ int luqrcp_piv(rlhip_ctx* c, int64_t sd, int64_t cols, const int64_t* ipiv_dev, 
 // y = alpha op(A) x + beta y (trans: NoTrans / Trans); the contract is rlhip_gemv_* in include/rlhip.h
 template <typename T>
 int gemv(rlhip_ctx* c, int trans, int64_t m, int64_t n, T alpha, const T* A, int64_t lda, const T* x, T beta, T* y);
+// *out_dev = x^T y by one workgroup in the fixed order of rlhip_normal_matvec_*'s d^T q (n > 0)
+template <typename T>
+int dot_dev(rlhip_ctx* c, int64_t n, const T* x, const T* y, T* out_dev);
 
 }  // namespace rlhip

@@ -924,20 +924,23 @@ int saso_dense(rlhip_ctx* c, const SasoOp* op, T* S /* d x m, zeroed here */) {
     return 0;
 }
 
-// B (d x n, ldb) = alpha * S[:, row0 : row0 + mloc] * A_loc (mloc x n, lda) + beta * B : the contribution of one row shard
-// (the whole product when row0 = 0, mloc = m)
+// How saso_apply_rows cuts the row blocks of a product into partial groups (each group is ONE running sum per output, the groups are added
+// in order by saso_reduce_kernel), and which kernel serves them.  One definition: saso_apply_csr_ordered replays the same sums on a sparse
+// operand and must cut them at the same rows.
+struct SasoGrouping {
+    int CT;
+    size_t smem, slab2;
+    int64_t tb0, tb1, nTb, ctiles, G, tpg, fb0, fb1, nfb, tpg_d, Gtot;
+    bool dma;
+    int head, tail;
+};
 template <typename T>
-int saso_apply_rows(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T* A, int64_t lda, int64_t row0, int64_t mloc, T beta,
-                    T* B, int64_t ldb) {
-    const int64_t d = op->d, m = op->m;
-    if (n <= 0) return 0;
-    if (row0 < 0 || mloc < 0 || row0 + mloc > m) return -6;
-    if (lda < (mloc > 1 ? mloc : 1)) return -6;
-    if (ldb < d) return -9;
+static int saso_grouping(const SasoOp* op, int64_t n, const void* A, int64_t lda, int64_t row0, int64_t mloc, SasoGrouping& s) {
+    const int64_t d = op->d;
+    const size_t lds_cap = 160 * 1024;
     const int64_t tb0 = (mloc > 0) ? row0 / d : 0, tb1 = (mloc > 0) ? (row0 + mloc + d - 1) / d : 0, nTb = tb1 - tb0;
     // columns per workgroup: the d x CT slab has to fit the CU's LDS (4 columns up to d = 5120 fp64 / 10240 fp32, then 2, then 1:
     // d <= 20480 fp64 / 40960 fp32; taller sketches are refused with -2, documented in rlhip.h)
-    const size_t lds_cap = 160 * 1024;
     const int CT = (sizeof(T) * (size_t)d * 4 <= lds_cap) ? 4 : (sizeof(T) * (size_t)d * 2 <= lds_cap) ? 2 : 1;
     const size_t smem = sizeof(T) * (size_t)d * CT;
     if (smem > lds_cap) return -2;
@@ -966,6 +969,27 @@ int saso_apply_rows(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T*
     const int64_t tpg_d = dma ? (nfb + G - 1) / G : tpg;
     if (dma) G = (nfb + tpg_d - 1) / tpg_d;
     const int64_t Gtot = G + head + tail;
+    s.CT = CT; s.smem = smem; s.slab2 = slab2; s.tb0 = tb0; s.tb1 = tb1; s.nTb = nTb; s.ctiles = ctiles; s.G = G; s.tpg = tpg; s.fb0 = fb0; s.fb1 = fb1;
+    s.nfb = nfb; s.tpg_d = tpg_d; s.Gtot = Gtot; s.dma = dma; s.head = head; s.tail = tail;
+    return 0;
+}
+
+// B (d x n, ldb) = alpha * S[:, row0 : row0 + mloc] * A_loc (mloc x n, lda) + beta * B : the contribution of one row shard
+// (the whole product when row0 = 0, mloc = m)
+template <typename T>
+int saso_apply_rows(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const T* A, int64_t lda, int64_t row0, int64_t mloc, T beta,
+                    T* B, int64_t ldb) {
+    const int64_t d = op->d, m = op->m;
+    if (n <= 0) return 0;
+    if (row0 < 0 || mloc < 0 || row0 + mloc > m) return -6;
+    if (lda < (mloc > 1 ? mloc : 1)) return -6;
+    if (ldb < d) return -9;
+    SasoGrouping sg;
+    if (const int grc = saso_grouping<T>(op, n, A, lda, row0, mloc, sg)) return grc;
+    const size_t lds_cap = 160 * 1024, smem = sg.smem, slab2 = sg.slab2;
+    const int CT = sg.CT, head = sg.head, tail = sg.tail;
+    const int64_t tb0 = sg.tb0, tb1 = sg.tb1, nTb = sg.nTb, ctiles = sg.ctiles, G = sg.G, tpg = sg.tpg, fb0 = sg.fb0, fb1 = sg.fb1, tpg_d = sg.tpg_d, Gtot = sg.Gtot;
+    const bool dma = sg.dma;
     ws_scope ws(c);
     T* partial = ws.alloc<T>((size_t)Gtot * d * n);
     if (!partial) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
@@ -1037,6 +1061,95 @@ int saso_apply_csr(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const int
 }
 template int saso_apply_csr<double>(rlhip_ctx*, const SasoOp*, int64_t, double, const int64_t*, const int64_t*, const double*, double, double*, int64_t, int64_t);
 template int saso_apply_csr<float>(rlhip_ctx*, const SasoOp*, int64_t, float, const int64_t*, const int64_t*, const float*, float, float*, int64_t, int64_t);
+
+// ---- S * A for a sparse A with the SUMS OF THE DENSE APPLY: for every output (r, c) the dense kernels above add sign * A[i, c] over the
+// source rows i of sketch row r in ascending order, one running sum per partial group of row blocks, and saso_reduce_kernel adds the
+// groups in order.  A term with A[i, c] = 0 changes no running sum, so adding the stored entries of column c alone, in ascending row, cut
+// into the same groups, gives the same bits (up to the sign of a zero).  One workgroup per column (= row of the transpose's CSR, entries
+// in ascending source row, no duplicates): it walks the groups in order; the entries of a group go through LDS in tiles of (sketch row,
+// signed value) pairs, and thread t applies, in pair order, the pairs of the sketch rows r = t mod 256 it owns -- so every accumulator
+// sees its terms in entry order with no atomic.  Independent-column operators only (the block-affine lists are not sorted by source row).
+// Dynamic LDS: d accumulators, SAO_PAIRS values, SAO_PAIRS entries.
+constexpr int SAO_PAIRS = 1024;
+template <typename T>
+__global__ __launch_bounds__(256) void saso_apply_csr_ordered_kernel(int64_t d, int64_t m, int nnz, const int32_t* __restrict__ rows,
+                                                                     const int64_t* __restrict__ rowptrT, const int64_t* __restrict__ colidxT,
+                                                                     const T* __restrict__ valsT, int64_t n, int64_t G, int64_t tpg, int64_t reg_end_block,
+                                                                     int tail, T* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    T* acc = reinterpret_cast<T*>(smem_raw);                    // [d]
+    T* pv = acc + d;                                            // [SAO_PAIRS]
+    uint32_t* pr = reinterpret_cast<uint32_t*>(pv + SAO_PAIRS); // [SAO_PAIRS]
+    const int tid = threadIdx.x;
+    const int64_t c = blockIdx.x;
+    const int E = SAO_PAIRS / nnz;                              // entries per tile (nnz <= 128)
+    int64_t p = rowptrT[c];
+    const int64_t pend = rowptrT[c + 1];
+    for (int64_t g = 0; g < G + tail; ++g) {
+        int64_t row_end = m;
+        if (g < G) {
+            const int64_t be = (g + 1) * tpg < reg_end_block ? (g + 1) * tpg : reg_end_block;
+            row_end = be * d < m ? be * d : m;
+        }
+        for (int64_t r = tid; r < d; r += 256) acc[r] = T(0);
+        int64_t lo = p, hi = pend;                              // the first entry of the column at or beyond row_end
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (colidxT[mid] < row_end) lo = mid + 1;
+            else hi = mid;
+        }
+        const int64_t pe = lo;
+        __syncthreads();
+        for (int64_t base = p; base < pe; base += E) {
+            const int cnt = (int)(pe - base < E ? pe - base : E);
+            for (int q = tid; q < cnt * nnz; q += 256) {
+                const int e = q / nnz, k = q - e * nnz;
+                pr[q] = (uint32_t)rows[colidxT[base + e] * nnz + k];
+                pv[q] = valsT[base + e];
+            }
+            __syncthreads();
+            for (int q = 0; q < cnt * nnz; ++q) {
+                const uint32_t ent = pr[q], r = ent & 0x7fffffffu;
+                if ((int)(r & 255u) == tid) acc[r] += (ent & 0x80000000u) ? -pv[q] : pv[q];
+            }
+            __syncthreads();
+        }
+        T* out = partial + g * d * n + c * d;
+        for (int64_t r = tid; r < d; r += 256) out[r] = acc[r];
+        __syncthreads();
+        p = pe;
+    }
+}
+
+// B (d x n, ldb) = alpha * S * A + beta * B for a sparse A given by the CSR of its transpose, bit for bit what saso_apply gives for the
+// same matrix stored densely with lda = m on a 16-byte aligned address.  Returns 1 when this route does not serve the operator
+// (block-affine mode, or a sketch too tall for the accumulators in LDS): the caller takes saso_apply_csr.
+template <typename T>
+int saso_apply_csr_ordered(rlhip_ctx* c, const SasoOp* op, int64_t n, T alpha, const int64_t* rowptrT, const int64_t* colidxT, const T* valsT, T beta,
+                           T* B, int64_t ldb) {
+    if (n <= 0) return 0;
+    if (ldb < op->d) return -9;
+    const int64_t d = op->d, m = op->m;
+    const size_t smem = sizeof(T) * (size_t)(d + SAO_PAIRS) + sizeof(uint32_t) * SAO_PAIRS;
+    if (op->mode != 1 || !op->rows || smem > 160 * 1024) return 1;
+    SasoGrouping sg;
+    if (saso_grouping<T>(op, n, nullptr, m > 1 ? m : 1, 0, m, sg)) return 1;
+    ws_scope ws(c);
+    T* partial = ws.alloc<T>((size_t)sg.Gtot * d * n);
+    if (!partial) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
+    // (row0 = 0: no ragged head; the regular groups cover the blocks below reg_end, a ragged last block is the tail group of the DMA route)
+    const int64_t reg_end = sg.dma ? sg.fb1 : sg.tb1;
+    RLHIP_FUNC_LDS(c, saso_apply_csr_ordered_kernel<T>, 160 * 1024);
+    hipLaunchKernelGGL(saso_apply_csr_ordered_kernel<T>, dim3((unsigned)n), dim3(256), smem, c->stream, d, m, op->nnz, (const int32_t*)op->rows, rowptrT, colidxT,
+                       valsT, n, m > 0 ? sg.G : (int64_t)1, sg.dma ? sg.tpg_d : sg.tpg, reg_end, m > 0 ? sg.tail : 0, partial);
+    RLHIP_LAUNCH_CHECK();
+    const int64_t total = d * n;
+    hipLaunchKernelGGL(saso_reduce_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, total, (int)sg.Gtot, partial, alpha, beta, B, d, ldb);
+    RLHIP_LAUNCH_CHECK();
+    return 0;
+}
+template int saso_apply_csr_ordered<double>(rlhip_ctx*, const SasoOp*, int64_t, double, const int64_t*, const int64_t*, const double*, double, double*, int64_t);
+template int saso_apply_csr_ordered<float>(rlhip_ctx*, const SasoOp*, int64_t, float, const int64_t*, const int64_t*, const float*, float, float*, int64_t);
 
 // in-place forward column permutation; idx is a DEVICE array of n 1-based indices (left untouched)
 // Small matrices (sketch-sized blocks: the finished rows of R_sk in CQRRPT's split QRCP, 512 x 512): the permutation as a parallel gather into

@@ -198,10 +198,15 @@ class Context:
         """routes of the matrix-vector layer: 46 fused normal matvec, 47 composed, 48 gemv 'N', 49 gemv 'T' (include/rlhip.h rlhip_lsq_path_count)"""
         return int(self.lib.rlhip_lsq_path_count(self.h, which))
 
+    def spmv_path_count(self, which: int) -> int:
+        """routes of the sparse matrix-vector layer: 50 / 51 / 52 a product with 4 / 16 / 64 lanes per row, 53 the split long-row route,
+        54 csr_normal_matvec calls (include/rlhip.h rlhip_spmv_path_count)"""
+        return int(self.lib.rlhip_spmv_path_count(self.h, which))
+
     # ---- options (include/rlhip.h: enum rlhip_option; -1 restores the default)
     OPT = dict(cholqrq_one_stream=0, gesdd_gram=1, jacobi_persist=2, trsm_xasm=3, saso_mode=4, hqrrp_tall_panel=5,
                bqrrp_lookahead_min_elems=6, bqrrp_cholqr_fallback=7, cqrrpt_fold_pivoting=8, cqrrpt_split_qrcp=9, sparse_sketch_densify=10, jacobi_clock_holders=11,
-               lsq_normal_fused=12)
+               lsq_normal_fused=12, spmv_lanes=13)
 
     def set_option(self, name: str, value: int) -> None:
         _lib.check(self.lib.rlhip_set_option(self.h, self.OPT[name], int(value)), "set_option")
@@ -1051,5 +1056,83 @@ def sap_lstsq(ctx: Context, A, m, n, b, c, delta, d_factor, nnz, tol, iter_lim, 
                                                        d_factor, nnz, tol, iter_lim, x.data_ptr(), y.data_ptr(), resid.data_ptr(), st,
                                                        C.byref(rank), C.byref(iters))
     _drv_check(ctx, rc, "sap_lstsq")
+    it = int(iters.value)
+    return dict(x=x, y=y, rank=int(rank.value), iters=it, resid=resid[: it + 1].cpu().numpy(), next_ctr=tuple(int(v) for v in st[:4]))
+
+
+# ---- the sparse matrix-vector layer (spmv.hip) and least squares over an operator (DenseOperator, CsrOperator, CscOperator, CooOperator)
+def csr_spmv(ctx: Context, nrows, ncols, rowptr, colidx, vals, alpha, x, beta, y):
+    """y = alpha A x + beta y in place for the nrows x ncols CSR (rowptr, colidx, vals) (rlhip_csr_spmv_*); the transposed product is the
+    same call on the transpose's CSR"""
+    suf, _ = _suf(y)
+    rc = getattr(ctx.lib, f"rlhip_csr_spmv_{suf}")(ctx.h, nrows, ncols, int(vals.numel()), _ptr(rowptr), _ptr(colidx), _ptr(vals), alpha, _ptr(x), beta,
+                                                  _ptr(y))
+    _lib.check(rc, "csr_spmv")
+    return y
+
+
+def csr_normal_matvec(ctx: Context, m, n, csr, csr_t, d, delta, q, t=None, want_dq=False, max_wg=0):
+    """q = A^T (A d) + delta d (rlhip_csr_normal_matvec_*) for A given as csr = (rowptr, colidx, vals) and csr_t, the same of its
+    transpose; t (optional, m values) receives A d.  Returns d^T q as a one-element device tensor when want_dq, else None."""
+    torch = _torch()
+    suf, _ = _suf(q)
+    dq = torch.zeros(1, dtype=q.dtype, device=q.device) if want_dq else None
+    rc = getattr(ctx.lib, f"rlhip_csr_normal_matvec_{suf}")(ctx.h, m, n, int(csr[2].numel()), _ptr(csr[0]), _ptr(csr[1]), _ptr(csr[2]), _ptr(csr_t[0]),
+                                                           _ptr(csr_t[1]), _ptr(csr_t[2]), _ptr(d), delta, _ptr(q), _ptr(t), _ptr(dq), max_wg)
+    _lib.check(rc, "csr_normal_matvec")
+    return dq
+
+
+def _single_op_descs(op):
+    ld, rd, m, n, dtype = _op_descs(op)
+    return C.byref(ld), (C.byref(rd) if rd is not None else None), m, n, dtype, (ld, rd)
+
+
+def pcg_saddle_op(ctx: Context, op, b, c, delta, iter_lim, tol, M, k, x0, ldm=None):
+    """pcg_saddle on an operator: same outputs as pcg_saddle"""
+    torch = _torch()
+    lp, rp, m, n, dtype, _keep = _single_op_descs(op)
+    suf = "f64" if dtype == torch.float64 else "f32"
+    dev = f"cuda:{ctx.device}"
+    x = torch.zeros(n, dtype=dtype, device=dev)
+    y = torch.zeros(m, dtype=dtype, device=dev)
+    resid = torch.full((iter_lim + 1,), float("nan"), dtype=dtype, device=dev)
+    iters = C.c_int64(0)
+    rc = getattr(ctx.lib, f"rlhip_drv_pcg_saddle_linop_{suf}")(ctx.h, lp, rp, b.data_ptr(), c.data_ptr(), delta, iter_lim, resid.data_ptr(), tol, k,
+                                                              M.data_ptr(), _ldc(M) if ldm is None else ldm, x0.data_ptr(), x.data_ptr(), y.data_ptr(),
+                                                              C.byref(iters))
+    _drv_check(ctx, rc, "pcg_saddle_op")
+    it = int(iters.value)
+    return dict(x=x, y=y, iters=it, resid=resid[: it + 1].cpu().numpy())
+
+
+def rpc_data_svd_saso_op(ctx: Context, op, d, nnz, ctr=(0, 0, 0, 0), key=(0, 0)):
+    """rpc_data_svd_saso on an operator: same outputs as rpc_data_svd_saso"""
+    torch = _torch()
+    lp, rp, m, n, dtype, _keep = _single_op_descs(op)
+    suf = "f64" if dtype == torch.float64 else "f32"
+    dev = f"cuda:{ctx.device}"
+    V_sk = torch.zeros(max(d * n, 1), dtype=dtype, device=dev)
+    sigma = torch.zeros(n, dtype=dtype, device=dev)
+    st = _state_arr(ctr, key)
+    rc = getattr(ctx.lib, f"rlhip_drv_rpc_data_svd_saso_linop_{suf}")(ctx.h, lp, rp, d, nnz, V_sk.data_ptr(), sigma.data_ptr(), st)
+    _drv_check(ctx, rc, "rpc_data_svd_saso_op")
+    return dict(V=V_sk[: n * n].view(n, n), sigma=sigma, next_ctr=tuple(int(v) for v in st[:4]))
+
+
+def sap_lstsq_op(ctx: Context, op, b, c, delta, d_factor, nnz, tol, iter_lim, ctr=(0, 0, 0, 0), key=(0, 0)):
+    """sap_lstsq on an operator: same outputs as sap_lstsq"""
+    torch = _torch()
+    lp, rp, m, n, dtype, _keep = _single_op_descs(op)
+    suf = "f64" if dtype == torch.float64 else "f32"
+    dev = f"cuda:{ctx.device}"
+    x = torch.zeros(n, dtype=dtype, device=dev)
+    y = torch.zeros(m, dtype=dtype, device=dev)
+    resid = torch.full((iter_lim + 1,), float("nan"), dtype=dtype, device=dev)
+    st = _state_arr(ctr, key)
+    rank, iters = C.c_int64(0), C.c_int64(0)
+    rc = getattr(ctx.lib, f"rlhip_drv_sap_lstsq_linop_{suf}")(ctx.h, lp, rp, b.data_ptr(), c.data_ptr(), delta, d_factor, nnz, tol, iter_lim,
+                                                             x.data_ptr(), y.data_ptr(), resid.data_ptr(), st, C.byref(rank), C.byref(iters))
+    _drv_check(ctx, rc, "sap_lstsq_op")
     it = int(iters.value)
     return dict(x=x, y=y, rank=int(rank.value), iters=it, resid=resid[: it + 1].cpu().numpy(), next_ctr=tuple(int(v) for v in st[:4]))
