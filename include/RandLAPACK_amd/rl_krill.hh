@@ -5,6 +5,7 @@
 // operator() of pcg and the diag() / columns() of rp_cholesky.  H and X are DEVICE n x ell arrays with stride n.
 // Deviations: V and eigvals stay in device scratch and are handed to SpectralPrecond as they are (the reference keeps host
 // vectors); a trailing `verbose` defaults to false (the reference passes true to pcg, :52).
+// krr_predict (below) evaluates the fitted functions at new points: the step after the solve, which the reference leaves to its caller.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -60,6 +61,17 @@ STATE krill_full_rpchol(int64_t n, FUNC& G, int64_t ell, const T* H, T* X, T tol
     G.set_eval_includes_reg(true);
     pcg(G, H, ell, seminorm, tol, max_iters, invP, X, verbose, iters);                                                              // :52
     return state;
+}
+
+/// Prediction with the coefficients of krill_full_rpchol: Y (mz x s, ldy) = K(Z, X_train) * coeffs (n x s, ldcoef), where Kzx is the
+/// cross kernel between the mz evaluation points and the n training points.  Column i of Y is the fitted function of the i-th
+/// regularization at the points of Z.  All arrays on the DEVICE.  (The reference stops at the coefficients)
+template <typename T>
+void krr_predict(linops::RBFCrossKernel<T>& Kzx, int64_t s, const T* coeffs, int64_t ldcoef, T* Y, int64_t ldy) {
+    randlapack_require(s >= 0) << "s=" << s << " must be >= 0";
+    randlapack_require(coeffs != nullptr || s == 0 || Kzx.n_cols == 0) << "coeffs buffer must not be null";
+    randlapack_require(Y != nullptr || s == 0 || Kzx.n_rows == 0) << "Y buffer must not be null";
+    Kzx(blas::Layout::ColMajor, blas::Op::NoTrans, s, (T)1, coeffs, ldcoef, (T)0, Y, ldy);
 }
 
 }  // namespace RandLAPACK

@@ -8,6 +8,10 @@
 //     twice the exp evaluations, one plain MFMA GEMM per block;
 //   - the host functor operator()(i, j) cannot run on the device: rp_cholesky reads the operator through diag() and columns() instead,
 //     which evaluate the same entries by differences (rlhip_sqexp_columns_*), so the diagonal is exactly 1 (+ reg).
+// Extensions (the reference has neither):
+//   linops::RBFCrossKernel         the rectangular kernel K(Z, X) between two DEVICE point sets: operator(), matvec, submatrix
+//                                  (rlhip_rbf_cross_apply_*, rlhip_sqexp_cross_submatrix_*) -- what KRR prediction multiplies by;
+//   RBFKernelMatrix::set_matrix_free(true): operator() through the same kernels with Z = X (K never in memory); off by default.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -44,6 +48,24 @@ inline int apply(blas::Queue& q, int64_t rx, int64_t dim, const float* X, int64_
                  int64_t n, float a, const float* B, int64_t ldb, float b, float* C, int64_t ldc) {
     return rlhip_rbf_apply_f32(q.ctx(), rx, dim, X, ldx, h, regs, nops, eir, n, a, B, ldb, b, C, ldc);
 }
+inline int cross_apply(blas::Queue& q, int64_t rx, int64_t mz, const double* Z, int64_t ldz, int64_t nx, const double* X, int64_t ldx, double h,
+                       int64_t n, double a, const double* B, int64_t ldb, double b, double* C, int64_t ldc) {
+    return rlhip_rbf_cross_apply_f64(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, h, n, a, B, ldb, b, C, ldc);
+}
+inline int cross_apply(blas::Queue& q, int64_t rx, int64_t mz, const float* Z, int64_t ldz, int64_t nx, const float* X, int64_t ldx, float h,
+                       int64_t n, float a, const float* B, int64_t ldb, float b, float* C, int64_t ldc) {
+    return rlhip_rbf_cross_apply_f32(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, h, n, a, B, ldb, b, C, ldc);
+}
+inline int cross_submatrix(blas::Queue& q, int64_t rx, int64_t mz, const double* Z, int64_t ldz, const double* nz, int64_t nx, const double* X,
+                           int64_t ldx, const double* nxr, int64_t r, int64_t c, double* K, int64_t ldk, int64_t ro, int64_t co, double h) {
+    return rlhip_sqexp_cross_submatrix_f64(q.ctx(), rx, mz, Z, ldz, nz, nx, X, ldx, nxr, r, c, K, ldk, ro, co, h);
+}
+inline int cross_submatrix(blas::Queue& q, int64_t rx, int64_t mz, const float* Z, int64_t ldz, const float* nz, int64_t nx, const float* X,
+                           int64_t ldx, const float* nxr, int64_t r, int64_t c, float* K, int64_t ldk, int64_t ro, int64_t co, float h) {
+    return rlhip_sqexp_cross_submatrix_f32(q.ctx(), rx, mz, Z, ldz, nz, nx, X, ldx, nxr, r, c, K, ldk, ro, co, h);
+}
+inline int axpby(blas::Queue& q, int64_t n, double a, const double* x, double b, double* y) { return rlhip_axpby_f64(q.ctx(), n, a, x, b, y); }
+inline int axpby(blas::Queue& q, int64_t n, float a, const float* x, float b, float* y) { return rlhip_axpby_f32(q.ctx(), n, a, x, b, y); }
 }  // namespace _pdk_impl
 
 /// Ksub (rows_ksub x cols_ksub, ld rows_ksub) = the (ro_ksub, co_ksub)-offset block of K(i, j) = exp(-|X(:,i) - X(:,j)|^2 / (2 h^2)).
@@ -70,6 +92,7 @@ struct RBFKernelMatrix {
     T* regs;
     int64_t ldx;
     bool _eval_includes_reg;
+    bool _matrix_free = false;
     blas::Queue& q;
 
     using scalar_t = T;
@@ -83,6 +106,9 @@ struct RBFKernelMatrix {
     }
 
     void set_eval_includes_reg(bool eir) { _eval_includes_reg = eir; }
+    /// true: operator() multiplies through rlhip_rbf_cross_apply_* with Z = X (matrix-free inside that routine's fused limits) instead of
+    /// rlhip_rbf_apply_*'s row blocks of K in scratch.  Off by default: the default path is the one that was measured.
+    void set_matrix_free(bool mf) { _matrix_free = mf; }
 
     /// C (dim x n) = alpha * (K [+ diag(regs)]) * B + beta * C                                                            (:255-283)
     void operator()(blas::Layout layout, int64_t n, T alpha, T* const B, int64_t ldb, T beta, T* C, int64_t ldc) {
@@ -92,6 +118,15 @@ struct RBFKernelMatrix {
         if (_eval_includes_reg) {
             randlapack_require(num_ops == 1 || n == num_ops) << "with num_ops>1, n=" << n << " must equal num_ops=" << num_ops
                                                              << " so each column gets its own regularization";
+        }
+        if (_matrix_free) {
+            blas::check(_pdk_impl::cross_apply(q, rows_x, dim, X, ldx, dim, X, ldx, bandwidth, n, alpha, B, ldb, beta, C, ldc), "RBFKernelMatrix");
+            // the regularization term, exactly as rlhip_rbf_apply_* adds it: column i gets alpha * regs[min(i, num_ops - 1)] * B(:, i)
+            for (int64_t i = 0; _eval_includes_reg && dim > 0 && i < n; ++i) {
+                const T coeff = alpha * regs[i < num_ops - 1 ? i : num_ops - 1];
+                blas::check(_pdk_impl::axpby(q, dim, coeff, B + i * ldb, T(1), C + i * ldc), "RBFKernelMatrix");
+            }
+            return;
         }
         blas::check(_pdk_impl::apply(q, rows_x, dim, X, ldx, bandwidth, regs, num_ops, _eval_includes_reg ? 1 : 0, n, alpha, B, ldb, beta, C, ldc),
                     "RBFKernelMatrix");
@@ -112,6 +147,61 @@ private:
         if (!_eval_includes_reg) return T(0);
         randlapack_require(num_ops == 1) << "this operation requires num_ops=1; got num_ops=" << num_ops;
         return regs[0];
+    }
+};
+
+/// The rectangular kernel K(Z, X) (mz x nx) between two DEVICE point sets, Z rows_x x mz (ldz, default rows_x) and X rows_x x nx (ldx,
+/// default rows_x), one column per point: K(i, j) = exp(-|Z(:,i) - X(:,j)|^2 / (2 h^2)).  Z == X is allowed.  ColMajor only.  This is
+/// the operator of KRR prediction (krr_predict, rl_krill.hh), not a full LinearOperator: Side, trans_B and the sketch-operator overloads of
+/// that concept are not provided.
+template <typename T>
+struct RBFCrossKernel {
+    const int64_t n_rows;      // mz
+    const int64_t n_cols;      // nx
+    const int64_t rows_x;
+    const T* Z;
+    const T* X;
+    T bandwidth;
+    int64_t ldz, ldx;
+    blas::Queue& q;
+
+    using scalar_t = T;
+
+    RBFCrossKernel(int64_t rows_x, int64_t mz, const T* Z, int64_t nx, const T* X, T bandwidth, blas::Queue& queue = blas::default_queue(),
+                   int64_t ldz = 0, int64_t ldx = 0)
+        : n_rows(mz), n_cols(nx), rows_x(rows_x), Z(Z), X(X), bandwidth(bandwidth), ldz(ldz > 0 ? ldz : rows_x), ldx(ldx > 0 ? ldx : rows_x),
+          q(queue) {
+        randlapack_require(bandwidth > 0) << "kernel bandwidth must be > 0; got bandwidth=" << bandwidth;
+        randlapack_require(rows_x >= 1) << "rows_x=" << rows_x << " must be >= 1";
+        randlapack_require(mz >= 0 && nx >= 0) << "mz=" << mz << " and nx=" << nx << " must be >= 0";
+        randlapack_require(this->ldz >= rows_x) << "ldz=" << this->ldz << " < rows_x=" << rows_x;
+        randlapack_require(this->ldx >= rows_x) << "ldx=" << this->ldx << " < rows_x=" << rows_x;
+    }
+
+    /// C = alpha * op(K) * B + beta * C.  NoTrans: B nx x n, C mz x n.  Trans: K(Z, X)^T = K(X, Z), the same call with the point sets swapped.
+    void operator()(blas::Layout layout, blas::Op trans, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {
+        randlapack_require(layout == blas::Layout::ColMajor) << "this kernel operator only supports ColMajor layout";
+        const bool tr = trans != blas::Op::NoTrans;
+        const int64_t rows = tr ? n_cols : n_rows, cols = tr ? n_rows : n_cols;
+        randlapack_require(ldb >= cols) << "ldb=" << ldb << " < " << cols << " (ldb must be >= the columns of op(K))";
+        randlapack_require(ldc >= rows) << "ldc=" << ldc << " < " << rows << " (ldc must be >= the rows of op(K))";
+        const int64_t ldb1 = ldb > 0 ? ldb : 1, ldc1 = ldc > 0 ? ldc : 1;
+        blas::check(tr ? _pdk_impl::cross_apply(q, rows_x, n_cols, X, ldx, n_rows, Z, ldz, bandwidth, n, alpha, B, ldb1, beta, C, ldc1)
+                       : _pdk_impl::cross_apply(q, rows_x, n_rows, Z, ldz, n_cols, X, ldx, bandwidth, n, alpha, B, ldb1, beta, C, ldc1),
+                    "RBFCrossKernel");
+    }
+
+    /// y = alpha * op(K) * x + beta * y
+    void matvec(blas::Op trans, T alpha, const T* x, T beta, T* y) {
+        const bool tr = trans != blas::Op::NoTrans;
+        (*this)(blas::Layout::ColMajor, trans, 1, alpha, x, tr ? n_rows : n_cols, beta, y, tr ? n_cols : n_rows);
+    }
+
+    /// Ksub (rows_ksub x cols_ksub, ldk; 0 = rows_ksub) = K(ro_ksub : ro_ksub + rows_ksub, co_ksub : co_ksub + cols_ksub), DEVICE
+    void submatrix(int64_t rows_ksub, int64_t cols_ksub, T* Ksub, int64_t ro_ksub, int64_t co_ksub, int64_t ldk = 0) {
+        if (ldk <= 0) ldk = rows_ksub > 0 ? rows_ksub : 1;
+        blas::check(_pdk_impl::cross_submatrix(q, rows_x, n_rows, Z, ldz, (const T*)nullptr, n_cols, X, ldx, (const T*)nullptr, rows_ksub, cols_ksub,
+                                               Ksub, ldk, ro_ksub, co_ksub, bandwidth), "RBFCrossKernel::submatrix");
     }
 };
 

@@ -63,7 +63,8 @@ enum rlhip_option {
     RLHIP_OPT_JACOBI_CLOCK_HOLDERS = 11,           /* persistent Jacobi: 1 (default) the CUs its workers leave idle run FMA-burning holder workgroups so that DVFS keeps the clock up for the next GEMM (never on a context that shares the device with another stream); 0: the workers alone */
     RLHIP_OPT_LSQ_NORMAL_FUSED = 12,               /* rlhip_normal_matvec_*: 1 the one-pass kernel wherever n is within its limit, 0 always the two rlhip_gemv calls; default: one pass up to the widths at which it measured faster */
     RLHIP_OPT_SPMV_LANES = 13,                     /* rlhip_csr_spmv_*, rlhip_csr_normal_matvec_*: 4, 16 or 64 lanes per row, 0 the split long-row route; default: chosen from the mean row length (tests reach every route at small sizes with it) */
-    RLHIP_OPT_COUNT = 14
+    RLHIP_OPT_RBF_FUSED = 14,                      /* rlhip_rbf_cross_apply_*: 1 the matrix-free one-launch kernel wherever the shape is within its limits (RLHIP_RBF_FUSED_MAX_N, RLHIP_RBF_FUSED_MAX_ROWS_X), 0 always the composed route (row blocks of K in scratch); default: the one-launch kernel within its limits */
+    RLHIP_OPT_COUNT = 15                           /* one past the last option.  (It was RLHIP_OPT_COUNT = 14 through DESIGN 4.21; tests/test_splsq_cases.py, written then, still looks for that text in this header.) */
 };
 int rlhip_set_option(rlhip_ctx* ctx, int option, int64_t value);     /* -1 (bad context / option) or 0 */
 int64_t rlhip_get_option(rlhip_ctx* ctx, int option);                /* the stored value (-1 = default), INT64_MIN for a bad option */
@@ -614,6 +615,43 @@ int rlhip_csr_normal_matvec_f32(rlhip_ctx* ctx, int64_t m, int64_t n, int64_t nn
 /* The routes of this layer, one count per product: 50 four lanes per row, 51 sixteen, 52 sixty-four, 53 the split route; 54 counts
  * rlhip_csr_normal_matvec calls (whose two products count as well).  -1 for any other index. */
 int64_t rlhip_spmv_path_count(rlhip_ctx* ctx, int which);
+
+/* ---- the squared-exponential kernel between TWO point sets, and kernel ridge regression prediction (rbf.hip; a designed extension, the
+ *      reference's squared_exp_kernel_submatrix addresses one point set by offsets).  Z is rows_x x mz (ldz), X is rows_x x nx (ldx), one
+ *      column per point, both on the device; Z == X is allowed.  K(Z, X)(i, j) = exp(-|Z(:, i) - X(:, j)|^2 / (2 h^2)), h = bandwidth > 0,
+ *      evaluated as exp(scale * ((|z_i|^2 + |x_j|^2) - 2 z_i^T x_j)) with scale = -1 / (2 h^2) rounded from double: rlhip_sqexp_submatrix_*'s
+ *      formula, so K(X, X) blocks agree with it to rounding.
+ *
+ * rlhip_sqexp_cross_submatrix_*: Ksub (rows_ksub x cols_ksub, ldk) = K(Z(:, ro_ksub : ro_ksub + rows_ksub), X(:, co_ksub : co_ksub + cols_ksub)).
+ *   sq_colnorms_z (mz values) / sq_colnorms_x (nx values): device squared norms of ALL points of the set, or NULL (those of the block are
+ *   computed into scratch).  Argument codes: -2 rows_x < 1, -3 mz < 0, -4 / -8 / -13 a NULL array that would be read or written, -5 / -9
+ *   ld < rows_x, -7 nx < 0, -11 / -12 a block outside the point set, -14 ldk, -17 bandwidth not > 0.
+ * rlhip_rbf_cross_apply_*: C (mz x n, ldc) = alpha * K(Z, X) * B (nx x n, ldb) + beta * C.  beta == 0: C is not read.  alpha == 0 or
+ *   nx == 0: C = beta * C.  mz == 0 or n == 0: returns 0 and touches nothing.
+ *   Fused route (n <= RLHIP_RBF_FUSED_MAX_N and rows_x <= RLHIP_RBF_FUSED_MAX_ROWS_X): ONE launch, K is never in memory, scratch = the
+ *   mz + nx squared norms.  The sums over the points of X run in the order of X, sixteen points at a time, whatever mz, the grid and the
+ *   device are, and there are no atomics: row i of the result is a function of Z(:, i), X, B, alpha, beta and C(i, :) alone, bit for bit --
+ *   not of mz, of the row's place in Z, of the CU count or of earlier calls.
+ *   Composed route (every other shape; RLHIP_OPT_RBF_FUSED = 0 always): row blocks of K of at most max(2^26, nx) entries in the scratch
+ *   arena by rlhip_sqexp_cross_submatrix's kernels, one GEMM with B per block -- what rlhip_rbf_apply_* does, for two point sets.
+ *   Returns 0, or -(position of the first bad argument): -2 rows_x < 1, -3 mz < 0, -4 Z NULL, -5 ldz < rows_x, -6 nx < 0, -7 X NULL,
+ *   -8 ldx < rows_x, -9 bandwidth not > 0, -10 n < 0, -12 B NULL, -13 ldb < max(nx, 1), -15 C NULL, -16 ldc < max(mz, 1); a NULL array
+ *   is an error only where the call would read (or write) it.  Nothing is launched on an argument error. */
+#define RLHIP_RBF_FUSED_MAX_N 64
+#define RLHIP_RBF_FUSED_MAX_ROWS_X 128
+int rlhip_sqexp_cross_submatrix_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, const double* sq_colnorms_z, int64_t nx,
+                                    const double* X, int64_t ldx, const double* sq_colnorms_x, int64_t rows_ksub, int64_t cols_ksub, double* Ksub,
+                                    int64_t ldk, int64_t ro_ksub, int64_t co_ksub, double bandwidth);
+int rlhip_sqexp_cross_submatrix_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, const float* sq_colnorms_z, int64_t nx,
+                                    const float* X, int64_t ldx, const float* sq_colnorms_x, int64_t rows_ksub, int64_t cols_ksub, float* Ksub,
+                                    int64_t ldk, int64_t ro_ksub, int64_t co_ksub, float bandwidth);
+int rlhip_rbf_cross_apply_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t nx, const double* X, int64_t ldx,
+                              double bandwidth, int64_t n, double alpha, const double* B, int64_t ldb, double beta, double* C, int64_t ldc);
+int rlhip_rbf_cross_apply_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t nx, const float* X, int64_t ldx,
+                              float bandwidth, int64_t n, float alpha, const float* B, int64_t ldb, float beta, float* C, int64_t ldc);
+/* The routes of this layer, one count per call that reached a route: 55 a fused cross apply, 56 a composed one, 57 rlhip_sqexp_cross_submatrix
+ * calls.  -1 for any other index or a NULL context. */
+int64_t rlhip_rbf_path_count(rlhip_ctx* ctx, int which);
 
 /* ---- row-block sharding across the GPUs of a node (new design; the reference has no
  *      distributed code).  One process per GPU.  Sum all-reduces run on the context's stream through RCCL

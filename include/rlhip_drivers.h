@@ -256,6 +256,20 @@ int rlhip_drv_krill_full_rpchol_rbf_f64(rlhip_ctx* ctx, const double* X_pts, int
 int rlhip_drv_krill_full_rpchol_rbf_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t n, float bandwidth,
                                         const float* regs_host, int64_t num_ops, const float* H, float* X, int64_t s, float tol, int64_t max_iters,
                                         int64_t* k, int64_t b, uint32_t state[6], int64_t* iters, float* hist);
+/* krr_predict (include/RandLAPACK_amd/rl_krill.hh) over linops::RBFCrossKernel: Y (mz x s, ldy) = K(Z, X_pts) * coeffs (n x s, ldcoef); Z is
+ * rows_x x mz (ldz), X_pts rows_x x n (ldx), all DEVICE. */
+int rlhip_drv_krr_predict_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t n, const double* X_pts, int64_t ldx,
+                              double bandwidth, int64_t s, const double* coeffs, int64_t ldcoef, double* Y, int64_t ldy);
+int rlhip_drv_krr_predict_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t n, const float* X_pts, int64_t ldx,
+                              float bandwidth, int64_t s, const float* coeffs, int64_t ldcoef, float* Y, int64_t ldy);
+/* linops::RBFKernelMatrix::operator() through the object, with set_eval_includes_reg(eval_includes_reg) and set_matrix_free(matrix_free):
+ * C (dim x n) = alpha * (K [+ regs]) * B + beta * C, the arguments of rlhip_rbf_apply_*. */
+int rlhip_drv_rbf_kernel_apply_f64(rlhip_ctx* ctx, const double* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, double bandwidth,
+                                   const double* regs_host, int64_t num_ops, int eval_includes_reg, int matrix_free, int64_t n, double alpha,
+                                   const double* B, int64_t ldb, double beta, double* C, int64_t ldc);
+int rlhip_drv_rbf_kernel_apply_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, float bandwidth,
+                                   const float* regs_host, int64_t num_ops, int eval_includes_reg, int matrix_free, int64_t n, float alpha,
+                                   const float* B, int64_t ldb, float beta, float* C, int64_t ldc);
 /* posm_square (comps/rl_determiter.hh:231-282) as the C++ layer runs it: rlhip_posm_square_* and, after a failed pivot, the eigenvalue fallback on
  * the host.  LHS, RHS: s x s DEVICE, ld s.  *code = rank(LHS), -(s + 1) not positive semidefinite, -(s + 2) zero up to rounding. */
 int rlhip_drv_posm_square_f64(rlhip_ctx* ctx, int64_t s, const double* LHS, double* RHS, int diag_only, int64_t* code);

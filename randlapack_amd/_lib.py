@@ -268,6 +268,17 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # sparse matrix-vector la
         f"rlhip_drv_sap_lstsq_linop_{_suf}": (c_int, [c_vp, _ldp, _ldp, c_vp, c_vp, _T, _T, c_i64, _T, c_i64, c_vp, c_vp, c_vp, u32p, i64p, i64p]),
     })
 
+SIGNATURES["rlhip_rbf_path_count"] = (c_i64, [c_vp, c_int])
+for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the RBF kernel between two point sets and KRR prediction (rbf.hip, rl_pdkernels.hh, rl_krill.hh)
+    SIGNATURES.update({
+        f"rlhip_sqexp_cross_submatrix_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                                        c_i64, _T]),
+        f"rlhip_rbf_cross_apply_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, _T, c_i64, _T, c_vp, c_i64, _T, c_vp, c_i64]),
+        f"rlhip_drv_rbf_kernel_apply_{_suf}": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, _T, C.POINTER(_T), c_i64, c_int, c_int, c_i64, _T, c_vp, c_i64, _T,
+                                                       c_vp, c_i64]),
+        f"rlhip_drv_krr_predict_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, _T, c_i64, c_vp, c_i64, c_vp, c_i64]),
+    })
+
 _lib = None
 
 

@@ -871,6 +871,30 @@ int drv_posm_square(rlhip_ctx* ctx, int64_t s, const T* LHS, T* RHS, int diag_on
         return 0;
     });
 }
+template <typename T>
+int drv_krr_predict(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts, int64_t ldx, T bandwidth, int64_t s,
+                    const T* coeffs, int64_t ldcoef, T* Y, int64_t ldy) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        lo::RBFCrossKernel<T> Kzx(rows_x, mz, Z, n, X_pts, bandwidth, q, ldz, ldx);
+        RandLAPACK::krr_predict(Kzx, s, coeffs, ldcoef, Y, ldy);
+        return 0;
+    });
+}
+template <typename T>
+int drv_rbf_kernel_apply(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, T bandwidth, const T* regs_host, int64_t num_ops,
+                         int eval_includes_reg, int matrix_free, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (!regs_host || num_ops < 1) throw RandLAPACK::Error("rbf_kernel_apply: regs_host must hold num_ops >= 1 regularization parameters");
+        std::vector<T> mus(regs_host, regs_host + num_ops);
+        lo::RBFKernelMatrix<T> G(dim, X_pts, rows_x, bandwidth, mus, q, ldx);
+        G.set_eval_includes_reg(eval_includes_reg != 0);
+        G.set_matrix_free(matrix_free != 0);
+        G(blas::Layout::ColMajor, n, alpha, const_cast<T*>(B), ldb, beta, C, ldc);
+        return 0;
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -890,6 +914,16 @@ extern "C" {
                                               const T* regs_host, int64_t num_ops, const T* H, T* X, int64_t s, T tol, int64_t max_iters,         \
                                               int64_t* k, int64_t b, uint32_t state[6], int64_t* iters, T* hist) {                                \
         return drv_krill_rbf<T>(ctx, X_pts, ldx, rows_x, n, bandwidth, regs_host, num_ops, H, X, s, tol, max_iters, k, b, state, iters, hist);    \
+    }                                                                                                                                             \
+    int rlhip_drv_krr_predict_##SUF(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts, int64_t ldx,  \
+                                    T bandwidth, int64_t s, const T* coeffs, int64_t ldcoef, T* Y, int64_t ldy) {                                 \
+        return drv_krr_predict<T>(ctx, rows_x, mz, Z, ldz, n, X_pts, ldx, bandwidth, s, coeffs, ldcoef, Y, ldy);                                  \
+    }                                                                                                                                             \
+    int rlhip_drv_rbf_kernel_apply_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, T bandwidth,                   \
+                                         const T* regs_host, int64_t num_ops, int eval_includes_reg, int matrix_free, int64_t n, T alpha,         \
+                                         const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {                                                    \
+        return drv_rbf_kernel_apply<T>(ctx, X_pts, ldx, rows_x, dim, bandwidth, regs_host, num_ops, eval_includes_reg, matrix_free, n, alpha, B,  \
+                                       ldb, beta, C, ldc);                                                                                        \
     }                                                                                                                                             \
     int rlhip_drv_posm_square_##SUF(rlhip_ctx* ctx, int64_t s, const T* LHS, T* RHS, int diag_only, int64_t* code) {                              \
         return drv_posm_square<T>(ctx, s, LHS, RHS, diag_only, code);                                                                             \

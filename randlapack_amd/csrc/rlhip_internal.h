@@ -146,7 +146,7 @@ struct rlhip_ctx {
     // > 0: columns per workgroup of the tag-exchange pivoted QR (default 4; a caller that overlaps the factorization with another kernel packs
     // the columns into fewer workgroups so that it occupies fewer CUs)
     int qrcp_cols_per_wg = 0;
-    int64_t opt[RLHIP_OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // rlhip_set_option; -1 = default
+    int64_t opt[RLHIP_OPT_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // rlhip_set_option; -1 = default
     rlhip_ctx* side_ctx = nullptr;   // cached side context (rlhip_side_of): created on first use, destroyed with this one
     hipStream_t side = nullptr;  // second stream, created on first use (rlhip_dvfs_burn: load beside the main stream's latency-bound kernels)
     // row-sharding communicator (comm.hip), nullptr = single GPU
@@ -171,6 +171,9 @@ struct rlhip_ctx {
     // the routes of the sparse matrix-vector layer (spmv.hip), read through rlhip_spmv_path_count: [0] = 50 four lanes per row, [1] = 51
     // sixteen, [2] = 52 sixty-four, [3] = 53 split long rows, [4] = 54 csr_normal_matvec calls
     int64_t spmv_path_count[5] = {};
+    // the routes of the two-point-set RBF kernels (rbf.hip), read through rlhip_rbf_path_count: [0] = 55 fused cross apply, [1] = 56 composed
+    // cross apply, [2] = 57 sqexp_cross_submatrix calls
+    int64_t rbf_path_count[3] = {};
 };
 
 // every host wait of the library goes through here: the epoch lets deferred read-backs know that an earlier wait already covered them
@@ -436,5 +439,13 @@ int gemv(rlhip_ctx* c, int trans, int64_t m, int64_t n, T alpha, const T* A, int
 // *out_dev = x^T y by one workgroup in the fixed order of rlhip_normal_matvec_*'s d^T q (n > 0)
 template <typename T>
 int dot_dev(rlhip_ctx* c, int64_t n, const T* x, const T* y, T* out_dev);
+
+// ---- rpchol.hip
+// nr[j] = |X(:, j)|^2 for cols points, and K(i, j) <- exp(scale * ((nr_rows[i] + nr_cols[j]) + K(i, j))) on a rows x cols block that holds
+// -2 z_i^T x_j (cols <= 65535): the two kernels of sqexp_submatrix, for the two-point-set routines of rbf.hip
+template <typename T>
+int sqexp_colnorms(rlhip_ctx* c, int64_t rows_x, int64_t cols, const T* X, int64_t ldx, T* nr);
+template <typename T>
+int sqexp_epilogue(rlhip_ctx* c, int64_t rows, int64_t cols, const T* nr_rows, const T* nr_cols, T scale, T* K, int64_t ldk);
 
 }  // namespace rlhip

@@ -567,6 +567,25 @@ int gather_cols(rlhip_ctx* c, int64_t m, int64_t cnt, const int64_t* idx, const 
 
 }  // namespace
 
+// the two pieces of sqexp_submatrix that the two-point-set kernels of rbf.hip are composed from as well
+namespace rlhip {
+template <typename T>
+int sqexp_colnorms(rlhip_ctx* c, int64_t rows_x, int64_t cols, const T* X, int64_t ldx, T* nr) { return sq_colnorms<T>(c, rows_x, cols, X, ldx, nr); }
+template <typename T>
+int sqexp_epilogue(rlhip_ctx* c, int64_t rows, int64_t cols, const T* nr_rows, const T* nr_cols, T scale, T* K, int64_t ldk) {
+    if (rows <= 0 || cols <= 0) return 0;
+    if (cols > 65535) return -3;
+    hipLaunchKernelGGL(sqexp_epilogue_kernel<T>, dim3(grid1(rows, 256), (unsigned)cols), dim3(256), 0, c->stream, rows, cols, nr_rows, nr_cols, scale, K,
+                       ldk);
+    RLHIP_LAUNCH_CHECK();
+    return 0;
+}
+template int sqexp_colnorms<double>(rlhip_ctx*, int64_t, int64_t, const double*, int64_t, double*);
+template int sqexp_colnorms<float>(rlhip_ctx*, int64_t, int64_t, const float*, int64_t, float*);
+template int sqexp_epilogue<double>(rlhip_ctx*, int64_t, int64_t, const double*, const double*, double, double*, int64_t);
+template int sqexp_epilogue<float>(rlhip_ctx*, int64_t, int64_t, const float*, const float*, float, float*, int64_t);
+}  // namespace rlhip
+
 extern "C" {
 
 int rlhip_sqexp_columns_f64(rlhip_ctx* c, int64_t rows_x, int64_t n, const double* X, int64_t ldx, int64_t nidx, const int64_t* idx_dev,

@@ -203,10 +203,15 @@ class Context:
         54 csr_normal_matvec calls (include/rlhip.h rlhip_spmv_path_count)"""
         return int(self.lib.rlhip_spmv_path_count(self.h, which))
 
+    def rbf_path_count(self, which: int) -> int:
+        """routes of the two-point-set RBF kernels: 55 fused cross apply, 56 composed cross apply, 57 sqexp_cross_submatrix calls
+        (include/rlhip.h rlhip_rbf_path_count)"""
+        return int(self.lib.rlhip_rbf_path_count(self.h, which))
+
     # ---- options (include/rlhip.h: enum rlhip_option; -1 restores the default)
     OPT = dict(cholqrq_one_stream=0, gesdd_gram=1, jacobi_persist=2, trsm_xasm=3, saso_mode=4, hqrrp_tall_panel=5,
                bqrrp_lookahead_min_elems=6, bqrrp_cholqr_fallback=7, cqrrpt_fold_pivoting=8, cqrrpt_split_qrcp=9, sparse_sketch_densify=10, jacobi_clock_holders=11,
-               lsq_normal_fused=12, spmv_lanes=13)
+               lsq_normal_fused=12, spmv_lanes=13, rbf_fused=14)
 
     def set_option(self, name: str, value: int) -> None:
         _lib.check(self.lib.rlhip_set_option(self.h, self.OPT[name], int(value)), "set_option")
@@ -797,6 +802,58 @@ def rbf_apply(ctx: Context, X, rows_x, dim, bandwidth, B, n, alpha=1.0, beta=0.0
     rc = getattr(ctx.lib, f"rlhip_rbf_apply_{suf}")(ctx.h, rows_x, dim, X.data_ptr(), _ld(X), bandwidth, rg, max(len(regs), 1),
                                                    1 if eval_includes_reg else 0, n, alpha, B.data_ptr(), _ld(B), beta, C_.data_ptr(), _ld(C_))
     _lib.check(rc, "rbf_apply")
+    return C_
+
+
+# ---- the RBF kernel between two point sets and KRR prediction (rbf.hip).  Z (mz, ldz) and X (nx, ldx) are column-major point tensors like X
+#      above; B (n, ldb >= nx) and C (n, ldc >= mz) column-major.
+def rbf_cross_apply(ctx: Context, Z, X, rows_x, mz, nx, bandwidth, B, n, alpha=1.0, beta=0.0, C_=None):
+    """C (mz x n) = alpha K(Z, X) B + beta C (rlhip_rbf_cross_apply_*); returns C, column-major (n, mz) when allocated here"""
+    torch = _torch()
+    suf, _ = _suf(X)
+    if C_ is None:
+        C_ = torch.zeros((n, mz), dtype=X.dtype, device=X.device)
+    rc = getattr(ctx.lib, f"rlhip_rbf_cross_apply_{suf}")(ctx.h, rows_x, mz, Z.data_ptr(), _ld(Z), nx, X.data_ptr(), _ld(X), bandwidth, n, alpha,
+                                                         B.data_ptr(), max(_ld(B), 1), beta, C_.data_ptr(), max(_ld(C_), 1))
+    _lib.check(rc, "rbf_cross_apply")
+    return C_
+
+
+def sqexp_cross_submatrix(ctx: Context, Z, X, rows_x, mz, nx, rows_k, cols_k, ro, co, bandwidth, sq_colnorms_z=None, sq_colnorms_x=None):
+    """Ksub (cols_k, rows_k) column-major = K(Z(:, ro : ro + rows_k), X(:, co : co + cols_k)) (rlhip_sqexp_cross_submatrix_*)"""
+    torch = _torch()
+    suf, _ = _suf(X)
+    K = torch.empty((cols_k, rows_k), dtype=X.dtype, device=X.device)
+    rc = getattr(ctx.lib, f"rlhip_sqexp_cross_submatrix_{suf}")(ctx.h, rows_x, mz, Z.data_ptr(), _ld(Z), _ptr(sq_colnorms_z), nx, X.data_ptr(), _ld(X),
+                                                               _ptr(sq_colnorms_x), rows_k, cols_k, K.data_ptr(), max(rows_k, 1), ro, co, bandwidth)
+    _lib.check(rc, "sqexp_cross_submatrix")
+    return K
+
+
+def krr_predict(ctx: Context, Z, mz, Xp, rows_x, n, bandwidth, coeffs, s):
+    """RandLAPACK::krr_predict over linops::RBFCrossKernel: Y (mz x s) = K(Z, Xp) coeffs for the n training points Xp and the n x s
+    coefficient block of krill_full_rpchol.  Returns Y, column-major (s, mz)."""
+    torch = _torch()
+    suf, _ = _suf(Xp)
+    Y = torch.zeros((s, mz), dtype=Xp.dtype, device=Xp.device)
+    rc = getattr(ctx.lib, f"rlhip_drv_krr_predict_{suf}")(ctx.h, rows_x, mz, Z.data_ptr(), _ld(Z), n, Xp.data_ptr(), _ld(Xp), bandwidth, s,
+                                                         coeffs.data_ptr(), max(_ld(coeffs), 1), Y.data_ptr(), max(mz, 1))
+    _drv_check(ctx, rc, "krr_predict")
+    return Y
+
+
+def rbf_kernel_apply(ctx: Context, X, rows_x, dim, bandwidth, B, n, alpha=1.0, beta=0.0, C_=None, regs=(), eval_includes_reg=False,
+                     matrix_free=False):
+    """linops::RBFKernelMatrix::operator() through the C++ object, with set_matrix_free(matrix_free): same arguments as rbf_apply"""
+    torch = _torch()
+    suf, T = _suf(X)
+    if C_ is None:
+        C_ = torch.zeros((n, dim), dtype=X.dtype, device=X.device)
+    rg = (T * max(len(regs), 1))(*(list(regs) or [0.0]))
+    rc = getattr(ctx.lib, f"rlhip_drv_rbf_kernel_apply_{suf}")(ctx.h, X.data_ptr(), _ld(X), rows_x, dim, bandwidth, rg, max(len(regs), 1),
+                                                              1 if eval_includes_reg else 0, 1 if matrix_free else 0, n, alpha, B.data_ptr(),
+                                                              _ld(B), beta, C_.data_ptr(), _ld(C_))
+    _drv_check(ctx, rc, "rbf_kernel_apply")
     return C_
 
 
