@@ -12,6 +12,8 @@
 //   linops::RBFCrossKernel         the rectangular kernel K(Z, X) between two DEVICE point sets: operator(), matvec, submatrix
 //                                  (rlhip_rbf_cross_apply_*, rlhip_sqexp_cross_submatrix_*) -- what KRR prediction multiplies by;
 //   RBFKernelMatrix::set_matrix_free(true): operator() through the same kernels with Z = X (K never in memory); off by default.
+// Extension: the kernel function is a member of both operators, PDKernel::SquaredExp by default; set_kernel selects Matern 3/2
+// or 5/2 (rlhip_pdk_*).  rp_cholesky, rpchol_pc_data, krill_full_rpchol and krr_predict reach the kernel through these objects only.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -21,48 +23,65 @@
 
 namespace RandLAPACK {
 
+/// the kernel functions of the device library, as a function of s = |z - x|^2 and the bandwidth l (include/rlhip.h, RLHIP_PDK_*):
+/// exp(-s / (2 l^2)); (1 + a) exp(-a), a = sqrt(3 s) / l; (1 + a + a^2 / 3) exp(-a), a = sqrt(5 s) / l
+enum class PDKernel : int { SquaredExp = RLHIP_PDK_SQEXP, Matern32 = RLHIP_PDK_MATERN32, Matern52 = RLHIP_PDK_MATERN52 };
+
+// the squared exponential goes through the entries it always went through, the other kinds through their generalisations (the same code)
 namespace _pdk_impl {
 inline int sqexp_submatrix(blas::Queue& q, int64_t rx, int64_t cx, const double* X, int64_t ldx, const double* nr, int64_t r, int64_t c,
-                           double* K, int64_t ldk, int64_t ro, int64_t co, double h) {
-    return rlhip_sqexp_submatrix_f64(q.ctx(), rx, cx, X, ldx, nr, r, c, K, ldk, ro, co, h);
+                           double* K, int64_t ldk, int64_t ro, int64_t co, PDKernel kf, double h) {
+    return kf == PDKernel::SquaredExp ? rlhip_sqexp_submatrix_f64(q.ctx(), rx, cx, X, ldx, nr, r, c, K, ldk, ro, co, h)
+                                      : rlhip_pdk_submatrix_f64(q.ctx(), rx, cx, X, ldx, nr, r, c, K, ldk, ro, co, (int)kf, h);
 }
 inline int sqexp_submatrix(blas::Queue& q, int64_t rx, int64_t cx, const float* X, int64_t ldx, const float* nr, int64_t r, int64_t c,
-                           float* K, int64_t ldk, int64_t ro, int64_t co, float h) {
-    return rlhip_sqexp_submatrix_f32(q.ctx(), rx, cx, X, ldx, nr, r, c, K, ldk, ro, co, h);
+                           float* K, int64_t ldk, int64_t ro, int64_t co, PDKernel kf, float h) {
+    return kf == PDKernel::SquaredExp ? rlhip_sqexp_submatrix_f32(q.ctx(), rx, cx, X, ldx, nr, r, c, K, ldk, ro, co, h)
+                                      : rlhip_pdk_submatrix_f32(q.ctx(), rx, cx, X, ldx, nr, r, c, K, ldk, ro, co, (int)kf, h);
 }
 inline int sq_colnorms(blas::Queue& q, int64_t rx, int64_t cx, const double* X, int64_t ldx, double* nr) { return rlhip_sq_colnorms_f64(q.ctx(), rx, cx, X, ldx, nr); }
 inline int sq_colnorms(blas::Queue& q, int64_t rx, int64_t cx, const float* X, int64_t ldx, float* nr) { return rlhip_sq_colnorms_f32(q.ctx(), rx, cx, X, ldx, nr); }
-inline int columns(blas::Queue& q, int64_t rx, int64_t n, const double* X, int64_t ldx, int64_t nidx, const int64_t* idx, double h, double reg,
-                   double* out, int64_t ldo) {
-    return rlhip_sqexp_columns_f64(q.ctx(), rx, n, X, ldx, nidx, idx, h, reg, out, ldo);
+inline int columns(blas::Queue& q, int64_t rx, int64_t n, const double* X, int64_t ldx, int64_t nidx, const int64_t* idx, PDKernel kf, double h,
+                   double reg, double* out, int64_t ldo) {
+    return kf == PDKernel::SquaredExp ? rlhip_sqexp_columns_f64(q.ctx(), rx, n, X, ldx, nidx, idx, h, reg, out, ldo)
+                                      : rlhip_pdk_columns_f64(q.ctx(), rx, n, X, ldx, nidx, idx, (int)kf, h, reg, out, ldo);
 }
-inline int columns(blas::Queue& q, int64_t rx, int64_t n, const float* X, int64_t ldx, int64_t nidx, const int64_t* idx, float h, float reg,
-                   float* out, int64_t ldo) {
-    return rlhip_sqexp_columns_f32(q.ctx(), rx, n, X, ldx, nidx, idx, h, reg, out, ldo);
+inline int columns(blas::Queue& q, int64_t rx, int64_t n, const float* X, int64_t ldx, int64_t nidx, const int64_t* idx, PDKernel kf, float h,
+                   float reg, float* out, int64_t ldo) {
+    return kf == PDKernel::SquaredExp ? rlhip_sqexp_columns_f32(q.ctx(), rx, n, X, ldx, nidx, idx, h, reg, out, ldo)
+                                      : rlhip_pdk_columns_f32(q.ctx(), rx, n, X, ldx, nidx, idx, (int)kf, h, reg, out, ldo);
 }
-inline int apply(blas::Queue& q, int64_t rx, int64_t dim, const double* X, int64_t ldx, double h, const double* regs, int64_t nops, int eir,
-                 int64_t n, double a, const double* B, int64_t ldb, double b, double* C, int64_t ldc) {
-    return rlhip_rbf_apply_f64(q.ctx(), rx, dim, X, ldx, h, regs, nops, eir, n, a, B, ldb, b, C, ldc);
+inline int apply(blas::Queue& q, int64_t rx, int64_t dim, const double* X, int64_t ldx, PDKernel kf, double h, const double* regs, int64_t nops,
+                 int eir, int64_t n, double a, const double* B, int64_t ldb, double b, double* C, int64_t ldc) {
+    return kf == PDKernel::SquaredExp ? rlhip_rbf_apply_f64(q.ctx(), rx, dim, X, ldx, h, regs, nops, eir, n, a, B, ldb, b, C, ldc)
+                                      : rlhip_pdk_apply_f64(q.ctx(), rx, dim, X, ldx, (int)kf, h, regs, nops, eir, n, a, B, ldb, b, C, ldc);
 }
-inline int apply(blas::Queue& q, int64_t rx, int64_t dim, const float* X, int64_t ldx, float h, const float* regs, int64_t nops, int eir,
-                 int64_t n, float a, const float* B, int64_t ldb, float b, float* C, int64_t ldc) {
-    return rlhip_rbf_apply_f32(q.ctx(), rx, dim, X, ldx, h, regs, nops, eir, n, a, B, ldb, b, C, ldc);
+inline int apply(blas::Queue& q, int64_t rx, int64_t dim, const float* X, int64_t ldx, PDKernel kf, float h, const float* regs, int64_t nops,
+                 int eir, int64_t n, float a, const float* B, int64_t ldb, float b, float* C, int64_t ldc) {
+    return kf == PDKernel::SquaredExp ? rlhip_rbf_apply_f32(q.ctx(), rx, dim, X, ldx, h, regs, nops, eir, n, a, B, ldb, b, C, ldc)
+                                      : rlhip_pdk_apply_f32(q.ctx(), rx, dim, X, ldx, (int)kf, h, regs, nops, eir, n, a, B, ldb, b, C, ldc);
 }
-inline int cross_apply(blas::Queue& q, int64_t rx, int64_t mz, const double* Z, int64_t ldz, int64_t nx, const double* X, int64_t ldx, double h,
-                       int64_t n, double a, const double* B, int64_t ldb, double b, double* C, int64_t ldc) {
-    return rlhip_rbf_cross_apply_f64(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, h, n, a, B, ldb, b, C, ldc);
+inline int cross_apply(blas::Queue& q, int64_t rx, int64_t mz, const double* Z, int64_t ldz, int64_t nx, const double* X, int64_t ldx, PDKernel kf,
+                       double h, int64_t n, double a, const double* B, int64_t ldb, double b, double* C, int64_t ldc) {
+    return kf == PDKernel::SquaredExp ? rlhip_rbf_cross_apply_f64(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, h, n, a, B, ldb, b, C, ldc)
+                                      : rlhip_pdk_cross_apply_f64(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, (int)kf, h, n, a, B, ldb, b, C, ldc);
 }
-inline int cross_apply(blas::Queue& q, int64_t rx, int64_t mz, const float* Z, int64_t ldz, int64_t nx, const float* X, int64_t ldx, float h,
-                       int64_t n, float a, const float* B, int64_t ldb, float b, float* C, int64_t ldc) {
-    return rlhip_rbf_cross_apply_f32(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, h, n, a, B, ldb, b, C, ldc);
+inline int cross_apply(blas::Queue& q, int64_t rx, int64_t mz, const float* Z, int64_t ldz, int64_t nx, const float* X, int64_t ldx, PDKernel kf,
+                       float h, int64_t n, float a, const float* B, int64_t ldb, float b, float* C, int64_t ldc) {
+    return kf == PDKernel::SquaredExp ? rlhip_rbf_cross_apply_f32(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, h, n, a, B, ldb, b, C, ldc)
+                                      : rlhip_pdk_cross_apply_f32(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, (int)kf, h, n, a, B, ldb, b, C, ldc);
 }
 inline int cross_submatrix(blas::Queue& q, int64_t rx, int64_t mz, const double* Z, int64_t ldz, const double* nz, int64_t nx, const double* X,
-                           int64_t ldx, const double* nxr, int64_t r, int64_t c, double* K, int64_t ldk, int64_t ro, int64_t co, double h) {
-    return rlhip_sqexp_cross_submatrix_f64(q.ctx(), rx, mz, Z, ldz, nz, nx, X, ldx, nxr, r, c, K, ldk, ro, co, h);
+                           int64_t ldx, const double* nxr, int64_t r, int64_t c, double* K, int64_t ldk, int64_t ro, int64_t co, PDKernel kf,
+                           double h) {
+    return kf == PDKernel::SquaredExp ? rlhip_sqexp_cross_submatrix_f64(q.ctx(), rx, mz, Z, ldz, nz, nx, X, ldx, nxr, r, c, K, ldk, ro, co, h)
+                                      : rlhip_pdk_cross_submatrix_f64(q.ctx(), rx, mz, Z, ldz, nz, nx, X, ldx, nxr, r, c, K, ldk, ro, co, (int)kf, h);
 }
 inline int cross_submatrix(blas::Queue& q, int64_t rx, int64_t mz, const float* Z, int64_t ldz, const float* nz, int64_t nx, const float* X,
-                           int64_t ldx, const float* nxr, int64_t r, int64_t c, float* K, int64_t ldk, int64_t ro, int64_t co, float h) {
-    return rlhip_sqexp_cross_submatrix_f32(q.ctx(), rx, mz, Z, ldz, nz, nx, X, ldx, nxr, r, c, K, ldk, ro, co, h);
+                           int64_t ldx, const float* nxr, int64_t r, int64_t c, float* K, int64_t ldk, int64_t ro, int64_t co, PDKernel kf,
+                           float h) {
+    return kf == PDKernel::SquaredExp ? rlhip_sqexp_cross_submatrix_f32(q.ctx(), rx, mz, Z, ldz, nz, nx, X, ldx, nxr, r, c, K, ldk, ro, co, h)
+                                      : rlhip_pdk_cross_submatrix_f32(q.ctx(), rx, mz, Z, ldz, nz, nx, X, ldx, nxr, r, c, K, ldk, ro, co, (int)kf, h);
 }
 inline int axpby(blas::Queue& q, int64_t n, double a, const double* x, double b, double* y) { return rlhip_axpby_f64(q.ctx(), n, a, x, b, y); }
 inline int axpby(blas::Queue& q, int64_t n, float a, const float* x, float b, float* y) { return rlhip_axpby_f32(q.ctx(), n, a, x, b, y); }
@@ -75,7 +94,16 @@ void squared_exp_kernel_submatrix(int64_t rows_x, int64_t cols_x, const T* X, T*
                                   int64_t ro_ksub, int64_t co_ksub, T bandwidth, blas::Queue& q = blas::default_queue()) {
     randlapack_require(bandwidth > 0) << "kernel bandwidth must be > 0; got bandwidth=" << bandwidth;
     blas::check(_pdk_impl::sqexp_submatrix(q, rows_x, cols_x, X, rows_x, sq_colnorms_x, rows_ksub, cols_ksub, Ksub, rows_ksub > 0 ? rows_ksub : 1,
-                                           ro_ksub, co_ksub, bandwidth), "squared_exp_kernel_submatrix");
+                                           ro_ksub, co_ksub, PDKernel::SquaredExp, bandwidth), "squared_exp_kernel_submatrix");
+}
+
+/// the same block for any kernel function of PDKernel (the Matern kinds clamp the expanded squared distance at 0)
+template <typename T>
+void pd_kernel_submatrix(PDKernel kernel, int64_t rows_x, int64_t cols_x, const T* X, T* sq_colnorms_x, int64_t rows_ksub, int64_t cols_ksub, T* Ksub,
+                         int64_t ro_ksub, int64_t co_ksub, T bandwidth, blas::Queue& q = blas::default_queue()) {
+    randlapack_require(bandwidth > 0) << "kernel bandwidth must be > 0; got bandwidth=" << bandwidth;
+    blas::check(_pdk_impl::sqexp_submatrix(q, rows_x, cols_x, X, rows_x, sq_colnorms_x, rows_ksub, cols_ksub, Ksub, rows_ksub > 0 ? rows_ksub : 1,
+                                           ro_ksub, co_ksub, kernel, bandwidth), "pd_kernel_submatrix");
 }
 
 namespace linops {
@@ -93,6 +121,7 @@ struct RBFKernelMatrix {
     int64_t ldx;
     bool _eval_includes_reg;
     bool _matrix_free = false;
+    PDKernel kernel = PDKernel::SquaredExp;
     blas::Queue& q;
 
     using scalar_t = T;
@@ -109,6 +138,8 @@ struct RBFKernelMatrix {
     /// true: operator() multiplies through rlhip_rbf_cross_apply_* with Z = X (matrix-free inside that routine's fused limits) instead of
     /// rlhip_rbf_apply_*'s row blocks of K in scratch.  Off by default: the default path is the one that was measured.
     void set_matrix_free(bool mf) { _matrix_free = mf; }
+    /// the kernel function of every entry point of this operator: operator() on both branches, columns(); the diagonal is 1 for each
+    void set_kernel(PDKernel k) { kernel = k; }
 
     /// C (dim x n) = alpha * (K [+ diag(regs)]) * B + beta * C                                                            (:255-283)
     void operator()(blas::Layout layout, int64_t n, T alpha, T* const B, int64_t ldb, T beta, T* C, int64_t ldc) {
@@ -120,7 +151,8 @@ struct RBFKernelMatrix {
                                                              << " so each column gets its own regularization";
         }
         if (_matrix_free) {
-            blas::check(_pdk_impl::cross_apply(q, rows_x, dim, X, ldx, dim, X, ldx, bandwidth, n, alpha, B, ldb, beta, C, ldc), "RBFKernelMatrix");
+            blas::check(_pdk_impl::cross_apply(q, rows_x, dim, X, ldx, dim, X, ldx, kernel, bandwidth, n, alpha, B, ldb, beta, C, ldc),
+                        "RBFKernelMatrix");
             // the regularization term, exactly as rlhip_rbf_apply_* adds it: column i gets alpha * regs[min(i, num_ops - 1)] * B(:, i)
             for (int64_t i = 0; _eval_includes_reg && dim > 0 && i < n; ++i) {
                 const T coeff = alpha * regs[i < num_ops - 1 ? i : num_ops - 1];
@@ -128,8 +160,8 @@ struct RBFKernelMatrix {
             }
             return;
         }
-        blas::check(_pdk_impl::apply(q, rows_x, dim, X, ldx, bandwidth, regs, num_ops, _eval_includes_reg ? 1 : 0, n, alpha, B, ldb, beta, C, ldc),
-                    "RBFKernelMatrix");
+        blas::check(_pdk_impl::apply(q, rows_x, dim, X, ldx, kernel, bandwidth, regs, num_ops, _eval_includes_reg ? 1 : 0, n, alpha, B, ldb, beta, C,
+                                     ldc), "RBFKernelMatrix");
     }
 
     /// the diagonal (DEVICE, dim entries): 1, or 1 + regs[0] when the evaluation includes the regularization (operator()(i, i), :285-292)
@@ -139,7 +171,7 @@ struct RBFKernelMatrix {
     }
     /// out(:, l) = K(:, idx_dev[l]) (+ regs[0] on the diagonal), DEVICE indices and output (dim x nidx, ldo)
     void columns(int64_t nidx, const int64_t* idx_dev, T* out, int64_t ldo) {
-        blas::check(_pdk_impl::columns(q, rows_x, dim, X, ldx, nidx, idx_dev, bandwidth, diag_reg(), out, ldo), "RBFKernelMatrix::columns");
+        blas::check(_pdk_impl::columns(q, rows_x, dim, X, ldx, nidx, idx_dev, kernel, bandwidth, diag_reg(), out, ldo), "RBFKernelMatrix::columns");
     }
 
 private:
@@ -151,7 +183,7 @@ private:
 };
 
 /// The rectangular kernel K(Z, X) (mz x nx) between two DEVICE point sets, Z rows_x x mz (ldz, default rows_x) and X rows_x x nx (ldx,
-/// default rows_x), one column per point: K(i, j) = exp(-|Z(:,i) - X(:,j)|^2 / (2 h^2)).  Z == X is allowed.  ColMajor only.  This is
+/// default rows_x), one column per point: K(i, j) = exp(-|Z(:,i) - X(:,j)|^2 / (2 h^2)), or the Matern kind chosen by set_kernel.  Z == X is allowed.  ColMajor only.  This is
 /// the operator of KRR prediction (krr_predict, rl_krill.hh), not a full LinearOperator: Side, trans_B and the sketch-operator overloads of
 /// that concept are not provided.
 template <typename T>
@@ -163,9 +195,12 @@ struct RBFCrossKernel {
     const T* X;
     T bandwidth;
     int64_t ldz, ldx;
+    PDKernel kernel = PDKernel::SquaredExp;
     blas::Queue& q;
 
     using scalar_t = T;
+
+    void set_kernel(PDKernel k) { kernel = k; }
 
     RBFCrossKernel(int64_t rows_x, int64_t mz, const T* Z, int64_t nx, const T* X, T bandwidth, blas::Queue& queue = blas::default_queue(),
                    int64_t ldz = 0, int64_t ldx = 0)
@@ -186,8 +221,8 @@ struct RBFCrossKernel {
         randlapack_require(ldb >= cols) << "ldb=" << ldb << " < " << cols << " (ldb must be >= the columns of op(K))";
         randlapack_require(ldc >= rows) << "ldc=" << ldc << " < " << rows << " (ldc must be >= the rows of op(K))";
         const int64_t ldb1 = ldb > 0 ? ldb : 1, ldc1 = ldc > 0 ? ldc : 1;
-        blas::check(tr ? _pdk_impl::cross_apply(q, rows_x, n_cols, X, ldx, n_rows, Z, ldz, bandwidth, n, alpha, B, ldb1, beta, C, ldc1)
-                       : _pdk_impl::cross_apply(q, rows_x, n_rows, Z, ldz, n_cols, X, ldx, bandwidth, n, alpha, B, ldb1, beta, C, ldc1),
+        blas::check(tr ? _pdk_impl::cross_apply(q, rows_x, n_cols, X, ldx, n_rows, Z, ldz, kernel, bandwidth, n, alpha, B, ldb1, beta, C, ldc1)
+                       : _pdk_impl::cross_apply(q, rows_x, n_rows, Z, ldz, n_cols, X, ldx, kernel, bandwidth, n, alpha, B, ldb1, beta, C, ldc1),
                     "RBFCrossKernel");
     }
 
@@ -201,7 +236,7 @@ struct RBFCrossKernel {
     void submatrix(int64_t rows_ksub, int64_t cols_ksub, T* Ksub, int64_t ro_ksub, int64_t co_ksub, int64_t ldk = 0) {
         if (ldk <= 0) ldk = rows_ksub > 0 ? rows_ksub : 1;
         blas::check(_pdk_impl::cross_submatrix(q, rows_x, n_rows, Z, ldz, (const T*)nullptr, n_cols, X, ldx, (const T*)nullptr, rows_ksub, cols_ksub,
-                                               Ksub, ldk, ro_ksub, co_ksub, bandwidth), "RBFCrossKernel::submatrix");
+                                               Ksub, ldk, ro_ksub, co_ksub, kernel, bandwidth), "RBFCrossKernel::submatrix");
     }
 };
 

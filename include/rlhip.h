@@ -447,6 +447,59 @@ int rlhip_rbf_apply_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t dim, const doubl
 int rlhip_rbf_apply_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t dim, const float* X, int64_t ldx, float bandwidth, const float* regs_host,
                         int64_t num_ops, int eval_includes_reg, int64_t n, float alpha, const float* B, int64_t ldb, float beta, float* C,
                         int64_t ldc);
+/* ---- the kernel function as an argument: the squared exponential and the Matern kernels of order 3/2 and 5/2 (a designed extension,
+ *      DESIGN 4.23; the reference has the squared exponential only).  With s = |z - x|^2 and l = bandwidth > 0:
+ *        RLHIP_PDK_SQEXP     exp(-s / (2 l^2))                                            what every rlhip_sqexp_* / rlhip_rbf_* entry computes
+ *        RLHIP_PDK_MATERN32  (1 + a) exp(-a),            a = sqrt(3) sqrt(s) / l
+ *        RLHIP_PDK_MATERN52  (1 + a + a^2 / 3) exp(-a),  a = sqrt(5) sqrt(s) / l
+ *      Each rlhip_pdk_* entry is the entry it generalises (columns <- rlhip_sqexp_columns, submatrix <- rlhip_sqexp_submatrix, apply <-
+ *      rlhip_rbf_apply, cross_submatrix <- rlhip_sqexp_cross_submatrix, cross_apply <- rlhip_rbf_cross_apply) with `int kernel` in front of
+ *      the bandwidth: the same routes, route counters (rlhip_rbf_path_count), options (RLHIP_OPT_RBF_FUSED), fused limits and scratch.  The
+ *      argument codes are the positions in the NEW list: those of `kernel` itself (an unknown kind) and of every argument behind it are one
+ *      larger than the older entry's.  With RLHIP_PDK_SQEXP an rlhip_pdk_* entry returns the bits of the older entry, which is a call of it.
+ *      Evaluation of the Matern kinds, the same on every route:
+ *        - c = sqrt(3) / l or sqrt(5) / l is computed in double and rounded once to T; so is 1 / 3;
+ *        - on the norm-expansion routes (submatrix, apply, cross_submatrix, cross_apply) s = (|z_i|^2 + |x_j|^2) - 2 z_i^T x_j is clamped by
+ *          s < 0 ? 0 : s -- a select, not fmax, so a NaN coordinate still gives a NaN entry;
+ *        - a = c * sqrt(s) with the accurate sqrt / sqrtf;
+ *        - the polynomial in Horner form, one fused multiply-add per step: 1 + a, and 1 + a * (1 + a * (1 / 3));
+ *        - times the accurate exp(-a) / expf(-a).
+ *      The fused and the composed route of cross_apply use this one formula and differ in the order of the sums only.  rlhip_pdk_columns_*
+ *      evaluates s by differences, as rlhip_sqexp_columns_* does: its entries i == idx[l] are exactly 1 + reg for every kind.  A point of X
+ *      past nx contributes exactly 0 in the fused kernel: a finite K times a staged zero of B.
+ *      The absolute error of the expanded s is about eps (|z|^2 + |x|^2); |dK/ds| <= 1 / (2 l^2), 3 / (2 l^2), 5 / (6 l^2) for the three
+ *      kinds, so an entry is off by about eps (1 + L (|z|^2 + |x|^2)).  Matern 1/2, exp(-sqrt(s) / l), is NOT offered: its derivative in s is
+ *      unbounded at s = 0, and the expansion would cost it half the digits near coincident points, the diagonal of K(X, X) included. */
+#define RLHIP_PDK_SQEXP 0
+#define RLHIP_PDK_MATERN32 1
+#define RLHIP_PDK_MATERN52 2
+int rlhip_pdk_columns_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t n, const double* X, int64_t ldx, int64_t nidx, const int64_t* idx_dev, int kernel,
+                          double bandwidth, double reg, double* out, int64_t ldo);
+int rlhip_pdk_columns_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t n, const float* X, int64_t ldx, int64_t nidx, const int64_t* idx_dev, int kernel,
+                          float bandwidth, float reg, float* out, int64_t ldo);
+int rlhip_pdk_submatrix_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t cols_x, const double* X, int64_t ldx, const double* sq_colnorms_x,
+                            int64_t rows_ksub, int64_t cols_ksub, double* Ksub, int64_t ldk, int64_t ro_ksub, int64_t co_ksub, int kernel,
+                            double bandwidth);
+int rlhip_pdk_submatrix_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t cols_x, const float* X, int64_t ldx, const float* sq_colnorms_x,
+                            int64_t rows_ksub, int64_t cols_ksub, float* Ksub, int64_t ldk, int64_t ro_ksub, int64_t co_ksub, int kernel,
+                            float bandwidth);
+int rlhip_pdk_apply_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t dim, const double* X, int64_t ldx, int kernel, double bandwidth,
+                        const double* regs_host, int64_t num_ops, int eval_includes_reg, int64_t n, double alpha, const double* B, int64_t ldb,
+                        double beta, double* C, int64_t ldc);
+int rlhip_pdk_apply_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t dim, const float* X, int64_t ldx, int kernel, float bandwidth,
+                        const float* regs_host, int64_t num_ops, int eval_includes_reg, int64_t n, float alpha, const float* B, int64_t ldb,
+                        float beta, float* C, int64_t ldc);
+int rlhip_pdk_cross_submatrix_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, const double* sq_colnorms_z, int64_t nx,
+                                  const double* X, int64_t ldx, const double* sq_colnorms_x, int64_t rows_ksub, int64_t cols_ksub, double* Ksub,
+                                  int64_t ldk, int64_t ro_ksub, int64_t co_ksub, int kernel, double bandwidth);
+int rlhip_pdk_cross_submatrix_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, const float* sq_colnorms_z, int64_t nx,
+                                  const float* X, int64_t ldx, const float* sq_colnorms_x, int64_t rows_ksub, int64_t cols_ksub, float* Ksub,
+                                  int64_t ldk, int64_t ro_ksub, int64_t co_ksub, int kernel, float bandwidth);
+int rlhip_pdk_cross_apply_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t nx, const double* X, int64_t ldx,
+                              int kernel, double bandwidth, int64_t n, double alpha, const double* B, int64_t ldb, double beta, double* C,
+                              int64_t ldc);
+int rlhip_pdk_cross_apply_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t nx, const float* X, int64_t ldx,
+                              int kernel, float bandwidth, int64_t n, float alpha, const float* B, int64_t ldb, float beta, float* C, int64_t ldc);
 /* rlhip_sample_indices_iid_*: RandBLAS::weights_to_cdf + sample_indices_iid as rp_cholesky calls them (rl_rpchol.hh:64, 131, 141-143).
  * RandBLAS is absent, so the stream is this library's own:
  *   weights   w_i = max(d_i, 0) (d: n DEVICE weights); all sums in double for both precisions, in this fixed order:

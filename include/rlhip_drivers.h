@@ -270,6 +270,29 @@ int rlhip_drv_rbf_kernel_apply_f64(rlhip_ctx* ctx, const double* X_pts, int64_t 
 int rlhip_drv_rbf_kernel_apply_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, float bandwidth,
                                    const float* regs_host, int64_t num_ops, int eval_includes_reg, int matrix_free, int64_t n, float alpha,
                                    const float* B, int64_t ldb, float beta, float* C, int64_t ldc);
+/* The four RBF drivers above with the kernel function as an argument (RLHIP_PDK_*, include/rlhip.h): `int kernel` in front of the bandwidth, passed
+ * to the object by set_kernel; everything behind the object -- rp_cholesky, rpchol_pc_data, pcg, krr_predict -- is the same code.  An unknown kind
+ * returns -(position of kernel): -6, -6, -9, -6. */
+int rlhip_drv_rpchol_pdk_f64(rlhip_ctx* ctx, const double* X, int64_t ldx, int64_t rows_x, int64_t n, int kernel, double bandwidth, double reg,
+                             int64_t* k, int64_t b, int64_t* S_host, double* F, int64_t ldf, uint32_t state[6], int status[2]);
+int rlhip_drv_rpchol_pdk_f32(rlhip_ctx* ctx, const float* X, int64_t ldx, int64_t rows_x, int64_t n, int kernel, float bandwidth, float reg,
+                             int64_t* k, int64_t b, int64_t* S_host, float* F, int64_t ldf, uint32_t state[6], int status[2]);
+int rlhip_drv_krill_full_rpchol_pdk_f64(rlhip_ctx* ctx, const double* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, double bandwidth,
+                                        const double* regs_host, int64_t num_ops, const double* H, double* X, int64_t s, double tol, int64_t max_iters,
+                                        int64_t* k, int64_t b, uint32_t state[6], int64_t* iters, double* hist);
+int rlhip_drv_krill_full_rpchol_pdk_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, float bandwidth,
+                                        const float* regs_host, int64_t num_ops, const float* H, float* X, int64_t s, float tol, int64_t max_iters,
+                                        int64_t* k, int64_t b, uint32_t state[6], int64_t* iters, float* hist);
+int rlhip_drv_krr_predict_pdk_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t n, const double* X_pts, int64_t ldx,
+                                  int kernel, double bandwidth, int64_t s, const double* coeffs, int64_t ldcoef, double* Y, int64_t ldy);
+int rlhip_drv_krr_predict_pdk_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t n, const float* X_pts, int64_t ldx,
+                                  int kernel, float bandwidth, int64_t s, const float* coeffs, int64_t ldcoef, float* Y, int64_t ldy);
+int rlhip_drv_pdk_kernel_apply_f64(rlhip_ctx* ctx, const double* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, int kernel, double bandwidth,
+                                   const double* regs_host, int64_t num_ops, int eval_includes_reg, int matrix_free, int64_t n, double alpha,
+                                   const double* B, int64_t ldb, double beta, double* C, int64_t ldc);
+int rlhip_drv_pdk_kernel_apply_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, int kernel, float bandwidth,
+                                   const float* regs_host, int64_t num_ops, int eval_includes_reg, int matrix_free, int64_t n, float alpha,
+                                   const float* B, int64_t ldb, float beta, float* C, int64_t ldc);
 /* posm_square (comps/rl_determiter.hh:231-282) as the C++ layer runs it: rlhip_posm_square_* and, after a failed pivot, the eigenvalue fallback on
  * the host.  LHS, RHS: s x s DEVICE, ld s.  *code = rank(LHS), -(s + 1) not positive semidefinite, -(s + 2) zero up to rounding. */
 int rlhip_drv_posm_square_f64(rlhip_ctx* ctx, int64_t s, const double* LHS, double* RHS, int diag_only, int64_t* code);

@@ -279,6 +279,15 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the RBF kernel between 
         f"rlhip_drv_krr_predict_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, _T, c_i64, c_vp, c_i64, c_vp, c_i64]),
     })
 
+for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the kernel function as an argument: every entry above that evaluates the kernel, with `int kernel` in front of the bandwidth
+    for _new, _old in (("rlhip_pdk_columns", "rlhip_sqexp_columns"), ("rlhip_pdk_submatrix", "rlhip_sqexp_submatrix"), ("rlhip_pdk_apply", "rlhip_rbf_apply"),
+                       ("rlhip_pdk_cross_submatrix", "rlhip_sqexp_cross_submatrix"), ("rlhip_pdk_cross_apply", "rlhip_rbf_cross_apply"),
+                       ("rlhip_drv_rpchol_pdk", "rlhip_drv_rpchol_rbf"), ("rlhip_drv_krill_full_rpchol_pdk", "rlhip_drv_krill_full_rpchol_rbf"),
+                       ("rlhip_drv_krr_predict_pdk", "rlhip_drv_krr_predict"), ("rlhip_drv_pdk_kernel_apply", "rlhip_drv_rbf_kernel_apply")):
+        _rt, _args = SIGNATURES[f"{_old}_{_suf}"]
+        _at = _args.index(_T)                                # the bandwidth is the first scalar of type T in each of these lists
+        SIGNATURES[f"{_new}_{_suf}"] = (_rt, _args[:_at] + [c_int] + _args[_at:])
+
 _lib = None
 
 

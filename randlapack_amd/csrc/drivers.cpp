@@ -732,13 +732,17 @@ int drv_rpchol(KOP& A, int64_t n, int64_t* k, int64_t b, int64_t* S_host, T* F, 
     status[1] = r.c_status;
     return 0;
 }
+// the kernel function of the *_pdk_* drivers (RLHIP_PDK_*); the *_rbf_* drivers pass the squared exponential
+inline bool pdk_known(int kernel) { return kernel >= RLHIP_PDK_SQEXP && kernel <= RLHIP_PDK_MATERN52; }
 template <typename T>
-int drv_rpchol_rbf(rlhip_ctx* ctx, const T* X, int64_t ldx, int64_t rows_x, int64_t n, T bandwidth, T reg, int64_t* k, int64_t b, int64_t* S_host,
-                   T* F, int64_t ldf, uint32_t state[6], int status[2]) {
+int drv_rpchol_rbf(rlhip_ctx* ctx, const T* X, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth, T reg, int64_t* k, int64_t b,
+                   int64_t* S_host, T* F, int64_t ldf, uint32_t state[6], int status[2]) {
+    if (!pdk_known(kernel)) return -6;
     return guarded([&] {
         blas::Queue q(ctx);
         std::vector<T> regs{reg};
         lo::RBFKernelMatrix<T> A(n, X, rows_x, bandwidth, regs, q, ldx);
+        A.set_kernel((RandLAPACK::PDKernel)kernel);
         A.set_eval_includes_reg(true);
         return drv_rpchol<T>(A, n, k, b, S_host, F, ldf, state, status);
     });
@@ -770,11 +774,19 @@ int drv_rpchol_pc_data_rbf(rlhip_ctx* ctx, const T* X, int64_t ldx, int64_t rows
 
 int rlhip_drv_rpchol_rbf_f64(rlhip_ctx* ctx, const double* X, int64_t ldx, int64_t rows_x, int64_t n, double bandwidth, double reg, int64_t* k,
                              int64_t b, int64_t* S_host, double* F, int64_t ldf, uint32_t state[6], int status[2]) {
-    return drv_rpchol_rbf<double>(ctx, X, ldx, rows_x, n, bandwidth, reg, k, b, S_host, F, ldf, state, status);
+    return drv_rpchol_rbf<double>(ctx, X, ldx, rows_x, n, RLHIP_PDK_SQEXP, bandwidth, reg, k, b, S_host, F, ldf, state, status);
+}
+int rlhip_drv_rpchol_pdk_f64(rlhip_ctx* ctx, const double* X, int64_t ldx, int64_t rows_x, int64_t n, int kernel, double bandwidth, double reg,
+                             int64_t* k, int64_t b, int64_t* S_host, double* F, int64_t ldf, uint32_t state[6], int status[2]) {
+    return drv_rpchol_rbf<double>(ctx, X, ldx, rows_x, n, kernel, bandwidth, reg, k, b, S_host, F, ldf, state, status);
 }
 int rlhip_drv_rpchol_rbf_f32(rlhip_ctx* ctx, const float* X, int64_t ldx, int64_t rows_x, int64_t n, float bandwidth, float reg, int64_t* k,
                              int64_t b, int64_t* S_host, float* F, int64_t ldf, uint32_t state[6], int status[2]) {
-    return drv_rpchol_rbf<float>(ctx, X, ldx, rows_x, n, bandwidth, reg, k, b, S_host, F, ldf, state, status);
+    return drv_rpchol_rbf<float>(ctx, X, ldx, rows_x, n, RLHIP_PDK_SQEXP, bandwidth, reg, k, b, S_host, F, ldf, state, status);
+}
+int rlhip_drv_rpchol_pdk_f32(rlhip_ctx* ctx, const float* X, int64_t ldx, int64_t rows_x, int64_t n, int kernel, float bandwidth, float reg,
+                             int64_t* k, int64_t b, int64_t* S_host, float* F, int64_t ldf, uint32_t state[6], int status[2]) {
+    return drv_rpchol_rbf<float>(ctx, X, ldx, rows_x, n, kernel, bandwidth, reg, k, b, S_host, F, ldf, state, status);
 }
 int rlhip_drv_rpchol_dense_f64(rlhip_ctx* ctx, int64_t n, const double* A, int64_t lda, int64_t* k, int64_t b, int64_t* S_host, double* F,
                                int64_t ldf, uint32_t state[6], int status[2]) {
@@ -840,14 +852,16 @@ int drv_pcg_rbf(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int
     });
 }
 template <typename T>
-int drv_krill_rbf(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, T bandwidth, const T* regs_host, int64_t num_ops, const T* H,
-                  T* X, int64_t s, T tol, int64_t max_iters, int64_t* k, int64_t b, uint32_t state[6], int64_t* iters, T* hist) {
+int drv_krill_rbf(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth, const T* regs_host, int64_t num_ops,
+                  const T* H, T* X, int64_t s, T tol, int64_t max_iters, int64_t* k, int64_t b, uint32_t state[6], int64_t* iters, T* hist) {
+    if (!pdk_known(kernel)) return -6;
     return guarded([&] {
         blas::Queue q(ctx);
         if (!regs_host || num_ops < 1) throw RandLAPACK::Error("krill: regs_host must hold num_ops >= 1 regularization parameters");
         if (!k || !state) throw RandLAPACK::Error("krill: k and state must not be null");
         std::vector<T> mus(regs_host, regs_host + num_ops);
         lo::RBFKernelMatrix<T> G(n, X_pts, rows_x, bandwidth, mus, q, ldx);
+        G.set_kernel((RandLAPACK::PDKernel)kernel);
         RandLAPACK::StatefulFrobeniusNorm<T> sn(q);
         State st = load_state(state);
         int64_t it = 0, kk = *k;
@@ -872,23 +886,28 @@ int drv_posm_square(rlhip_ctx* ctx, int64_t s, const T* LHS, T* RHS, int diag_on
     });
 }
 template <typename T>
-int drv_krr_predict(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts, int64_t ldx, T bandwidth, int64_t s,
-                    const T* coeffs, int64_t ldcoef, T* Y, int64_t ldy) {
+int drv_krr_predict(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts, int64_t ldx, int kernel, T bandwidth,
+                    int64_t s, const T* coeffs, int64_t ldcoef, T* Y, int64_t ldy) {
+    if (!pdk_known(kernel)) return -9;
     return guarded([&] {
         blas::Queue q(ctx);
         lo::RBFCrossKernel<T> Kzx(rows_x, mz, Z, n, X_pts, bandwidth, q, ldz, ldx);
+        Kzx.set_kernel((RandLAPACK::PDKernel)kernel);
         RandLAPACK::krr_predict(Kzx, s, coeffs, ldcoef, Y, ldy);
         return 0;
     });
 }
 template <typename T>
-int drv_rbf_kernel_apply(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, T bandwidth, const T* regs_host, int64_t num_ops,
-                         int eval_includes_reg, int matrix_free, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {
+int drv_rbf_kernel_apply(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, int kernel, T bandwidth, const T* regs_host,
+                         int64_t num_ops, int eval_includes_reg, int matrix_free, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C,
+                         int64_t ldc) {
+    if (!pdk_known(kernel)) return -6;
     return guarded([&] {
         blas::Queue q(ctx);
         if (!regs_host || num_ops < 1) throw RandLAPACK::Error("rbf_kernel_apply: regs_host must hold num_ops >= 1 regularization parameters");
         std::vector<T> mus(regs_host, regs_host + num_ops);
         lo::RBFKernelMatrix<T> G(dim, X_pts, rows_x, bandwidth, mus, q, ldx);
+        G.set_kernel((RandLAPACK::PDKernel)kernel);
         G.set_eval_includes_reg(eval_includes_reg != 0);
         G.set_matrix_free(matrix_free != 0);
         G(blas::Layout::ColMajor, n, alpha, const_cast<T*>(B), ldb, beta, C, ldc);
@@ -913,17 +932,34 @@ extern "C" {
     int rlhip_drv_krill_full_rpchol_rbf_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, T bandwidth,                \
                                               const T* regs_host, int64_t num_ops, const T* H, T* X, int64_t s, T tol, int64_t max_iters,         \
                                               int64_t* k, int64_t b, uint32_t state[6], int64_t* iters, T* hist) {                                \
-        return drv_krill_rbf<T>(ctx, X_pts, ldx, rows_x, n, bandwidth, regs_host, num_ops, H, X, s, tol, max_iters, k, b, state, iters, hist);    \
+        return drv_krill_rbf<T>(ctx, X_pts, ldx, rows_x, n, RLHIP_PDK_SQEXP, bandwidth, regs_host, num_ops, H, X, s, tol, max_iters, k, b, state,  \
+                                iters, hist);                                                                                                     \
+    }                                                                                                                                             \
+    int rlhip_drv_krill_full_rpchol_pdk_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth,    \
+                                              const T* regs_host, int64_t num_ops, const T* H, T* X, int64_t s, T tol, int64_t max_iters,         \
+                                              int64_t* k, int64_t b, uint32_t state[6], int64_t* iters, T* hist) {                                \
+        return drv_krill_rbf<T>(ctx, X_pts, ldx, rows_x, n, kernel, bandwidth, regs_host, num_ops, H, X, s, tol, max_iters, k, b, state, iters,   \
+                                hist);                                                                                                            \
     }                                                                                                                                             \
     int rlhip_drv_krr_predict_##SUF(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts, int64_t ldx,  \
                                     T bandwidth, int64_t s, const T* coeffs, int64_t ldcoef, T* Y, int64_t ldy) {                                 \
-        return drv_krr_predict<T>(ctx, rows_x, mz, Z, ldz, n, X_pts, ldx, bandwidth, s, coeffs, ldcoef, Y, ldy);                                  \
+        return drv_krr_predict<T>(ctx, rows_x, mz, Z, ldz, n, X_pts, ldx, RLHIP_PDK_SQEXP, bandwidth, s, coeffs, ldcoef, Y, ldy);                 \
+    }                                                                                                                                             \
+    int rlhip_drv_krr_predict_pdk_##SUF(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts,           \
+                                        int64_t ldx, int kernel, T bandwidth, int64_t s, const T* coeffs, int64_t ldcoef, T* Y, int64_t ldy) {    \
+        return drv_krr_predict<T>(ctx, rows_x, mz, Z, ldz, n, X_pts, ldx, kernel, bandwidth, s, coeffs, ldcoef, Y, ldy);                          \
     }                                                                                                                                             \
     int rlhip_drv_rbf_kernel_apply_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, T bandwidth,                   \
                                          const T* regs_host, int64_t num_ops, int eval_includes_reg, int matrix_free, int64_t n, T alpha,         \
                                          const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {                                                    \
-        return drv_rbf_kernel_apply<T>(ctx, X_pts, ldx, rows_x, dim, bandwidth, regs_host, num_ops, eval_includes_reg, matrix_free, n, alpha, B,  \
-                                       ldb, beta, C, ldc);                                                                                        \
+        return drv_rbf_kernel_apply<T>(ctx, X_pts, ldx, rows_x, dim, RLHIP_PDK_SQEXP, bandwidth, regs_host, num_ops, eval_includes_reg,           \
+                                       matrix_free, n, alpha, B, ldb, beta, C, ldc);                                                              \
+    }                                                                                                                                             \
+    int rlhip_drv_pdk_kernel_apply_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, int kernel, T bandwidth,       \
+                                         const T* regs_host, int64_t num_ops, int eval_includes_reg, int matrix_free, int64_t n, T alpha,         \
+                                         const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {                                                    \
+        return drv_rbf_kernel_apply<T>(ctx, X_pts, ldx, rows_x, dim, kernel, bandwidth, regs_host, num_ops, eval_includes_reg, matrix_free, n,    \
+                                       alpha, B, ldb, beta, C, ldc);                                                                              \
     }                                                                                                                                             \
     int rlhip_drv_posm_square_##SUF(rlhip_ctx* ctx, int64_t s, const T* LHS, T* RHS, int diag_only, int64_t* code) {                              \
         return drv_posm_square<T>(ctx, s, LHS, RHS, diag_only, code);                                                                             \

@@ -7,6 +7,9 @@
 //                      arena, cross submatrix + GEMM with B per block -- rbf_apply's scheme for two point sets.
 // Both routes evaluate an entry by the same formula, exp(scale * ((|z_i|^2 + |x_j|^2) - 2 z_i.x_j)), scale = -1 / (2 h^2) rounded from
 // double, the accurate exp / expf, no clamp; they differ in the order of the sums only.
+//   rlhip_pdk_cross_submatrix_*, rlhip_pdk_cross_apply_*: the same two routines with the kernel function as an argument.  The
+//       Matern kinds evaluate matern_of_s (rlhip_device.h) where the squared exponential evaluates exp, on both routes: the squared distance
+//       clamped at 0, a sqrt, two fused multiply-adds, an exp.
 //
 // The fused kernel.  A 256-thread workgroup owns 64 points of Z, 16 per wave; lane (g = lane >> 4, c = lane & 15) of a wave holds, for
 // its wave's point c, the Z rows 4 kk + g (times -2, exact) in registers for the whole loop.  X is walked in tiles of TP points that are
@@ -26,6 +29,7 @@
 
 namespace {
 using namespace rlhip_dev;
+using rlhip::PdkFn;
 
 constexpr int RBF_WG = 256;
 constexpr int RBF_ZP = 64;                  // points of Z per workgroup
@@ -54,10 +58,12 @@ struct RbfArgs {
     const T* zn; const T* xn;      // |Z(:, i)|^2, |X(:, j)|^2
     const T* B; int64_t ldb;
     T* C; int64_t ldc;
-    T alpha, beta, scale;
+    T alpha, beta, scale, third;      // scale, third: PdkFn's constants
 };
 
-template <typename T, int KS, int NT>
+// MATERN = false is the squared exponential, true the two Matern kinds (told apart by a.third alone, matern_of_s): the squared exponential
+// keeps an instantiation of its own, so the sqrt and the polynomial cost it no register.
+template <typename T, int KS, int NT, bool MATERN>
 __global__ __launch_bounds__(RBF_WG) void rbf_fused_kernel(const RbfArgs<T> a) {
     using M = Mfma16x4<T>;
     using acc_t = typename M::acc_t;
@@ -138,7 +144,11 @@ __global__ __launch_bounds__(RBF_WG) void rbf_fused_kernel(const RbfArgs<T> a) {
             if (st + 1 < TP / 16) snext = first(st + 1);      // the matrix pipe runs this beside the exps below
             T p[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) p[r] = rbf_exp(a.scale * ((znorm + Ns[16 * st + M::drow_g(g, r)]) + s[r]));
+            for (int r = 0; r < 4; ++r) {
+                const T sq = (znorm + Ns[16 * st + M::drow_g(g, r)]) + s[r];
+                if constexpr (MATERN) p[r] = matern_of_s(sq, a.scale, a.third);
+                else p[r] = rbf_exp(a.scale * sq);
+            }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 const T* bc = Bs + (16 * nt + c) * BSP + 16 * st;      // column 16 nt + c of the B tile, this sub-tile's points
@@ -183,29 +193,29 @@ __global__ void rbf_scale_kernel(int64_t m, int64_t n, T beta, T* __restrict__ C
     *q = beta == T(0) ? T(0) : beta * *q;
 }
 
-template <typename T, int KS, int NT>
+template <typename T, int KS, int NT, bool MATERN>
 int launch_fused(rlhip_ctx* c, const RbfArgs<T>& a) {
     constexpr size_t bytes = 2 * (size_t)rbf_tile_elems<T, KS, NT>(rbf_tp<T, KS, NT>()) * sizeof(T);
     static_assert(bytes <= (size_t)RBF_LDS_CAP, "fused RBF kernel: the two staging buffers exceed the LDS budget");
     const int64_t wgs = (a.mz + RBF_ZP - 1) / RBF_ZP;
-    hipLaunchKernelGGL((rbf_fused_kernel<T, KS, NT>), dim3((unsigned)wgs), dim3(RBF_WG), bytes, c->stream, a);
+    hipLaunchKernelGGL((rbf_fused_kernel<T, KS, NT, MATERN>), dim3((unsigned)wgs), dim3(RBF_WG), bytes, c->stream, a);
     RLHIP_LAUNCH_CHECK();
     return 0;
 }
-template <typename T, int KS>
+template <typename T, int KS, bool MATERN>
 int launch_fused_n(rlhip_ctx* c, const RbfArgs<T>& a) {
-    if (a.n <= 16) return launch_fused<T, KS, 1>(c, a);
-    if (a.n <= 32) return launch_fused<T, KS, 2>(c, a);
-    return launch_fused<T, KS, 4>(c, a);
+    if (a.n <= 16) return launch_fused<T, KS, 1, MATERN>(c, a);
+    if (a.n <= 32) return launch_fused<T, KS, 2, MATERN>(c, a);
+    return launch_fused<T, KS, 4, MATERN>(c, a);
 }
-template <typename T>
+template <typename T, bool MATERN>
 int launch_fused_rows(rlhip_ctx* c, const RbfArgs<T>& a) {      // KS = rows_x / 4 rounded up to a power of two (zero rows add exactly 0)
-    if (a.rows_x <= 4) return launch_fused_n<T, 1>(c, a);
-    if (a.rows_x <= 8) return launch_fused_n<T, 2>(c, a);
-    if (a.rows_x <= 16) return launch_fused_n<T, 4>(c, a);
-    if (a.rows_x <= 32) return launch_fused_n<T, 8>(c, a);
-    if (a.rows_x <= 64) return launch_fused_n<T, 16>(c, a);
-    return launch_fused_n<T, 32>(c, a);
+    if (a.rows_x <= 4) return launch_fused_n<T, 1, MATERN>(c, a);
+    if (a.rows_x <= 8) return launch_fused_n<T, 2, MATERN>(c, a);
+    if (a.rows_x <= 16) return launch_fused_n<T, 4, MATERN>(c, a);
+    if (a.rows_x <= 32) return launch_fused_n<T, 8, MATERN>(c, a);
+    if (a.rows_x <= 64) return launch_fused_n<T, 16, MATERN>(c, a);
+    return launch_fused_n<T, 32, MATERN>(c, a);
 }
 
 inline unsigned grid1(int64_t work, int per) { return (unsigned)((work + per - 1) / per); }
@@ -213,23 +223,22 @@ inline unsigned grid1(int64_t work, int per) { return (unsigned)((work + per - 1
 // K (rows_k x cols_k, ldk) = K(Zb, Xb) for rows_k points Zb and cols_k points Xb with their norms: no argument checks, no counter
 template <typename T>
 int cross_block(rlhip_ctx* c, int64_t rows_x, int64_t rows_k, const T* Zb, int64_t ldz, const T* nz, int64_t cols_k, const T* Xb, int64_t ldx,
-                const T* nx, T scale, T* K, int64_t ldk) {
+                const T* nx, PdkFn<T> f, T* K, int64_t ldk) {
     for (int64_t c0 = 0; c0 < cols_k; c0 += 65535) {      // the epilogue's grid has one column per blockIdx.y
         const int64_t cc = (cols_k - c0) < 65535 ? (cols_k - c0) : 65535;
         int rc = rlhip::gemm<T>(c, rlhip::Trans, rlhip::NoTrans, rows_k, cc, rows_x, T(-2), Zb, ldz, Xb + c0 * ldx, ldx, T(0), K + c0 * ldk, ldk);
-        if (rc == 0) rc = rlhip::sqexp_epilogue<T>(c, rows_k, cc, nz, nx + c0, scale, K + c0 * ldk, ldk);
+        if (rc == 0) rc = rlhip::pdk_epilogue<T>(c, rows_k, cc, nz, nx + c0, f, K + c0 * ldk, ldk);
         if (rc) return rc;
     }
     return 0;
 }
 
+// The two routines below serve the squared-exponential entries (kernel = RLHIP_PDK_SQEXP, sh = 0) and the rlhip_pdk_* entries, whose argument
+// lists have `kernel` in front of the bandwidth: sh = 1 moves the codes of the arguments from there on by one.
 template <typename T>
-T rbf_scale_of(T bandwidth) { return (T)(-1.0 / (2.0 * (double)bandwidth * (double)bandwidth)); }
-
-template <typename T>
-int sqexp_cross_submatrix(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, const T* sq_colnorms_z, int64_t nx, const T* X,
-                          int64_t ldx, const T* sq_colnorms_x, int64_t rows_k, int64_t cols_k, T* K, int64_t ldk, int64_t ro, int64_t co,
-                          T bandwidth) {
+int pdk_cross_submatrix(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, const T* sq_colnorms_z, int64_t nx, const T* X,
+                        int64_t ldx, const T* sq_colnorms_x, int64_t rows_k, int64_t cols_k, T* K, int64_t ldk, int64_t ro, int64_t co,
+                        int kernel, int sh, T bandwidth) {
     if (!c) return -1;
     if (rows_x < 1) return -2;
     if (mz < 0) return -3;
@@ -243,7 +252,8 @@ int sqexp_cross_submatrix(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, 
     if (cols_k < 0 || co < 0 || co + cols_k > nx) return -12;
     if (!K && work) return -13;
     if (ldk < (rows_k > 1 ? rows_k : 1)) return -14;
-    if (!(bandwidth > T(0))) return -17;
+    if (!rlhip::pdk_kind_ok(kernel)) return -17;
+    if (!(bandwidth > T(0))) return -(17 + sh);
     c->rbf_path_count[2]++;
     if (!work) return 0;
     ws_scope ws(c);
@@ -263,12 +273,12 @@ int sqexp_cross_submatrix(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, 
         if (rc) return rc;
         nxr = tmp;
     }
-    return cross_block<T>(c, rows_x, rows_k, Z + ro * ldz, ldz, nz, cols_k, X + co * ldx, ldx, nxr, rbf_scale_of(bandwidth), K, ldk);
+    return cross_block<T>(c, rows_x, rows_k, Z + ro * ldz, ldz, nz, cols_k, X + co * ldx, ldx, nxr, rlhip::pdk_fn<T>(kernel, bandwidth), K, ldk);
 }
 
 template <typename T>
-int rbf_cross_apply(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t nx, const T* X, int64_t ldx, T bandwidth, int64_t n,
-                    T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {
+int pdk_cross_apply(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t nx, const T* X, int64_t ldx, int kernel, int sh,
+                    T bandwidth, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {
     if (!c) return -1;
     if (rows_x < 1) return -2;
     if (mz < 0) return -3;
@@ -279,12 +289,13 @@ int rbf_cross_apply(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_
     if (nx < 0) return -6;
     if (!X && product) return -7;
     if (ldx < rows_x) return -8;
-    if (!(bandwidth > T(0))) return -9;
-    if (n < 0) return -10;
-    if (!B && product) return -12;
-    if (ldb < (nx > 1 ? nx : 1)) return -13;
-    if (!C && out) return -15;
-    if (ldc < (mz > 1 ? mz : 1)) return -16;
+    if (!rlhip::pdk_kind_ok(kernel)) return -9;
+    if (!(bandwidth > T(0))) return -(9 + sh);
+    if (n < 0) return -(10 + sh);
+    if (!B && product) return -(12 + sh);
+    if (ldb < (nx > 1 ? nx : 1)) return -(13 + sh);
+    if (!C && out) return -(15 + sh);
+    if (ldc < (mz > 1 ? mz : 1)) return -(16 + sh);
     if (!out) return 0;
     if (!product) {
         if (beta != T(1)) {
@@ -295,7 +306,7 @@ int rbf_cross_apply(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_
     }
     const int64_t route = c->opt[RLHIP_OPT_RBF_FUSED];
     const bool fused = route != 0 && n <= RLHIP_RBF_FUSED_MAX_N && rows_x <= RLHIP_RBF_FUSED_MAX_ROWS_X;
-    const T scale = rbf_scale_of(bandwidth);
+    const PdkFn<T> f = rlhip::pdk_fn<T>(kernel, bandwidth);
     ws_scope ws(c);
     T* nr = ws.alloc<T>((size_t)(mz + nx));                    // the fused route's whole scratch
     if (!nr) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
@@ -304,8 +315,8 @@ int rbf_cross_apply(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_
     if (rc) return rc;
     if (fused) {
         c->rbf_path_count[0]++;
-        RbfArgs<T> a{rows_x, mz, nx, n, Z, ldz, X, ldx, nr, nr + mz, B, ldb, C, ldc, alpha, beta, scale};
-        return launch_fused_rows<T>(c, a);
+        RbfArgs<T> a{rows_x, mz, nx, n, Z, ldz, X, ldx, nr, nr + mz, B, ldb, C, ldc, alpha, beta, f.scale, f.third};
+        return f.matern ? launch_fused_rows<T, true>(c, a) : launch_fused_rows<T, false>(c, a);
     }
     c->rbf_path_count[1]++;
     int64_t rb = ((int64_t)1 << 26) / nx;                      // the K block holds at most 2^26 entries (one row when nx > 2^26)
@@ -315,7 +326,7 @@ int rbf_cross_apply(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_
     if (!Kb) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     for (int64_t r0 = 0; rc == 0 && r0 < mz; r0 += rb) {
         const int64_t rows = (mz - r0) < rb ? (mz - r0) : rb;
-        rc = cross_block<T>(c, rows_x, rows, Z + r0 * ldz, ldz, nr + r0, nx, X, ldx, nr + mz, scale, Kb, rows);
+        rc = cross_block<T>(c, rows_x, rows, Z + r0 * ldz, ldz, nr + r0, nx, X, ldx, nr + mz, f, Kb, rows);
         if (rc == 0) rc = rlhip::gemm<T>(c, rlhip::NoTrans, rlhip::NoTrans, rows, n, nx, alpha, Kb, rows, B, ldb, beta, C + r0, ldc);
     }
     return rc;
@@ -328,23 +339,37 @@ extern "C" {
 int rlhip_sqexp_cross_submatrix_f64(rlhip_ctx* c, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, const double* sq_colnorms_z, int64_t nx,
                                     const double* X, int64_t ldx, const double* sq_colnorms_x, int64_t rows_ksub, int64_t cols_ksub, double* Ksub,
                                     int64_t ldk, int64_t ro_ksub, int64_t co_ksub, double bandwidth) {
-    return sqexp_cross_submatrix<double>(c, rows_x, mz, Z, ldz, sq_colnorms_z, nx, X, ldx, sq_colnorms_x, rows_ksub, cols_ksub, Ksub, ldk, ro_ksub,
-                                         co_ksub, bandwidth);
+    return pdk_cross_submatrix<double>(c, rows_x, mz, Z, ldz, sq_colnorms_z, nx, X, ldx, sq_colnorms_x, rows_ksub, cols_ksub, Ksub, ldk, ro_ksub, co_ksub,
+                                    RLHIP_PDK_SQEXP, 0, bandwidth);
 }
 int rlhip_sqexp_cross_submatrix_f32(rlhip_ctx* c, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, const float* sq_colnorms_z, int64_t nx,
                                     const float* X, int64_t ldx, const float* sq_colnorms_x, int64_t rows_ksub, int64_t cols_ksub, float* Ksub,
                                     int64_t ldk, int64_t ro_ksub, int64_t co_ksub, float bandwidth) {
-    return sqexp_cross_submatrix<float>(c, rows_x, mz, Z, ldz, sq_colnorms_z, nx, X, ldx, sq_colnorms_x, rows_ksub, cols_ksub, Ksub, ldk, ro_ksub,
-                                        co_ksub, bandwidth);
+    return pdk_cross_submatrix<float>(c, rows_x, mz, Z, ldz, sq_colnorms_z, nx, X, ldx, sq_colnorms_x, rows_ksub, cols_ksub, Ksub, ldk, ro_ksub, co_ksub,
+                                    RLHIP_PDK_SQEXP, 0, bandwidth);
 }
 int rlhip_rbf_cross_apply_f64(rlhip_ctx* c, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t nx, const double* X, int64_t ldx,
                               double bandwidth, int64_t n, double alpha, const double* B, int64_t ldb, double beta, double* C, int64_t ldc) {
-    return rbf_cross_apply<double>(c, rows_x, mz, Z, ldz, nx, X, ldx, bandwidth, n, alpha, B, ldb, beta, C, ldc);
+    return pdk_cross_apply<double>(c, rows_x, mz, Z, ldz, nx, X, ldx, RLHIP_PDK_SQEXP, 0, bandwidth, n, alpha, B, ldb, beta, C, ldc);
 }
 int rlhip_rbf_cross_apply_f32(rlhip_ctx* c, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t nx, const float* X, int64_t ldx,
                               float bandwidth, int64_t n, float alpha, const float* B, int64_t ldb, float beta, float* C, int64_t ldc) {
-    return rbf_cross_apply<float>(c, rows_x, mz, Z, ldz, nx, X, ldx, bandwidth, n, alpha, B, ldb, beta, C, ldc);
+    return pdk_cross_apply<float>(c, rows_x, mz, Z, ldz, nx, X, ldx, RLHIP_PDK_SQEXP, 0, bandwidth, n, alpha, B, ldb, beta, C, ldc);
 }
+// the same two routines with the kernel function as an argument
+#define RLHIP_DEFINE_PDK_CROSS(SUF, T)                                                                                                            \
+    int rlhip_pdk_cross_submatrix_##SUF(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, const T* sq_colnorms_z, int64_t nx,    \
+                                        const T* X, int64_t ldx, const T* sq_colnorms_x, int64_t rows_ksub, int64_t cols_ksub, T* Ksub,           \
+                                        int64_t ldk, int64_t ro_ksub, int64_t co_ksub, int kernel, T bandwidth) {                                 \
+        return pdk_cross_submatrix<T>(c, rows_x, mz, Z, ldz, sq_colnorms_z, nx, X, ldx, sq_colnorms_x, rows_ksub, cols_ksub, Ksub, ldk, ro_ksub,  \
+                                      co_ksub, kernel, 1, bandwidth);                                                                             \
+    }                                                                                                                                             \
+    int rlhip_pdk_cross_apply_##SUF(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t nx, const T* X, int64_t ldx,       \
+                                    int kernel, T bandwidth, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {            \
+        return pdk_cross_apply<T>(c, rows_x, mz, Z, ldz, nx, X, ldx, kernel, 1, bandwidth, n, alpha, B, ldb, beta, C, ldc);                       \
+    }
+RLHIP_DEFINE_PDK_CROSS(f64, double)
+RLHIP_DEFINE_PDK_CROSS(f32, float)
 int64_t rlhip_rbf_path_count(rlhip_ctx* c, int which) { return (c && which >= 55 && which <= 57) ? c->rbf_path_count[which - 55] : -1; }
 
 }  // extern "C"

@@ -98,6 +98,23 @@ template <> struct Mfma16x4<float> {
     static __device__ __forceinline__ int drow(int lane, int r) { return drow_g(lane >> 4, r); }
 };
 
+// ---- the Matern 3/2 and 5/2 kernels as a function of the squared distance s (the contract is in include/rlhip.h):
+//      (1 + a (1 + a third)) exp(-a), a = c sqrt(s), in Horner form, each step one fused multiply-add.  c = sqrt(3) / l, third = 0 is Matern
+//      3/2: fma(a, 0, 1) is exactly 1, so the polynomial is 1 + a rounded once, for every a.  c = sqrt(5) / l, third = 1 / 3 is Matern 5/2.
+//      The clamp is a select, not fmax: a NaN s stays NaN.  s == 0 gives exactly 1.
+__device__ __forceinline__ double pdk_sqrt(double x) { return sqrt(x); }
+__device__ __forceinline__ float pdk_sqrt(float x) { return sqrtf(x); }
+__device__ __forceinline__ double pdk_exp(double x) { return exp(x); }
+__device__ __forceinline__ float pdk_exp(float x) { return expf(x); }
+__device__ __forceinline__ double pdk_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+__device__ __forceinline__ float pdk_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+template <typename T>
+__device__ __forceinline__ T matern_of_s(T s, T c, T third) {
+    s = s < T(0) ? T(0) : s;
+    const T a = c * pdk_sqrt(s);
+    return pdk_fma(a, pdk_fma(a, third, T(1)), T(1)) * pdk_exp(-a);
+}
+
 // an integer as a type: the argument of a generic lambda that needs it at compile time
 template <int N> struct IntC { static constexpr int value = N; };
 

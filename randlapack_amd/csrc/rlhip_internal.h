@@ -441,11 +441,27 @@ template <typename T>
 int dot_dev(rlhip_ctx* c, int64_t n, const T* x, const T* y, T* out_dev);
 
 // ---- rpchol.hip
-// nr[j] = |X(:, j)|^2 for cols points, and K(i, j) <- exp(scale * ((nr_rows[i] + nr_cols[j]) + K(i, j))) on a rows x cols block that holds
-// -2 z_i^T x_j (cols <= 65535): the two kernels of sqexp_submatrix, for the two-point-set routines of rbf.hip
+// The kernel function of a positive-definite kernel matrix as the device kernels take it (RLHIP_PDK_*): whether it is a Matern
+// kind, and two constants, each computed in double and rounded once to T.  scale = -1 / (2 l^2) for the squared exponential, sqrt(3) / l
+// and sqrt(5) / l for Matern 3/2 and 5/2; third = 1 / 3 for Matern 5/2 and 0 otherwise (matern_of_s, rlhip_device.h).
+template <typename T>
+struct PdkFn {
+    bool matern;
+    T scale, third;
+};
+inline bool pdk_kind_ok(int kernel) { return kernel >= RLHIP_PDK_SQEXP && kernel <= RLHIP_PDK_MATERN52; }
+template <typename T>
+PdkFn<T> pdk_fn(int kernel, T bandwidth) {
+    const double l = (double)bandwidth;
+    if (kernel == RLHIP_PDK_SQEXP) return {false, (T)(-1.0 / (2.0 * l * l)), T(0)};
+    if (kernel == RLHIP_PDK_MATERN32) return {true, (T)(1.7320508075688772 / l), T(0)};             // sqrt(3), correctly rounded
+    return {true, (T)(2.23606797749979 / l), (T)(1.0 / 3.0)};                                         // sqrt(5), correctly rounded
+}
+// nr[j] = |X(:, j)|^2 for cols points, and K(i, j) <- f((nr_rows[i] + nr_cols[j]) + K(i, j)) on a rows x cols block that holds -2 z_i^T x_j
+// (cols <= 65535), f the kernel function: the two kernels of the norm-expansion submatrix, for the two-point-set routines of rbf.hip
 template <typename T>
 int sqexp_colnorms(rlhip_ctx* c, int64_t rows_x, int64_t cols, const T* X, int64_t ldx, T* nr);
 template <typename T>
-int sqexp_epilogue(rlhip_ctx* c, int64_t rows, int64_t cols, const T* nr_rows, const T* nr_cols, T scale, T* K, int64_t ldk);
+int pdk_epilogue(rlhip_ctx* c, int64_t rows, int64_t cols, const T* nr_rows, const T* nr_cols, PdkFn<T> f, T* K, int64_t ldk);
 
 }  // namespace rlhip

@@ -7,6 +7,9 @@
 //   sqexp_submatrix    squared_exp_kernel_submatrix (rl_pdkernels.hh:133): MFMA GEMM for -2 X_rows^T X_cols, then one epilogue kernel
 //                      adds the squared column norms and takes exp.
 //   rbf_apply          linops::RBFKernelMatrix::operator() (rl_pdkernels.hh:255-283) by full row blocks of K.
+//   pdk_*              the three routines above with the kernel function as an argument: the squared exponential or Matern
+//                      3/2, 5/2.  The two device kernels that evaluate it take it as a template flag; the squared exponential's code is
+//                      the one it always was.
 //   sample_indices_iid RandBLAS::weights_to_cdf + sample_indices_iid (rl_rpchol.hh:64, 131, 141); the stream is this library's own and
 //                      is specified in include/rlhip.h.
 //   rpchol_panel_finish the trsm of rl_rpchol.hh:174 followed by the downdate of :47-62 (d -= row norms^2, d[S'] = 0).
@@ -14,8 +17,10 @@
 #include <cfloat>
 #include <cstring>
 #include "rlhip_internal.h"
+#include "rlhip_device.h"
 
 namespace {
+using rlhip::PdkFn;
 
 constexpr int COL_TILE_L = 64;      // kernel columns per workgroup (accumulators per thread)
 constexpr int COL_TILE_R = 64;      // feature rows staged per LDS chunk
@@ -58,10 +63,12 @@ __device__ inline double dexp(double x) { return exp(x); }
 __device__ inline float dexp(float x) { return expf(x); }
 
 // ---- (a) kernel columns.  Workgroup: 256 points x COL_TILE_L indices; X(:, idx tile) is staged in LDS COL_TILE_R rows at a time, each
-// thread keeps COL_TILE_L accumulators and reads its own point's features once per index tile.
-template <typename T>
+// thread keeps COL_TILE_L accumulators and reads its own point's features once per index tile.  MATERN: the squared distance goes through
+// matern_of_s(s, cs, third) instead of exp(-s * cs), cs = 1 / (2 h^2) there and sqrt(3) / l, sqrt(5) / l here; s = 0 gives exactly 1 in both.
+template <typename T, bool MATERN>
 __global__ __launch_bounds__(256) void sqexp_columns_kernel(int64_t rows_x, int64_t n, const T* __restrict__ X, int64_t ldx, int64_t nidx,
-                                                            const int64_t* __restrict__ idx, T inv2h2, T reg, T* __restrict__ out, int64_t ldo) {
+                                                            const int64_t* __restrict__ idx, T cs, T third, T reg, T* __restrict__ out,
+                                                            int64_t ldo) {
     __shared__ T xs[COL_TILE_R * COL_TILE_L];
     __shared__ int64_t js[COL_TILE_L];
     const int tid = threadIdx.x;
@@ -96,7 +103,9 @@ __global__ __launch_bounds__(256) void sqexp_columns_kernel(int64_t rows_x, int6
 #pragma unroll
     for (int l = 0; l < COL_TILE_L; ++l) {
         if (l < lcnt) {
-            T v = dexp(-(acc[l] * inv2h2));
+            T v;
+            if constexpr (MATERN) v = rlhip_dev::matern_of_s(acc[l], cs, third);
+            else v = dexp(-(acc[l] * cs));
             if (i == js[l]) v += reg;
             out[i + (l0 + l) * ldo] = v;
         }
@@ -113,14 +122,16 @@ __global__ void sq_colnorms_kernel(int64_t rows_x, int64_t cols, const T* __rest
     nr[j] = s;
 }
 
-template <typename T>
-__global__ void sqexp_epilogue_kernel(int64_t rows, int64_t cols, const T* __restrict__ nr_rows, const T* __restrict__ nr_cols, T scale,
+template <typename T, bool MATERN>
+__global__ void sqexp_epilogue_kernel(int64_t rows, int64_t cols, const T* __restrict__ nr_rows, const T* __restrict__ nr_cols, T scale, T third,
                                       T* __restrict__ K, int64_t ldk) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t j = blockIdx.y;
     if (i >= rows) return;
     T* p = K + i + j * ldk;
-    *p = dexp(scale * ((nr_rows[i] + nr_cols[j]) + *p));
+    const T s = (nr_rows[i] + nr_cols[j]) + *p;
+    if constexpr (MATERN) *p = rlhip_dev::matern_of_s(s, scale, third);
+    else *p = dexp(scale * s);
 }
 
 // ---- (c) sampler.  Chunk c holds weights [c*256, c*256 + 256); w_i = max(d_i, 0).  All sums in double:
@@ -350,21 +361,41 @@ __global__ void gather_cols_kernel(int64_t m, const int64_t* __restrict__ idx, c
 
 inline unsigned grid1(int64_t work, int per) { return (unsigned)((work + per - 1) / per); }
 
+// The three routines below serve the rlhip_sqexp_* / rlhip_rbf_apply_* entries (kernel = RLHIP_PDK_SQEXP, sh = 0) and the rlhip_pdk_* entries,
+// whose argument lists have `kernel` in front of the bandwidth: sh = 1 moves the codes of the arguments from there on by one.
 template <typename T>
-int sqexp_columns(rlhip_ctx* c, int64_t rows_x, int64_t n, const T* X, int64_t ldx, int64_t nidx, const int64_t* idx, T bandwidth, T reg,
-                  T* out, int64_t ldo) {
+int pdk_columns(rlhip_ctx* c, int64_t rows_x, int64_t n, const T* X, int64_t ldx, int64_t nidx, const int64_t* idx, int kernel, int sh, T bandwidth,
+                T reg, T* out, int64_t ldo) {
     if (rows_x < 1) return -2;
     if (n < 0) return -3;
     if (ldx < rows_x) return -5;
     if (nidx < 0) return -6;
-    if (!(bandwidth > T(0))) return -8;
-    if (ldo < (n > 1 ? n : 1)) return -11;
+    if (!rlhip::pdk_kind_ok(kernel)) return -8;
+    if (!(bandwidth > T(0))) return -(8 + sh);
+    if (ldo < (n > 1 ? n : 1)) return -(11 + sh);
     if (n == 0 || nidx == 0) return 0;
-    const T inv2h2 = (T)(1.0 / (2.0 * (double)bandwidth * (double)bandwidth));
     const int64_t ltiles = (nidx + COL_TILE_L - 1) / COL_TILE_L;
     if (ltiles > 65535) return -6;
-    hipLaunchKernelGGL(sqexp_columns_kernel<T>, dim3(grid1(n, 256), (unsigned)ltiles), dim3(256), 0, c->stream, rows_x, n, X, ldx, nidx, idx,
-                       inv2h2, reg, out, ldo);
+    const dim3 grid(grid1(n, 256), (unsigned)ltiles);
+    if (kernel == RLHIP_PDK_SQEXP) {
+        const T inv2h2 = (T)(1.0 / (2.0 * (double)bandwidth * (double)bandwidth));
+        hipLaunchKernelGGL((sqexp_columns_kernel<T, false>), grid, dim3(256), 0, c->stream, rows_x, n, X, ldx, nidx, idx, inv2h2, T(0), reg, out, ldo);
+    } else {
+        const PdkFn<T> f = rlhip::pdk_fn<T>(kernel, bandwidth);
+        hipLaunchKernelGGL((sqexp_columns_kernel<T, true>), grid, dim3(256), 0, c->stream, rows_x, n, X, ldx, nidx, idx, f.scale, f.third, reg, out,
+                           ldo);
+    }
+    RLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename T>
+int launch_epilogue(rlhip_ctx* c, int64_t rows, int64_t cols, const T* nr_rows, const T* nr_cols, PdkFn<T> f, T* K, int64_t ldk) {
+    const dim3 grid(grid1(rows, 256), (unsigned)cols);
+    if (f.matern)
+        hipLaunchKernelGGL((sqexp_epilogue_kernel<T, true>), grid, dim3(256), 0, c->stream, rows, cols, nr_rows, nr_cols, f.scale, f.third, K, ldk);
+    else
+        hipLaunchKernelGGL((sqexp_epilogue_kernel<T, false>), grid, dim3(256), 0, c->stream, rows, cols, nr_rows, nr_cols, f.scale, f.third, K, ldk);
     RLHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -378,15 +409,16 @@ int sq_colnorms(rlhip_ctx* c, int64_t rows_x, int64_t cols, const T* X, int64_t 
 }
 
 template <typename T>
-int sqexp_submatrix(rlhip_ctx* c, int64_t rows_x, int64_t cols_x, const T* X, int64_t ldx, const T* sq_colnorms_x, int64_t rows_k,
-                    int64_t cols_k, T* K, int64_t ldk, int64_t ro, int64_t co, T bandwidth) {
+int pdk_submatrix(rlhip_ctx* c, int64_t rows_x, int64_t cols_x, const T* X, int64_t ldx, const T* sq_colnorms_x, int64_t rows_k,
+                  int64_t cols_k, T* K, int64_t ldk, int64_t ro, int64_t co, int kernel, int sh, T bandwidth) {
     if (rows_x < 1) return -2;
     if (cols_x < 0) return -3;
     if (ldx < rows_x) return -5;
     if (rows_k < 0 || ro < 0 || ro + rows_k > cols_x) return -7;
     if (cols_k < 0 || co < 0 || co + cols_k > cols_x) return -8;
     if (ldk < (rows_k > 1 ? rows_k : 1)) return -10;
-    if (!(bandwidth > T(0))) return -13;
+    if (!rlhip::pdk_kind_ok(kernel)) return -13;
+    if (!(bandwidth > T(0))) return -(13 + sh);
     if (rows_k == 0 || cols_k == 0) return 0;
     if (cols_k > 65535) return -8;
     ws_scope ws(c);
@@ -399,13 +431,7 @@ int sqexp_submatrix(rlhip_ctx* c, int64_t rows_x, int64_t cols_x, const T* X, in
         nr = tmp;
     }
     int rc = rlhip::gemm<T>(c, rlhip::Trans, rlhip::NoTrans, rows_k, cols_k, rows_x, T(-2), X + ro * ldx, ldx, X + co * ldx, ldx, T(0), K, ldk);
-    if (rc == 0) {
-        const T scale = (T)(-1.0 / (2.0 * (double)bandwidth * (double)bandwidth));
-        hipLaunchKernelGGL(sqexp_epilogue_kernel<T>, dim3(grid1(rows_k, 256), (unsigned)cols_k), dim3(256), 0, c->stream, rows_k, cols_k,
-                           nr + ro, nr + co, scale, K, ldk);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = RLHIP_ERR_HIP(e);
-    }
+    if (rc == 0) rc = launch_epilogue<T>(c, rows_k, cols_k, nr + ro, nr + co, rlhip::pdk_fn<T>(kernel, bandwidth), K, ldk);
     return rc;
 }
 
@@ -418,17 +444,18 @@ int axpby_dev<float>(rlhip_ctx* c, int64_t n, float a, const float* x, float b, 
 
 // C (dim x n) = alpha * (K [+ regs]) * B + beta * C, K evaluated in full row blocks of at most max(2^26, dim) entries of scratch
 template <typename T>
-int rbf_apply(rlhip_ctx* c, int64_t rows_x, int64_t dim, const T* X, int64_t ldx, T bandwidth, const T* regs_host, int64_t num_ops,
-              int eval_includes_reg, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {
+int pdk_apply(rlhip_ctx* c, int64_t rows_x, int64_t dim, const T* X, int64_t ldx, int kernel, int sh, T bandwidth, const T* regs_host,
+              int64_t num_ops, int eval_includes_reg, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {
     if (rows_x < 1) return -2;
     if (dim < 0) return -3;
     if (ldx < rows_x) return -5;
-    if (!(bandwidth > T(0))) return -6;
-    if (eval_includes_reg && (!regs_host || num_ops < 1)) return -7;
-    if (eval_includes_reg && num_ops != 1 && n != num_ops) return -10;
-    if (n < 0) return -10;
-    if (ldb < (dim > 1 ? dim : 1)) return -13;
-    if (ldc < (dim > 1 ? dim : 1)) return -16;
+    if (!rlhip::pdk_kind_ok(kernel)) return -6;
+    if (!(bandwidth > T(0))) return -(6 + sh);
+    if (eval_includes_reg && (!regs_host || num_ops < 1)) return -(7 + sh);
+    if (eval_includes_reg && num_ops != 1 && n != num_ops) return -(10 + sh);
+    if (n < 0) return -(10 + sh);
+    if (ldb < (dim > 1 ? dim : 1)) return -(13 + sh);
+    if (ldc < (dim > 1 ? dim : 1)) return -(16 + sh);
     if (dim == 0 || n == 0) return 0;
     ws_scope ws(c);
     int rc = 0;
@@ -444,7 +471,7 @@ int rbf_apply(rlhip_ctx* c, int64_t rows_x, int64_t dim, const T* X, int64_t ldx
         // K(r0 : r0+rows, :) -- the transpose of the column block, which is what the MFMA GEMM's row operand wants
         for (int64_t c0 = 0; rc == 0 && c0 < dim; c0 += 65535) {
             const int64_t cc = (dim - c0) < 65535 ? (dim - c0) : 65535;
-            rc = sqexp_submatrix<T>(c, rows_x, dim, X, ldx, nr, rows, cc, Kb + c0 * rows, rows, r0, c0, bandwidth);
+            rc = pdk_submatrix<T>(c, rows_x, dim, X, ldx, nr, rows, cc, Kb + c0 * rows, rows, r0, c0, kernel, 0, bandwidth);
         }
         if (rc == 0) rc = rlhip::gemm<T>(c, rlhip::NoTrans, rlhip::NoTrans, rows, n, dim, alpha, Kb, rows, B, ldb, beta, C + r0, ldc);
     }
@@ -567,42 +594,39 @@ int gather_cols(rlhip_ctx* c, int64_t m, int64_t cnt, const int64_t* idx, const 
 
 }  // namespace
 
-// the two pieces of sqexp_submatrix that the two-point-set kernels of rbf.hip are composed from as well
+// the two pieces of pdk_submatrix that the two-point-set kernels of rbf.hip are composed from as well
 namespace rlhip {
 template <typename T>
 int sqexp_colnorms(rlhip_ctx* c, int64_t rows_x, int64_t cols, const T* X, int64_t ldx, T* nr) { return sq_colnorms<T>(c, rows_x, cols, X, ldx, nr); }
 template <typename T>
-int sqexp_epilogue(rlhip_ctx* c, int64_t rows, int64_t cols, const T* nr_rows, const T* nr_cols, T scale, T* K, int64_t ldk) {
+int pdk_epilogue(rlhip_ctx* c, int64_t rows, int64_t cols, const T* nr_rows, const T* nr_cols, PdkFn<T> f, T* K, int64_t ldk) {
     if (rows <= 0 || cols <= 0) return 0;
     if (cols > 65535) return -3;
-    hipLaunchKernelGGL(sqexp_epilogue_kernel<T>, dim3(grid1(rows, 256), (unsigned)cols), dim3(256), 0, c->stream, rows, cols, nr_rows, nr_cols, scale, K,
-                       ldk);
-    RLHIP_LAUNCH_CHECK();
-    return 0;
+    return launch_epilogue<T>(c, rows, cols, nr_rows, nr_cols, f, K, ldk);
 }
 template int sqexp_colnorms<double>(rlhip_ctx*, int64_t, int64_t, const double*, int64_t, double*);
 template int sqexp_colnorms<float>(rlhip_ctx*, int64_t, int64_t, const float*, int64_t, float*);
-template int sqexp_epilogue<double>(rlhip_ctx*, int64_t, int64_t, const double*, const double*, double, double*, int64_t);
-template int sqexp_epilogue<float>(rlhip_ctx*, int64_t, int64_t, const float*, const float*, float, float*, int64_t);
+template int pdk_epilogue<double>(rlhip_ctx*, int64_t, int64_t, const double*, const double*, PdkFn<double>, double*, int64_t);
+template int pdk_epilogue<float>(rlhip_ctx*, int64_t, int64_t, const float*, const float*, PdkFn<float>, float*, int64_t);
 }  // namespace rlhip
 
 extern "C" {
 
 int rlhip_sqexp_columns_f64(rlhip_ctx* c, int64_t rows_x, int64_t n, const double* X, int64_t ldx, int64_t nidx, const int64_t* idx_dev,
                             double bandwidth, double reg, double* out, int64_t ldo) {
-    return sqexp_columns<double>(c, rows_x, n, X, ldx, nidx, idx_dev, bandwidth, reg, out, ldo);
+    return pdk_columns<double>(c, rows_x, n, X, ldx, nidx, idx_dev, RLHIP_PDK_SQEXP, 0, bandwidth, reg, out, ldo);
 }
 int rlhip_sqexp_columns_f32(rlhip_ctx* c, int64_t rows_x, int64_t n, const float* X, int64_t ldx, int64_t nidx, const int64_t* idx_dev,
                             float bandwidth, float reg, float* out, int64_t ldo) {
-    return sqexp_columns<float>(c, rows_x, n, X, ldx, nidx, idx_dev, bandwidth, reg, out, ldo);
+    return pdk_columns<float>(c, rows_x, n, X, ldx, nidx, idx_dev, RLHIP_PDK_SQEXP, 0, bandwidth, reg, out, ldo);
 }
 int rlhip_sqexp_submatrix_f64(rlhip_ctx* c, int64_t rows_x, int64_t cols_x, const double* X, int64_t ldx, const double* sq_colnorms_x,
                               int64_t rows_ksub, int64_t cols_ksub, double* Ksub, int64_t ldk, int64_t ro_ksub, int64_t co_ksub, double bandwidth) {
-    return sqexp_submatrix<double>(c, rows_x, cols_x, X, ldx, sq_colnorms_x, rows_ksub, cols_ksub, Ksub, ldk, ro_ksub, co_ksub, bandwidth);
+    return pdk_submatrix<double>(c, rows_x, cols_x, X, ldx, sq_colnorms_x, rows_ksub, cols_ksub, Ksub, ldk, ro_ksub, co_ksub, RLHIP_PDK_SQEXP, 0, bandwidth);
 }
 int rlhip_sqexp_submatrix_f32(rlhip_ctx* c, int64_t rows_x, int64_t cols_x, const float* X, int64_t ldx, const float* sq_colnorms_x,
                               int64_t rows_ksub, int64_t cols_ksub, float* Ksub, int64_t ldk, int64_t ro_ksub, int64_t co_ksub, float bandwidth) {
-    return sqexp_submatrix<float>(c, rows_x, cols_x, X, ldx, sq_colnorms_x, rows_ksub, cols_ksub, Ksub, ldk, ro_ksub, co_ksub, bandwidth);
+    return pdk_submatrix<float>(c, rows_x, cols_x, X, ldx, sq_colnorms_x, rows_ksub, cols_ksub, Ksub, ldk, ro_ksub, co_ksub, RLHIP_PDK_SQEXP, 0, bandwidth);
 }
 int rlhip_sq_colnorms_f64(rlhip_ctx* c, int64_t rows_x, int64_t cols_x, const double* X, int64_t ldx, double* nr) {
     return rows_x < 1 ? -2 : ldx < rows_x ? -5 : sq_colnorms<double>(c, rows_x, cols_x, X, ldx, nr);
@@ -613,13 +637,29 @@ int rlhip_sq_colnorms_f32(rlhip_ctx* c, int64_t rows_x, int64_t cols_x, const fl
 int rlhip_rbf_apply_f64(rlhip_ctx* c, int64_t rows_x, int64_t dim, const double* X, int64_t ldx, double bandwidth, const double* regs_host,
                         int64_t num_ops, int eval_includes_reg, int64_t n, double alpha, const double* B, int64_t ldb, double beta, double* C,
                         int64_t ldc) {
-    return rbf_apply<double>(c, rows_x, dim, X, ldx, bandwidth, regs_host, num_ops, eval_includes_reg, n, alpha, B, ldb, beta, C, ldc);
+    return pdk_apply<double>(c, rows_x, dim, X, ldx, RLHIP_PDK_SQEXP, 0, bandwidth, regs_host, num_ops, eval_includes_reg, n, alpha, B, ldb, beta, C, ldc);
 }
 int rlhip_rbf_apply_f32(rlhip_ctx* c, int64_t rows_x, int64_t dim, const float* X, int64_t ldx, float bandwidth, const float* regs_host,
                         int64_t num_ops, int eval_includes_reg, int64_t n, float alpha, const float* B, int64_t ldb, float beta, float* C,
                         int64_t ldc) {
-    return rbf_apply<float>(c, rows_x, dim, X, ldx, bandwidth, regs_host, num_ops, eval_includes_reg, n, alpha, B, ldb, beta, C, ldc);
+    return pdk_apply<float>(c, rows_x, dim, X, ldx, RLHIP_PDK_SQEXP, 0, bandwidth, regs_host, num_ops, eval_includes_reg, n, alpha, B, ldb, beta, C, ldc);
 }
+// the same three routines with the kernel function as an argument
+#define RLHIP_DEFINE_PDK_SQUARE(SUF, T)                                                                                                           \
+    int rlhip_pdk_columns_##SUF(rlhip_ctx* c, int64_t rows_x, int64_t n, const T* X, int64_t ldx, int64_t nidx, const int64_t* idx_dev, int kernel, \
+                                T bandwidth, T reg, T* out, int64_t ldo) {                                                                        \
+        return pdk_columns<T>(c, rows_x, n, X, ldx, nidx, idx_dev, kernel, 1, bandwidth, reg, out, ldo);                                          \
+    }                                                                                                                                             \
+    int rlhip_pdk_submatrix_##SUF(rlhip_ctx* c, int64_t rows_x, int64_t cols_x, const T* X, int64_t ldx, const T* sq_colnorms_x, int64_t rows_ksub, \
+                                  int64_t cols_ksub, T* Ksub, int64_t ldk, int64_t ro_ksub, int64_t co_ksub, int kernel, T bandwidth) {           \
+        return pdk_submatrix<T>(c, rows_x, cols_x, X, ldx, sq_colnorms_x, rows_ksub, cols_ksub, Ksub, ldk, ro_ksub, co_ksub, kernel, 1, bandwidth); \
+    }                                                                                                                                             \
+    int rlhip_pdk_apply_##SUF(rlhip_ctx* c, int64_t rows_x, int64_t dim, const T* X, int64_t ldx, int kernel, T bandwidth, const T* regs_host,    \
+                              int64_t num_ops, int eval_includes_reg, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {   \
+        return pdk_apply<T>(c, rows_x, dim, X, ldx, kernel, 1, bandwidth, regs_host, num_ops, eval_includes_reg, n, alpha, B, ldb, beta, C, ldc); \
+    }
+RLHIP_DEFINE_PDK_SQUARE(f64, double)
+RLHIP_DEFINE_PDK_SQUARE(f32, float)
 int rlhip_sample_indices_iid_f64(rlhip_ctx* c, int64_t n, const double* d, int64_t k, int unique, const uint32_t ctr[4], const uint32_t key[2],
                                  uint32_t next_ctr[4], int64_t* out_dev, int64_t* out_host, int64_t* count, int* status) {
     return sample_indices_iid<double>(c, n, d, k, unique, ctr, key, next_ctr, out_dev, out_host, count, status);

@@ -857,6 +857,98 @@ def rbf_kernel_apply(ctx: Context, X, rows_x, dim, bandwidth, B, n, alpha=1.0, b
     return C_
 
 
+# ---- the kernel function as an argument: the wrappers above with `kernel` in front of the bandwidth -- PDK_SQEXP, PDK_MATERN32 or
+#      PDK_MATERN52 (RLHIP_PDK_* of include/rlhip.h).  Same tensors, same layouts, same routes and counters.
+PDK_SQEXP, PDK_MATERN32, PDK_MATERN52 = 0, 1, 2
+
+
+def pdk_columns(ctx: Context, X, rows_x, n, idx, kernel, bandwidth, reg=0.0, out=None):
+    """sqexp_columns for the kernel function `kernel`: out(i, l) = K(x_i, x_idx[l]) by differences (+ reg where i == idx[l])"""
+    torch = _torch()
+    suf, _ = _suf(X)
+    nidx = int(idx.numel())
+    if out is None:
+        out = torch.empty((nidx, n), dtype=X.dtype, device=X.device)
+    rc = getattr(ctx.lib, f"rlhip_pdk_columns_{suf}")(ctx.h, rows_x, n, X.data_ptr(), _ld(X), nidx, idx.data_ptr(), kernel, bandwidth, reg,
+                                                     out.data_ptr(), _ld(out) if nidx > 1 else max(n, 1))
+    _lib.check(rc, "pdk_columns")
+    return out
+
+
+def pdk_submatrix(ctx: Context, X, rows_x, cols_x, rows_k, cols_k, ro, co, kernel, bandwidth, sq_colnorms=None):
+    """sqexp_submatrix for the kernel function `kernel`: Ksub (cols_k, rows_k) column-major"""
+    torch = _torch()
+    suf, _ = _suf(X)
+    K = torch.empty((cols_k, rows_k), dtype=X.dtype, device=X.device)
+    rc = getattr(ctx.lib, f"rlhip_pdk_submatrix_{suf}")(ctx.h, rows_x, cols_x, X.data_ptr(), _ld(X), _ptr(sq_colnorms), rows_k, cols_k, K.data_ptr(),
+                                                       max(rows_k, 1), ro, co, kernel, bandwidth)
+    _lib.check(rc, "pdk_submatrix")
+    return K
+
+
+def pdk_apply(ctx: Context, X, rows_x, dim, kernel, bandwidth, B, n, alpha=1.0, beta=0.0, C_=None, regs=(), eval_includes_reg=False):
+    """rbf_apply for the kernel function `kernel`: C = alpha (K [+ regs]) B + beta C by row blocks of K; B, C column-major (n, dim)"""
+    torch = _torch()
+    suf, T = _suf(X)
+    if C_ is None:
+        C_ = torch.zeros((n, dim), dtype=X.dtype, device=X.device)
+    rg = (T * max(len(regs), 1))(*(list(regs) or [0.0]))
+    rc = getattr(ctx.lib, f"rlhip_pdk_apply_{suf}")(ctx.h, rows_x, dim, X.data_ptr(), _ld(X), kernel, bandwidth, rg, max(len(regs), 1),
+                                                   1 if eval_includes_reg else 0, n, alpha, B.data_ptr(), _ld(B), beta, C_.data_ptr(), _ld(C_))
+    _lib.check(rc, "pdk_apply")
+    return C_
+
+
+def pdk_cross_apply(ctx: Context, Z, X, rows_x, mz, nx, kernel, bandwidth, B, n, alpha=1.0, beta=0.0, C_=None):
+    """rbf_cross_apply for the kernel function `kernel`: C (mz x n) = alpha K(Z, X) B + beta C, fused or composed"""
+    torch = _torch()
+    suf, _ = _suf(X)
+    if C_ is None:
+        C_ = torch.zeros((n, mz), dtype=X.dtype, device=X.device)
+    rc = getattr(ctx.lib, f"rlhip_pdk_cross_apply_{suf}")(ctx.h, rows_x, mz, Z.data_ptr(), _ld(Z), nx, X.data_ptr(), _ld(X), kernel, bandwidth, n, alpha,
+                                                         B.data_ptr(), max(_ld(B), 1), beta, C_.data_ptr(), max(_ld(C_), 1))
+    _lib.check(rc, "pdk_cross_apply")
+    return C_
+
+
+def pdk_cross_submatrix(ctx: Context, Z, X, rows_x, mz, nx, rows_k, cols_k, ro, co, kernel, bandwidth, sq_colnorms_z=None, sq_colnorms_x=None):
+    """sqexp_cross_submatrix for the kernel function `kernel`: Ksub (cols_k, rows_k) column-major"""
+    torch = _torch()
+    suf, _ = _suf(X)
+    K = torch.empty((cols_k, rows_k), dtype=X.dtype, device=X.device)
+    rc = getattr(ctx.lib, f"rlhip_pdk_cross_submatrix_{suf}")(ctx.h, rows_x, mz, Z.data_ptr(), _ld(Z), _ptr(sq_colnorms_z), nx, X.data_ptr(), _ld(X),
+                                                             _ptr(sq_colnorms_x), rows_k, cols_k, K.data_ptr(), max(rows_k, 1), ro, co, kernel,
+                                                             bandwidth)
+    _lib.check(rc, "pdk_cross_submatrix")
+    return K
+
+
+def krr_predict_pdk(ctx: Context, Z, mz, Xp, rows_x, n, kernel, bandwidth, coeffs, s):
+    """krr_predict over an RBFCrossKernel with set_kernel(kernel): Y (mz x s) = K(Z, Xp) coeffs, column-major (s, mz)"""
+    torch = _torch()
+    suf, _ = _suf(Xp)
+    Y = torch.zeros((s, mz), dtype=Xp.dtype, device=Xp.device)
+    rc = getattr(ctx.lib, f"rlhip_drv_krr_predict_pdk_{suf}")(ctx.h, rows_x, mz, Z.data_ptr(), _ld(Z), n, Xp.data_ptr(), _ld(Xp), kernel, bandwidth, s,
+                                                             coeffs.data_ptr(), max(_ld(coeffs), 1), Y.data_ptr(), max(mz, 1))
+    _drv_check(ctx, rc, "krr_predict_pdk")
+    return Y
+
+
+def pdk_kernel_apply(ctx: Context, X, rows_x, dim, kernel, bandwidth, B, n, alpha=1.0, beta=0.0, C_=None, regs=(), eval_includes_reg=False,
+                     matrix_free=False):
+    """linops::RBFKernelMatrix::operator() through the C++ object with set_kernel(kernel) and set_matrix_free(matrix_free)"""
+    torch = _torch()
+    suf, T = _suf(X)
+    if C_ is None:
+        C_ = torch.zeros((n, dim), dtype=X.dtype, device=X.device)
+    rg = (T * max(len(regs), 1))(*(list(regs) or [0.0]))
+    rc = getattr(ctx.lib, f"rlhip_drv_pdk_kernel_apply_{suf}")(ctx.h, X.data_ptr(), _ld(X), rows_x, dim, kernel, bandwidth, rg, max(len(regs), 1),
+                                                              1 if eval_includes_reg else 0, 1 if matrix_free else 0, n, alpha, B.data_ptr(),
+                                                              _ld(B), beta, C_.data_ptr(), _ld(C_))
+    _drv_check(ctx, rc, "pdk_kernel_apply")
+    return C_
+
+
 def sample_indices_iid(ctx: Context, d, k, unique=False, ctr=(0, 0, 0, 0), key=(0, 0)):
     """the library's weighted iid sampler (include/rlhip.h rlhip_sample_indices_iid_*) on the device weights d.
     Returns dict(S (numpy int64: k draws, or the sorted distinct ones), count, status, next_ctr, S_dev)."""
@@ -894,6 +986,21 @@ def drv_rpchol_rbf(ctx: Context, X, rows_x, n, bandwidth, k, b, reg=0.0, ctr=(0,
     rc = getattr(ctx.lib, f"rlhip_drv_rpchol_rbf_{suf}")(ctx.h, X.data_ptr(), _ld(X), rows_x, n, bandwidth, reg, C.byref(kk), b,
                                                         S.ctypes.data_as(C.POINTER(C.c_int64)), F.data_ptr(), n, st, status)
     _drv_check(ctx, rc, "rpchol_rbf")
+    return _rpchol_out(ctx, st, kk, S, F, status)
+
+
+def drv_rpchol_pdk(ctx: Context, X, rows_x, n, kernel, bandwidth, k, b, reg=0.0, ctr=(0, 0, 0, 0), key=(0, 0)):
+    """drv_rpchol_rbf for the kernel function `kernel` (PDK_*): the same dict"""
+    torch = _torch()
+    suf, _ = _suf(X)
+    F = torch.zeros((k, n), dtype=X.dtype, device=X.device)
+    S = np.full(max(k, 1), -1, dtype=np.int64)
+    kk = C.c_int64(k)
+    st = _state_arr(ctr, key)
+    status = (C.c_int * 2)()
+    rc = getattr(ctx.lib, f"rlhip_drv_rpchol_pdk_{suf}")(ctx.h, X.data_ptr(), _ld(X), rows_x, n, kernel, bandwidth, reg, C.byref(kk), b,
+                                                        S.ctypes.data_as(C.POINTER(C.c_int64)), F.data_ptr(), n, st, status)
+    _drv_check(ctx, rc, "rpchol_pdk")
     return _rpchol_out(ctx, st, kk, S, F, status)
 
 
@@ -1029,6 +1136,21 @@ def krill_full_rpchol_rbf(ctx: Context, Xp, rows_x, n, bandwidth, regs, H, X, s,
     rc = getattr(ctx.lib, f"rlhip_drv_krill_full_rpchol_rbf_{suf}")(ctx.h, Xp.data_ptr(), _ldc(Xp), rows_x, n, bandwidth, rg, len(regs), H.data_ptr(),
                                                                    X.data_ptr(), s, tol, max_iters, C.byref(kk), b, st, C.byref(iters), hist)
     _drv_check(ctx, rc, "krill_full_rpchol_rbf")
+    out = _pcg_out(X, iters, hist)
+    out.update(k=int(kk.value), next_ctr=tuple(int(x) for x in st[:4]))
+    return out
+
+
+def krill_full_rpchol_pdk(ctx: Context, Xp, rows_x, n, kernel, bandwidth, regs, H, X, s, tol, max_iters, k=-1, b=-1, ctr=(0, 0, 0, 0), key=(0, 0)):
+    """krill_full_rpchol_rbf for the kernel function `kernel` (PDK_*): the same dict"""
+    suf, T = _suf(Xp)
+    rg, hist, iters = _pcg_args(T, regs, max_iters)
+    kk = C.c_int64(k)
+    st = _state_arr(ctr, key)
+    rc = getattr(ctx.lib, f"rlhip_drv_krill_full_rpchol_pdk_{suf}")(ctx.h, Xp.data_ptr(), _ldc(Xp), rows_x, n, kernel, bandwidth, rg, len(regs),
+                                                                   H.data_ptr(), X.data_ptr(), s, tol, max_iters, C.byref(kk), b, st, C.byref(iters),
+                                                                   hist)
+    _drv_check(ctx, rc, "krill_full_rpchol_pdk")
     out = _pcg_out(X, iters, hist)
     out.update(k=int(kk.value), next_ctr=tuple(int(x) for x in st[:4]))
     return out

@@ -1,12 +1,15 @@
-"""Times of K * B for the squared-exponential kernel on three routes, from device events:
+"""Times of K * B for the squared-exponential kernel (or, with --kernel, a Matern kernel: DESIGN 4.23) on three routes, from device events
+(DESIGN 4.22):
   (a) rlhip_rbf_apply_*            row blocks of K in scratch, three passes per block (the square operator's route)
   (b) rlhip_rbf_cross_apply_*      composed: the same scheme for two point sets (RLHIP_OPT_RBF_FUSED = 0)
   (c) rlhip_rbf_cross_apply_*      fused: one launch, K never in memory (RLHIP_OPT_RBF_FUSED = 1)
 for the square shape dim x dim (Z = X) and one prediction shape mz x nx, in fp64 and fp32.
 
-    python scripts/rbf_cross_time.py [--dim 131072] [--rows-x 16] [--n 1,8,64] [--mz 16384] [--reps 3] [--out profiles/rbf_cross_time.jsonl]
+    python scripts/rbf_cross_time.py [--kernel sqexp|matern32|matern52] [--dim 131072] [--rows-x 16] [--n 1,8,64] [--mz 16384] [--reps 3]
+                                     [--out profiles/rbf_cross_time.jsonl]
 
-One JSON line per (shape, precision, n, route): milliseconds, exp evaluations per second, and the scratch arena's high-water mark of a fresh
+--kernel sqexp calls the rlhip_rbf_* entries named above, the Matern kinds their rlhip_pdk_* generalisations (the same routes).
+One JSON line per (shape, precision, n, route): milliseconds, kernel evaluations per second (exp_per_s), and the scratch arena's high-water mark of a fresh
 context that ran this route only.  Reads nothing outside the tree."""
 import argparse
 import json
@@ -41,11 +44,13 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--prec", default="f64,f32")
     ap.add_argument("--out", default="")
+    ap.add_argument("--kernel", choices=["sqexp", "matern32", "matern52"], default="sqexp")
     a = ap.parse_args()
     import torch
     from randlapack_amd import device as dev
 
     h = 0.7 * a.rows_x ** 0.5
+    kind = {"sqexp": dev.PDK_SQEXP, "matern32": dev.PDK_MATERN32, "matern52": dev.PDK_MATERN52}[a.kernel]
     lines = []
     for prec in a.prec.split(","):
         dt = torch.float64 if prec == "f64" else torch.float32
@@ -62,17 +67,20 @@ def main():
             results = {}
             for route, opt in routes:
                 ctx = dev.Context(0)       # a fresh scratch arena: its high-water mark is this route's
-                if opt is None:
-                    fn = lambda: dev.rbf_apply(ctx, X, a.rows_x, a.dim, h, B, n, C_=Cm)
-                else:
+                if opt is not None:
                     ctx.set_option("rbf_fused", opt)
-                    fn = lambda: dev.rbf_cross_apply(ctx, Zp, X, a.rows_x, mz, a.dim, h, B, n, C_=Cm)
+                if a.kernel == "sqexp":
+                    fn = ((lambda: dev.rbf_apply(ctx, X, a.rows_x, a.dim, h, B, n, C_=Cm)) if opt is None else
+                          (lambda: dev.rbf_cross_apply(ctx, Zp, X, a.rows_x, mz, a.dim, h, B, n, C_=Cm)))
+                else:
+                    fn = ((lambda: dev.pdk_apply(ctx, X, a.rows_x, a.dim, kind, h, B, n, C_=Cm)) if opt is None else
+                          (lambda: dev.pdk_cross_apply(ctx, Zp, X, a.rows_x, mz, a.dim, kind, h, B, n, C_=Cm)))
                 before = [ctx.rbf_path_count(w) for w in (55, 56)]
                 times = timed(torch, fn, a.reps)
                 took = [ctx.rbf_path_count(w) - b for w, b in zip((55, 56), before)]
                 results[route] = Cm.clone()
                 ms = min(times)
-                line = dict(shape=shape, prec=prec, rows_x=a.rows_x, mz=mz, nx=a.dim, n=n, route=route, ms=[round(t, 3) for t in times],
+                line = dict(kernel=a.kernel, shape=shape, prec=prec, rows_x=a.rows_x, mz=mz, nx=a.dim, n=n, route=route, ms=[round(t, 3) for t in times],
                             ms_min=round(ms, 3), exp_per_s=round(mz * a.dim / (ms * 1e-3), 0), fused_calls=took[0], composed_calls=took[1],
                             arena_highwater_bytes=int(ctx.lib.rlhip_workspace_highwater(ctx.h)))
                 ctx.close()
