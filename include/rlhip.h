@@ -568,6 +568,17 @@ int rlhip_spectral_precond_apply_f64(rlhip_ctx* ctx, int64_t dim, int64_t dim_pr
 int rlhip_spectral_precond_apply_f32(rlhip_ctx* ctx, int64_t dim, int64_t dim_pre, const float* V, int64_t ldv, const float* D_dev, int64_t num_ops,
                                      int64_t n, float alpha, const float* B, int64_t ldb, float beta, float* C, int64_t ldc, float* W_dev,
                                      double* colnorm2_dev);
+/* rlhip_ridge_filter_*: the filter of restricted kernel ridge regression (RandLAPACK::krill_restricted_rpchol, rl_krill.hh):
+ * C(j, i) *= sigma[j] / (sigma[j]^2 + mu_i) for the k x s block C (ldc), mu_i = mus_dev[num_mus == 1 ? 0 : i].  sigma_dev: the k singular
+ * values of the factor, decreasing.  mu_i == 0 is the pseudo-inverse: where sigma[j] <= rcond * sigma[0] the factor is exactly 0; with
+ * mu_i > 0 nothing is cut.  The factor is computed in double for both precisions and rounded once; the product is taken in the precision of
+ * C.  One thread per entry, plain loads and stores, no atomics; rows k .. ldc-1 of C are never touched.  k == 0 or s == 0 returns 0 and
+ * touches nothing.  Argument codes, checked before anything is enqueued: -2 k < 0, -3 s < 0, -9 ldc < max(1, k); then, when k > 0 and
+ * s > 0: -4 sigma_dev NULL, -5 mus_dev NULL, -100 num_mus neither 1 nor s, -7 rcond < 0 or NaN, -8 C NULL. */
+int rlhip_ridge_filter_f64(rlhip_ctx* ctx, int64_t k, int64_t s, const double* sigma_dev, const double* mus_dev, int64_t num_mus, double rcond,
+                           double* C, int64_t ldc);
+int rlhip_ridge_filter_f32(rlhip_ctx* ctx, int64_t k, int64_t s, const float* sigma_dev, const float* mus_dev, int64_t num_mus, float rcond,
+                           float* C, int64_t ldc);
 /* The routes of the two update kernels, one count per call: 43 a fused rlhip_pcg_update_xr, 44 a fused rlhip_pcg_update_p, 45 either one on
  * the composed route (s > 64).  They continue the numbering of rlhip_path_count below but are read here: that function's range ends at 42
  * and answers -1 beyond it.  -1 for any other index. */

@@ -293,6 +293,35 @@ int rlhip_drv_pdk_kernel_apply_f64(rlhip_ctx* ctx, const double* X_pts, int64_t 
 int rlhip_drv_pdk_kernel_apply_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, int kernel, float bandwidth,
                                    const float* regs_host, int64_t num_ops, int eval_includes_reg, int matrix_free, int64_t n, float alpha,
                                    const float* B, int64_t ldb, float beta, float* C, int64_t ldc);
+/* Restricted kernel ridge regression (include/RandLAPACK_amd/rl_krill.hh) over linops::RBFKernelMatrix with the kernel function
+ * `kernel` (RLHIP_PDK_*): the k centres are points of X_pts, the model is k coefficients per right-hand side.  H: n x s (ldh), alpha: k x s
+ * (ldalpha), both DEVICE; regs_host: num_ops (1 or s) regularization parameters >= 0 on the HOST.  An unknown kind returns -(position of
+ * kernel): -6, -6, -9; a refused argument -100 with rlhip_last_error().
+ * krill_restricted_rpchol: the centres are the pivots of rp_cholesky.  *k in: centres asked for (< 0: sqrt(n)), out: the achieved rank; b: block
+ * size (< 0: min(64, n / 4)); S_host (k_in entries) receives the centres in selection order, -1 behind the achieved rank, where the rows of
+ * alpha are zero; status[2] = {w_status, c_status} as rlhip_drv_rpchol_* report them; state[6] advances as theirs. */
+int rlhip_drv_krill_restricted_rpchol_pdk_f64(rlhip_ctx* ctx, const double* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, double bandwidth,
+                                              const double* regs_host, int64_t num_ops, const double* H, int64_t ldh, int64_t s, int64_t* k, int64_t b,
+                                              int64_t* S_host, double* alpha, int64_t ldalpha, uint32_t state[6], int status[2]);
+int rlhip_drv_krill_restricted_rpchol_pdk_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, float bandwidth,
+                                              const float* regs_host, int64_t num_ops, const float* H, int64_t ldh, int64_t s, int64_t* k, int64_t b,
+                                              int64_t* S_host, float* alpha, int64_t ldalpha, uint32_t state[6], int status[2]);
+/* krill_restricted: the same fit with the k distinct centres S_host given.  *info = potrf's info of K(S,S): 0, or the 1-based position of the
+ * first centre that depends on the ones before it; then alpha is untouched. */
+int rlhip_drv_krill_restricted_pdk_f64(rlhip_ctx* ctx, const double* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, double bandwidth,
+                                       const double* regs_host, int64_t num_ops, const double* H, int64_t ldh, int64_t s, int64_t k, const int64_t* S_host,
+                                       double* alpha, int64_t ldalpha, int64_t* info);
+int rlhip_drv_krill_restricted_pdk_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, float bandwidth,
+                                       const float* regs_host, int64_t num_ops, const float* H, int64_t ldh, int64_t s, int64_t k, const int64_t* S_host,
+                                       float* alpha, int64_t ldalpha, int64_t* info);
+/* krr_predict_restricted: Y (mz x s, ldy) = K(Z, X_pts(:, S)) alpha -- the k centre columns are gathered and krr_predict runs on them: mz x k
+ * kernel evaluations.  Z is rows_x x mz (ldz), X_pts rows_x x n (ldx); k <= 65535. */
+int rlhip_drv_krr_predict_restricted_pdk_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t n, const double* X_pts,
+                                             int64_t ldx, int kernel, double bandwidth, int64_t k, const int64_t* S_host, int64_t s, const double* alpha,
+                                             int64_t ldalpha, double* Y, int64_t ldy);
+int rlhip_drv_krr_predict_restricted_pdk_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t n, const float* X_pts,
+                                             int64_t ldx, int kernel, float bandwidth, int64_t k, const int64_t* S_host, int64_t s, const float* alpha,
+                                             int64_t ldalpha, float* Y, int64_t ldy);
 /* posm_square (comps/rl_determiter.hh:231-282) as the C++ layer runs it: rlhip_posm_square_* and, after a failed pivot, the eigenvalue fallback on
  * the host.  LHS, RHS: s x s DEVICE, ld s.  *code = rank(LHS), -(s + 1) not positive semidefinite, -(s + 2) zero up to rounding. */
 int rlhip_drv_posm_square_f64(rlhip_ctx* ctx, int64_t s, const double* LHS, double* RHS, int diag_only, int64_t* code);

@@ -288,6 +288,18 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the kernel function as 
         _at = _args.index(_T)                                # the bandwidth is the first scalar of type T in each of these lists
         SIGNATURES[f"{_new}_{_suf}"] = (_rt, _args[:_at] + [c_int] + _args[_at:])
 
+for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # restricted kernel ridge regression (pcg.hip rlhip_ridge_filter_*, rl_krill.hh)
+    _Tp = C.POINTER(_T)
+    SIGNATURES.update({
+        f"rlhip_ridge_filter_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, _T, c_vp, c_i64]),
+        f"rlhip_drv_krill_restricted_rpchol_pdk_{_suf}": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, _T, _Tp, c_i64, c_vp, c_i64, c_i64, i64p, c_i64,
+                                                                  i64p, c_vp, c_i64, u32p, intp]),
+        f"rlhip_drv_krill_restricted_pdk_{_suf}": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, _T, _Tp, c_i64, c_vp, c_i64, c_i64, c_i64, i64p, c_vp,
+                                                           c_i64, i64p]),
+        f"rlhip_drv_krr_predict_restricted_pdk_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, _T, c_i64, i64p, c_i64, c_vp,
+                                                                 c_i64, c_vp, c_i64]),
+    })
+
 _lib = None
 
 

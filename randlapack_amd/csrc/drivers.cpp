@@ -898,6 +898,56 @@ int drv_krr_predict(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int6
     });
 }
 template <typename T>
+int drv_krill_restricted_rpchol(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth, const T* regs_host,
+                                int64_t num_ops, const T* H, int64_t ldh, int64_t s, int64_t* k, int64_t b, int64_t* S_host, T* alpha, int64_t ldalpha,
+                                uint32_t state[6], int status[2]) {
+    if (!pdk_known(kernel)) return -6;
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (!regs_host || num_ops < 1) throw RandLAPACK::Error("krill_restricted_rpchol: regs_host must hold num_ops >= 1 regularization parameters");
+        if (!k || !state || !status) throw RandLAPACK::Error("krill_restricted_rpchol: k, state and status must not be null");
+        std::vector<T> mus(regs_host, regs_host + num_ops);
+        lo::RBFKernelMatrix<T> G(n, X_pts, rows_x, bandwidth, mus, q, ldx);
+        G.set_kernel((RandLAPACK::PDKernel)kernel);
+        State st = load_state(state);
+        RandLAPACK::KrillRestrictedInfo info;
+        st = RandLAPACK::krill_restricted_rpchol(n, G, s, H, ldh, *k, S_host, alpha, ldalpha, st, b, &info);
+        store_state(st, state);
+        status[0] = info.w_status;
+        status[1] = info.c_status;
+        return 0;
+    });
+}
+template <typename T>
+int drv_krill_restricted(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth, const T* regs_host,
+                         int64_t num_ops, const T* H, int64_t ldh, int64_t s, int64_t k, const int64_t* S_host, T* alpha, int64_t ldalpha,
+                         int64_t* info) {
+    if (!pdk_known(kernel)) return -6;
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (!regs_host || num_ops < 1) throw RandLAPACK::Error("krill_restricted: regs_host must hold num_ops >= 1 regularization parameters");
+        if (!info) throw RandLAPACK::Error("krill_restricted: info must not be null");
+        std::vector<T> mus(regs_host, regs_host + num_ops);
+        lo::RBFKernelMatrix<T> G(n, X_pts, rows_x, bandwidth, mus, q, ldx);
+        G.set_kernel((RandLAPACK::PDKernel)kernel);
+        *info = RandLAPACK::krill_restricted(n, G, s, H, ldh, k, S_host, alpha, ldalpha);
+        return 0;
+    });
+}
+template <typename T>
+int drv_krr_predict_restricted(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts, int64_t ldx, int kernel,
+                               T bandwidth, int64_t k, const int64_t* S_host, int64_t s, const T* alpha, int64_t ldalpha, T* Y, int64_t ldy) {
+    if (!pdk_known(kernel)) return -9;
+    return guarded([&] {
+        blas::Queue q(ctx);
+        std::vector<T> regs{(T)0};
+        lo::RBFKernelMatrix<T> G(n, X_pts, rows_x, bandwidth, regs, q, ldx);
+        G.set_kernel((RandLAPACK::PDKernel)kernel);
+        RandLAPACK::krr_predict_restricted(G, k, S_host, mz, Z, ldz, s, alpha, ldalpha, Y, ldy);
+        return 0;
+    });
+}
+template <typename T>
 int drv_rbf_kernel_apply(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, int kernel, T bandwidth, const T* regs_host,
                          int64_t num_ops, int eval_includes_reg, int matrix_free, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C,
                          int64_t ldc) {
@@ -963,6 +1013,24 @@ extern "C" {
     }                                                                                                                                             \
     int rlhip_drv_posm_square_##SUF(rlhip_ctx* ctx, int64_t s, const T* LHS, T* RHS, int diag_only, int64_t* code) {                              \
         return drv_posm_square<T>(ctx, s, LHS, RHS, diag_only, code);                                                                             \
+    }                                                                                                                                             \
+    int rlhip_drv_krill_restricted_rpchol_pdk_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel,           \
+                                                    T bandwidth, const T* regs_host, int64_t num_ops, const T* H, int64_t ldh, int64_t s,         \
+                                                    int64_t* k, int64_t b, int64_t* S_host, T* alpha, int64_t ldalpha, uint32_t state[6],         \
+                                                    int status[2]) {                                                                              \
+        return drv_krill_restricted_rpchol<T>(ctx, X_pts, ldx, rows_x, n, kernel, bandwidth, regs_host, num_ops, H, ldh, s, k, b, S_host, alpha,  \
+                                              ldalpha, state, status);                                                                            \
+    }                                                                                                                                             \
+    int rlhip_drv_krill_restricted_pdk_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth,     \
+                                             const T* regs_host, int64_t num_ops, const T* H, int64_t ldh, int64_t s, int64_t k,                  \
+                                             const int64_t* S_host, T* alpha, int64_t ldalpha, int64_t* info) {                                   \
+        return drv_krill_restricted<T>(ctx, X_pts, ldx, rows_x, n, kernel, bandwidth, regs_host, num_ops, H, ldh, s, k, S_host, alpha, ldalpha,   \
+                                       info);                                                                                                     \
+    }                                                                                                                                             \
+    int rlhip_drv_krr_predict_restricted_pdk_##SUF(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n,                \
+                                                   const T* X_pts, int64_t ldx, int kernel, T bandwidth, int64_t k, const int64_t* S_host,        \
+                                                   int64_t s, const T* alpha, int64_t ldalpha, T* Y, int64_t ldy) {                               \
+        return drv_krr_predict_restricted<T>(ctx, rows_x, mz, Z, ldz, n, X_pts, ldx, kernel, bandwidth, k, S_host, s, alpha, ldalpha, Y, ldy);    \
     }
 RLHIP_DEFINE_PCG_DRIVERS(f64, double)
 RLHIP_DEFINE_PCG_DRIVERS(f32, float)

@@ -7,6 +7,8 @@
 //   pcg_update_p           P <- NR + P beta (:485-488) in place, a thread owns a row.
 //   spectral_precond_apply SpectralPrecond::operator() (rl_sym_linops.hh:328-378): two products of the library's GEMM around one scaling
 //                          kernel and one axpby kernel, then the squared column norms of the result.
+//   ridge_filter           the filter of restricted kernel ridge regression (include/RandLAPACK_amd/rl_krill.hh, restricted_tail): one
+//                          element-wise kernel between the two small products of that tail.
 //
 // No kernel here waits for another workgroup and none uses a floating-point atomic: a sum over rows goes through one partial per
 // workgroup and column in the scratch arena (wave sums by shuffles, the four waves added in order) and a one-workgroup kernel that adds the
@@ -230,6 +232,21 @@ __global__ void precond_axpby_kernel(int64_t dim, int64_t n, T alpha, const T* _
     }
 }
 
+// ---- (e) C(j, i) *= sigma[j] / (sigma[j]^2 + mu_i), the factor in double for both precisions and rounded once to T.  mu_i == 0: the
+// pseudo-inverse, factor 0 where sigma[j] <= rcond sigma[0].  A thread owns an entry; beyond the grid's cap it strides.
+template <typename T>
+__global__ __launch_bounds__(256) void ridge_filter_kernel(int64_t k, int64_t s, const T* __restrict__ sigma, const T* __restrict__ mus,
+                                                           int64_t num_mus, T rcond, T* __restrict__ C, int64_t ldc) {
+    const int64_t total = k * s;
+    const double cut = (double)rcond * (double)sigma[0];
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = t % k, i = t / k;
+        const double sg = (double)sigma[j], mu = (double)mus[num_mus == 1 ? 0 : i];
+        const double f = (mu == 0.0 && sg <= cut) ? 0.0 : sg / fma(sg, sg, mu);
+        C[j + i * ldc] *= (T)f;
+    }
+}
+
 inline unsigned stream_grid(rlhip_ctx* c, int64_t total) {
     const int64_t want = (total + 255) / 256, cap = (int64_t)c->num_cu * 8;
     return (unsigned)(want < 1 ? 1 : (want < cap ? want : cap));
@@ -395,6 +412,23 @@ int spectral_precond_apply(rlhip_ctx* c, int64_t dim, int64_t dim_pre, const T* 
     return rc;
 }
 
+template <typename T>
+int ridge_filter(rlhip_ctx* c, int64_t k, int64_t s, const T* sigma, const T* mus, int64_t num_mus, T rcond, T* C, int64_t ldc) {
+    if (!c) return -1;
+    if (k < 0) return -2;
+    if (s < 0) return -3;
+    if (ldc < (k > 1 ? k : 1)) return -9;
+    if (k == 0 || s == 0) return 0;
+    if (!sigma) return -4;
+    if (!mus) return -5;
+    if (num_mus != 1 && num_mus != s) return -100;
+    if (!(rcond >= T(0))) return -7;
+    if (!C) return -8;
+    hipLaunchKernelGGL(ridge_filter_kernel<T>, dim3(stream_grid(c, k * s)), dim3(256), 0, c->stream, k, s, sigma, mus, num_mus, rcond, C, ldc);
+    RLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -419,6 +453,10 @@ int64_t rlhip_pcg_path_count(rlhip_ctx* c, int which) { return (c && which >= 43
                                            int64_t num_ops, int64_t n, T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc,          \
                                            T* W_dev, double* colnorm2_dev) {                                                                 \
         return spectral_precond_apply<T>(c, dim, dim_pre, V, ldv, D_dev, num_ops, n, alpha, B, ldb, beta, C, ldc, W_dev, colnorm2_dev);      \
+    }                                                                                                                                        \
+    int rlhip_ridge_filter_##SUF(rlhip_ctx* c, int64_t k, int64_t s, const T* sigma_dev, const T* mus_dev, int64_t num_mus, T rcond, T* C,   \
+                                 int64_t ldc) {                                                                                              \
+        return ridge_filter<T>(c, k, s, sigma_dev, mus_dev, num_mus, rcond, C, ldc);                                                         \
     }
 RLHIP_DEFINE_PCG(f64, double)
 RLHIP_DEFINE_PCG(f32, float)

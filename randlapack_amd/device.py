@@ -1156,6 +1156,70 @@ def krill_full_rpchol_pdk(ctx: Context, Xp, rows_x, n, kernel, bandwidth, regs, 
     return out
 
 
+# ---- restricted kernel ridge regression (include/RandLAPACK_amd/rl_krill.hh): k centres among the n training points, k
+#      coefficients per right-hand side.  H (s, ldh >= n) and alpha (s, ldalpha >= k) are column-major blocks as everywhere in this module.
+def ridge_filter(ctx: Context, sigma, mus, C_, k, s, rcond=0.0, ldc=None):
+    """C(j, i) *= sigma[j] / (sigma[j]^2 + mus[len(mus) == 1 ? 0 : i]) in place on the k x s block C_ (rlhip_ridge_filter_*); mu == 0 cuts
+    sigma[j] <= rcond sigma[0] to an exact 0.  Returns C_."""
+    suf, _ = _suf(C_)
+    rc = getattr(ctx.lib, f"rlhip_ridge_filter_{suf}")(ctx.h, k, s, _ptr(sigma), _ptr(mus), int(mus.numel()), rcond, C_.data_ptr(),
+                                                      _ldc(C_) if ldc is None else ldc)
+    _lib.check(rc, "ridge_filter")
+    return C_
+
+
+def krill_restricted_rpchol_pdk(ctx: Context, Xp, rows_x, n, kernel, bandwidth, regs, H, s, k=-1, b=-1, ctr=(0, 0, 0, 0), key=(0, 0), ldalpha=None):
+    """krill_restricted_rpchol over the kernel matrix of the points Xp with the kernel function `kernel` (PDK_*): dict(alpha (s, ldalpha)
+    column-major with zero rows behind the achieved rank, S (numpy, the centres in selection order), k, status, c_status, next_ctr)"""
+    torch = _torch()
+    suf, T = _suf(Xp)
+    k_in = int(np.sqrt(n)) if k < 0 else k
+    lda = max(k_in, 1) if ldalpha is None else ldalpha
+    alpha = torch.full((s, lda), float("nan"), dtype=Xp.dtype, device=Xp.device)
+    S = np.full(max(k_in, 1), -1, dtype=np.int64)
+    rg = (T * len(regs))(*regs)
+    kk = C.c_int64(k)
+    st = _state_arr(ctr, key)
+    status = (C.c_int * 2)()
+    rc = getattr(ctx.lib, f"rlhip_drv_krill_restricted_rpchol_pdk_{suf}")(ctx.h, Xp.data_ptr(), _ldc(Xp), rows_x, n, kernel, bandwidth, rg, len(regs),
+                                                                         H.data_ptr(), _ldc(H), s, C.byref(kk), b,
+                                                                         S.ctypes.data_as(C.POINTER(C.c_int64)), alpha.data_ptr(), lda, st, status)
+    _drv_check(ctx, rc, "krill_restricted_rpchol_pdk")
+    kf = int(kk.value)
+    return dict(alpha=alpha, S=S[:kf].copy(), S_all=S, k=kf, status=int(status[0]), c_status=int(status[1]), next_ctr=tuple(int(x) for x in st[:4]))
+
+
+def krill_restricted_pdk(ctx: Context, Xp, rows_x, n, kernel, bandwidth, regs, H, s, S, alpha=None):
+    """krill_restricted with the centres S (a sequence of distinct point indices): (info, alpha).  info = 0, or the 1-based position of the
+    first centre that depends on the ones before it -- then alpha is as it was handed in."""
+    torch = _torch()
+    suf, T = _suf(Xp)
+    S = np.ascontiguousarray(S, dtype=np.int64)
+    k = int(S.size)
+    if alpha is None:
+        alpha = torch.full((s, max(k, 1)), float("nan"), dtype=Xp.dtype, device=Xp.device)
+    rg = (T * len(regs))(*regs)
+    info = C.c_int64(0)
+    rc = getattr(ctx.lib, f"rlhip_drv_krill_restricted_pdk_{suf}")(ctx.h, Xp.data_ptr(), _ldc(Xp), rows_x, n, kernel, bandwidth, rg, len(regs),
+                                                                  H.data_ptr(), _ldc(H), s, k, S.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                                  alpha.data_ptr(), _ldc(alpha), C.byref(info))
+    _drv_check(ctx, rc, "krill_restricted_pdk")
+    return int(info.value), alpha
+
+
+def krr_predict_restricted_pdk(ctx: Context, Z, mz, Xp, rows_x, n, kernel, bandwidth, S, alpha, s):
+    """krr_predict_restricted: Y (mz x s) = K(Z, Xp(:, S)) alpha for the k = len(S) centres and the k x s block alpha; column-major (s, mz)"""
+    torch = _torch()
+    suf, _ = _suf(Xp)
+    S = np.ascontiguousarray(S, dtype=np.int64)
+    Y = torch.zeros((s, mz), dtype=Xp.dtype, device=Xp.device)
+    rc = getattr(ctx.lib, f"rlhip_drv_krr_predict_restricted_pdk_{suf}")(ctx.h, rows_x, mz, Z.data_ptr(), _ld(Z), n, Xp.data_ptr(), _ld(Xp), kernel,
+                                                                        bandwidth, int(S.size), S.ctypes.data_as(C.POINTER(C.c_int64)), s,
+                                                                        alpha.data_ptr(), max(_ldc(alpha), 1), Y.data_ptr(), max(mz, 1))
+    _drv_check(ctx, rc, "krr_predict_restricted_pdk")
+    return Y
+
+
 # ---- matrix-vector layer, pcg_saddle and the sketched least-squares preconditioners (lsq.hip; include/RandLAPACK_amd/rl_determiter.hh,
 #      rl_preconditioners.hh, rl_lstsq.hh).  A matrix is a column-major tensor (cols, ld) as everywhere in this module, a vector a 1-D tensor
 #      that may be longer than the length in use.
