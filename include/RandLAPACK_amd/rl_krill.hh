@@ -145,6 +145,8 @@ STATE krill_full_rpchol(int64_t n, FUNC& G, int64_t ell, const T* H, T* X, T tol
 /// Prediction with the coefficients of krill_full_rpchol: Y (mz x s, ldy) = K(Z, X_train) * coeffs (n x s, ldcoef), where Kzx is the
 /// cross kernel between the mz evaluation points and the n training points.  Column i of Y is the fitted function of the i-th
 /// regularization at the points of Z.  All arrays on the DEVICE.  (The reference stops at the coefficients)
+/// Few evaluation points against many training points: Kzx.set_split_x(true) beforehand splits the fused kernel's walk over the training
+/// points; the choice travels with the operator, so there is no argument for it here.
 template <typename T>
 void krr_predict(linops::RBFCrossKernel<T>& Kzx, int64_t s, const T* coeffs, int64_t ldcoef, T* Y, int64_t ldy) {
     randlapack_require(s >= 0) << "s=" << s << " must be >= 0";
@@ -238,7 +240,8 @@ int64_t krill_restricted(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ld
 
 /// Prediction with the coefficients of a restricted fit: Y (mz x s, ldy) = K(Z, X(:, S)) alpha (k x s, ldalpha), with G's points, kernel
 /// function and bandwidth.  The k centre columns of G.X are gathered into scratch and krr_predict runs on them: mz x k kernel
-/// evaluations.  S HOST (every entry in [0, G.dim)), everything else DEVICE.  Z: rows_x x mz, ldz.
+/// evaluations.  S HOST (every entry in [0, G.dim)), everything else DEVICE.  Z: rows_x x mz, ldz.  G.set_split_x(true) is handed on to
+/// the cross kernel built here, as G's kernel function is.
 template <typename T>
 void krr_predict_restricted(linops::RBFKernelMatrix<T>& G, int64_t k, const int64_t* S, int64_t mz, const T* Z, int64_t ldz, int64_t s,
                             const T* alpha, int64_t ldalpha, T* Y, int64_t ldy) {
@@ -256,6 +259,7 @@ void krr_predict_restricted(linops::RBFKernelMatrix<T>& G, int64_t k, const int6
     }
     linops::RBFCrossKernel<T> Kzs(G.rows_x, mz, Z, k, Xs, G.bandwidth, q, ldz, G.rows_x);
     Kzs.set_kernel(G.kernel);
+    Kzs.set_split_x(G._split_x);
     krr_predict(Kzs, s, alpha, ldalpha > 0 ? ldalpha : 1, Y, ldy);
 }
 

@@ -12,6 +12,7 @@
 //   linops::RBFCrossKernel         the rectangular kernel K(Z, X) between two DEVICE point sets: operator(), matvec, submatrix
 //                                  (rlhip_rbf_cross_apply_*, rlhip_sqexp_cross_submatrix_*) -- what KRR prediction multiplies by;
 //   RBFKernelMatrix::set_matrix_free(true): operator() through the same kernels with Z = X (K never in memory); off by default.
+// Extension: set_split_x(true) on either operator runs its cross apply with the fused kernel split over X; off by default.
 // Extension: the kernel function is a member of both operators, PDKernel::SquaredExp by default; set_kernel selects Matern 3/2
 // or 5/2 (rlhip_pdk_*).  rp_cholesky, rpchol_pc_data, krill_full_rpchol and krr_predict reach the kernel through these objects only.
 #pragma once
@@ -71,6 +72,20 @@ inline int cross_apply(blas::Queue& q, int64_t rx, int64_t mz, const float* Z, i
     return kf == PDKernel::SquaredExp ? rlhip_rbf_cross_apply_f32(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, h, n, a, B, ldb, b, C, ldc)
                                       : rlhip_pdk_cross_apply_f32(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, (int)kf, h, n, a, B, ldb, b, C, ldc);
 }
+/// while alive and `on`: RLHIP_OPT_RBF_FUSED = 2 (the fused cross apply split over X) on q's context; the value found is put back
+struct split_x_scope {
+    rlhip_ctx* ctx;
+    int64_t found;
+    bool on;
+    split_x_scope(blas::Queue& q, bool on) : ctx(q.ctx()), found(-1), on(on) {
+        if (!on) return;
+        found = rlhip_get_option(ctx, RLHIP_OPT_RBF_FUSED);
+        rlhip_set_option(ctx, RLHIP_OPT_RBF_FUSED, 2);
+    }
+    ~split_x_scope() { if (on) rlhip_set_option(ctx, RLHIP_OPT_RBF_FUSED, found); }
+    split_x_scope(const split_x_scope&) = delete;
+    split_x_scope& operator=(const split_x_scope&) = delete;
+};
 inline int cross_submatrix(blas::Queue& q, int64_t rx, int64_t mz, const double* Z, int64_t ldz, const double* nz, int64_t nx, const double* X,
                            int64_t ldx, const double* nxr, int64_t r, int64_t c, double* K, int64_t ldk, int64_t ro, int64_t co, PDKernel kf,
                            double h) {
@@ -121,6 +136,7 @@ struct RBFKernelMatrix {
     int64_t ldx;
     bool _eval_includes_reg;
     bool _matrix_free = false;
+    bool _split_x = false;
     PDKernel kernel = PDKernel::SquaredExp;
     blas::Queue& q;
 
@@ -138,6 +154,9 @@ struct RBFKernelMatrix {
     /// true: operator() multiplies through rlhip_rbf_cross_apply_* with Z = X (matrix-free inside that routine's fused limits) instead of
     /// rlhip_rbf_apply_*'s row blocks of K in scratch.  Off by default: the default path is the one that was measured.
     void set_matrix_free(bool mf) { _matrix_free = mf; }
+    /// true: the matrix-free product runs with RLHIP_OPT_RBF_FUSED = 2, the fused kernel split over X where rlhip_rbf_split_chunks(dim, dim) > 1
+    /// (DESIGN 4.25); the option is put back to what it was after the call.  No effect without set_matrix_free(true).  Off by default.
+    void set_split_x(bool s) { _split_x = s; }
     /// the kernel function of every entry point of this operator: operator() on both branches, columns(); the diagonal is 1 for each
     void set_kernel(PDKernel k) { kernel = k; }
 
@@ -151,6 +170,7 @@ struct RBFKernelMatrix {
                                                              << " so each column gets its own regularization";
         }
         if (_matrix_free) {
+            _pdk_impl::split_x_scope split(q, _split_x);
             blas::check(_pdk_impl::cross_apply(q, rows_x, dim, X, ldx, dim, X, ldx, kernel, bandwidth, n, alpha, B, ldb, beta, C, ldc),
                         "RBFKernelMatrix");
             // the regularization term, exactly as rlhip_rbf_apply_* adds it: column i gets alpha * regs[min(i, num_ops - 1)] * B(:, i)
@@ -196,11 +216,15 @@ struct RBFCrossKernel {
     T bandwidth;
     int64_t ldz, ldx;
     PDKernel kernel = PDKernel::SquaredExp;
+    bool _split_x = false;
     blas::Queue& q;
 
     using scalar_t = T;
 
     void set_kernel(PDKernel k) { kernel = k; }
+    /// true: operator() (and matvec) run with RLHIP_OPT_RBF_FUSED = 2, the fused kernel split over X where rlhip_rbf_split_chunks says so
+    /// (DESIGN 4.25): for few evaluation points against many training points.  The option is put back after the call.  Off by default.
+    void set_split_x(bool s) { _split_x = s; }
 
     RBFCrossKernel(int64_t rows_x, int64_t mz, const T* Z, int64_t nx, const T* X, T bandwidth, blas::Queue& queue = blas::default_queue(),
                    int64_t ldz = 0, int64_t ldx = 0)
@@ -221,6 +245,7 @@ struct RBFCrossKernel {
         randlapack_require(ldb >= cols) << "ldb=" << ldb << " < " << cols << " (ldb must be >= the columns of op(K))";
         randlapack_require(ldc >= rows) << "ldc=" << ldc << " < " << rows << " (ldc must be >= the rows of op(K))";
         const int64_t ldb1 = ldb > 0 ? ldb : 1, ldc1 = ldc > 0 ? ldc : 1;
+        _pdk_impl::split_x_scope split(q, _split_x);
         blas::check(tr ? _pdk_impl::cross_apply(q, rows_x, n_cols, X, ldx, n_rows, Z, ldz, kernel, bandwidth, n, alpha, B, ldb1, beta, C, ldc1)
                        : _pdk_impl::cross_apply(q, rows_x, n_rows, Z, ldz, n_cols, X, ldx, kernel, bandwidth, n, alpha, B, ldb1, beta, C, ldc1),
                     "RBFCrossKernel");

@@ -63,7 +63,7 @@ enum rlhip_option {
     RLHIP_OPT_JACOBI_CLOCK_HOLDERS = 11,           /* persistent Jacobi: 1 (default) the CUs its workers leave idle run FMA-burning holder workgroups so that DVFS keeps the clock up for the next GEMM (never on a context that shares the device with another stream); 0: the workers alone */
     RLHIP_OPT_LSQ_NORMAL_FUSED = 12,               /* rlhip_normal_matvec_*: 1 the one-pass kernel wherever n is within its limit, 0 always the two rlhip_gemv calls; default: one pass up to the widths at which it measured faster */
     RLHIP_OPT_SPMV_LANES = 13,                     /* rlhip_csr_spmv_*, rlhip_csr_normal_matvec_*: 4, 16 or 64 lanes per row, 0 the split long-row route; default: chosen from the mean row length (tests reach every route at small sizes with it) */
-    RLHIP_OPT_RBF_FUSED = 14,                      /* rlhip_rbf_cross_apply_*: 1 the matrix-free one-launch kernel wherever the shape is within its limits (RLHIP_RBF_FUSED_MAX_N, RLHIP_RBF_FUSED_MAX_ROWS_X), 0 always the composed route (row blocks of K in scratch); default: the one-launch kernel within its limits */
+    RLHIP_OPT_RBF_FUSED = 14,                      /* rlhip_rbf_cross_apply_*: 1 the matrix-free one-launch kernel wherever the shape is within its limits (RLHIP_RBF_FUSED_MAX_N, RLHIP_RBF_FUSED_MAX_ROWS_X), 0 always the composed route (row blocks of K in scratch), 2 the fused kernel split over X wherever rlhip_rbf_split_chunks(mz, nx) > 1 (two launches, partial sums in scratch) and as 1 elsewhere; default: the one-launch kernel within its limits, never split */
     RLHIP_OPT_COUNT = 15                           /* one past the last option.  (It was RLHIP_OPT_COUNT = 14 through DESIGN 4.21; tests/test_splsq_cases.py, written then, still looks for that text in this header.) */
 };
 int rlhip_set_option(rlhip_ctx* ctx, int option, int64_t value);     /* -1 (bad context / option) or 0 */
@@ -696,6 +696,14 @@ int64_t rlhip_spmv_path_count(rlhip_ctx* ctx, int which);
  *   mz + nx squared norms.  The sums over the points of X run in the order of X, sixteen points at a time, whatever mz, the grid and the
  *   device are, and there are no atomics: row i of the result is a function of Z(:, i), X, B, alpha, beta and C(i, :) alone, bit for bit --
  *   not of mz, of the row's place in Z, of the CU count or of earlier calls.
+ *   Fused and split over X (RLHIP_OPT_RBF_FUSED = 2, the same limits): the one-launch grid is ceil(mz / 64) workgroups that
+ *   each walk all of X, a small part of the device when mz is small.  With g = rlhip_rbf_split_chunks(mz, nx) > 1 the kernel runs on a
+ *   grid of ceil(mz / 64) x g, chunk b of X = the points [b CH, min(nx, (b + 1) CH)), CH = 64 ceil(nx / (64 g)); the g partial results go
+ *   to scratch (g * 64 ceil(mz / 64) * n values beside the norms) and a second launch adds them in the order of b and applies alpha and
+ *   beta.  No atomics.  Bit contract of value 2: row i of the result is a function of Z(:, i), X, B, alpha, beta, C(i, :) and g, and g is
+ *   a function of (mz, nx) alone -- not of the row's place in Z, of the device or its CU count, of earlier calls or of the grid's
+ *   scheduling.  With g == 1 the call runs the one-launch kernel and gives the bits of value 1.  A split apply counts as a fused apply
+ *   (55) and in rlhip_rbf_split_count.
  *   Composed route (every other shape; RLHIP_OPT_RBF_FUSED = 0 always): row blocks of K of at most max(2^26, nx) entries in the scratch
  *   arena by rlhip_sqexp_cross_submatrix's kernels, one GEMM with B per block -- what rlhip_rbf_apply_* does, for two point sets.
  *   Returns 0, or -(position of the first bad argument): -2 rows_x < 1, -3 mz < 0, -4 Z NULL, -5 ldz < rows_x, -6 nx < 0, -7 X NULL,
@@ -703,6 +711,10 @@ int64_t rlhip_spmv_path_count(rlhip_ctx* ctx, int which);
  *   is an error only where the call would read (or write) it.  Nothing is launched on an argument error. */
 #define RLHIP_RBF_FUSED_MAX_N 64
 #define RLHIP_RBF_FUSED_MAX_ROWS_X 128
+/* The split rule's constants: RLHIP_RBF_SPLIT_W work items (Z tile x chunk) are aimed at, four per CU of a 256-CU part; a chunk is never
+ * shorter than RLHIP_RBF_SPLIT_CH_MIN points of X, so nx < 2 * RLHIP_RBF_SPLIT_CH_MIN is never split. */
+#define RLHIP_RBF_SPLIT_W 1024
+#define RLHIP_RBF_SPLIT_CH_MIN 512
 int rlhip_sqexp_cross_submatrix_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, const double* sq_colnorms_z, int64_t nx,
                                     const double* X, int64_t ldx, const double* sq_colnorms_x, int64_t rows_ksub, int64_t cols_ksub, double* Ksub,
                                     int64_t ldk, int64_t ro_ksub, int64_t co_ksub, double bandwidth);
@@ -716,6 +728,12 @@ int rlhip_rbf_cross_apply_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const 
 /* The routes of this layer, one count per call that reached a route: 55 a fused cross apply, 56 a composed one, 57 rlhip_sqexp_cross_submatrix
  * calls.  -1 for any other index or a NULL context. */
 int64_t rlhip_rbf_path_count(rlhip_ctx* ctx, int which);
+/* The number g >= 1 of chunks that RLHIP_OPT_RBF_FUSED = 2 cuts X into for mz points of Z and nx points of X; no context: g depends on
+ * nothing else.  ztiles = ceil(mz / 64); g = min(ceil(RLHIP_RBF_SPLIT_W / ztiles), floor(nx / RLHIP_RBF_SPLIT_CH_MIN)), 1 if that is < 2;
+ * else CH = 64 ceil(nx / (64 g)) and g = ceil(nx / CH), so no chunk is empty.  1 for mz == 0 or nx == 0, -1 for a negative argument. */
+int64_t rlhip_rbf_split_chunks(int64_t mz, int64_t nx);
+/* Fused cross applies of this context that ran split over X (each counted under 55 as well); -1 for a NULL context. */
+int64_t rlhip_rbf_split_count(rlhip_ctx* ctx);
 
 /* ---- row-block sharding across the GPUs of a node (new design; the reference has no
  *      distributed code).  One process per GPU.  Sum all-reduces run on the context's stream through RCCL

@@ -269,6 +269,8 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # sparse matrix-vector la
     })
 
 SIGNATURES["rlhip_rbf_path_count"] = (c_i64, [c_vp, c_int])
+SIGNATURES["rlhip_rbf_split_chunks"] = (c_i64, [c_i64, c_i64])      # the fused cross apply's split over X
+SIGNATURES["rlhip_rbf_split_count"] = (c_i64, [c_vp])
 for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the RBF kernel between two point sets and KRR prediction (rbf.hip, rl_pdkernels.hh, rl_krill.hh)
     SIGNATURES.update({
         f"rlhip_sqexp_cross_submatrix_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,

@@ -23,6 +23,13 @@
 // beside the VALU instead of in front of it.  X points past nx are never read: the staging stores zeros for them (rows of X, rows of B,
 // norm), so such a point contributes exp(scale * zn) * 0 = 0 exactly.  The sums over j run in the order of j, sixteen at a time, whatever
 // mz, the grid or the device: row i of the result is a function of Z(:, i), X, B, alpha, beta and C(i, :) alone.
+//
+// The split over X (RLHIP_OPT_RBF_FUSED = 2 only).  With few points of Z the grid above is a few workgroups that each walk
+// all of X.  rlhip_rbf_split_chunks(mz, nx) = g is a function of the shape alone; where g > 1 the same kernel (SPLIT = true) runs on a grid
+// of ztiles x g: workgroup (i, b) walks the points [b CH, min(nx, (b + 1) CH)) of X, CH a multiple of 64 and so of every TP, with the
+// pipeline above -- the staging zero-fills behind the chunk's end -- and stores its raw accumulators to part[b][column][row] in the scratch
+// arena (row stride: mz rounded up to 64, so every lane stores).  rbf_reduce_kernel, one thread per entry of C, adds the g partials in the
+// order of b and applies alpha and beta.  No atomics, two launches; row i is a function of the same arguments and of g.
 #include <cmath>
 #include "rlhip_internal.h"
 #include "rlhip_device.h"
@@ -59,11 +66,13 @@ struct RbfArgs {
     const T* B; int64_t ldb;
     T* C; int64_t ldc;
     T alpha, beta, scale, third;      // scale, third: PdkFn's constants
+    T* part; int64_t ch, mzp;         // SPLIT only: the partials [chunk][column][row], points of X per chunk, rows of a partial (64 ztiles)
 };
 
 // MATERN = false is the squared exponential, true the two Matern kinds (told apart by a.third alone, matern_of_s): the squared exponential
 // keeps an instantiation of its own, so the sqrt and the polynomial cost it no register.
-template <typename T, int KS, int NT, bool MATERN>
+// SPLIT = false walks all of X and writes C; SPLIT = true walks chunk blockIdx.y of X and writes its partial (see the header comment).
+template <typename T, int KS, int NT, bool MATERN, bool SPLIT>
 __global__ __launch_bounds__(RBF_WG) void rbf_fused_kernel(const RbfArgs<T> a) {
     using M = Mfma16x4<T>;
     using acc_t = typename M::acc_t;
@@ -86,24 +95,26 @@ __global__ __launch_bounds__(RBF_WG) void rbf_fused_kernel(const RbfArgs<T> a) {
         zreg[kk] = (zok && row < a.rows_x) ? T(-2) * a.Z[zp * a.ldz + row] : T(0);
     }
     const T znorm = zok ? a.zn[zp] : T(0);
+    const int64_t xbeg = SPLIT ? (int64_t)blockIdx.y * a.ch : 0;                                     // this workgroup's points of X
+    const int64_t xend = SPLIT ? (xbeg + a.ch < a.nx ? xbeg + a.ch : a.nx) : a.nx;
 
     acc_t acc[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) acc[nt] = acc_t{0, 0, 0, 0};
 
     T xpre[XPT], bpre[BPT], npre = T(0);
-    auto fetch = [&](int64_t x0) {      // global -> registers; nothing past point nx - 1, row rows_x - 1 or column n - 1 is read
+    auto fetch = [&](int64_t x0) {      // global -> registers; nothing past point xend - 1, row rows_x - 1 or column n - 1 is read
 #pragma unroll
         for (int e = 0; e < XPT; ++e) {
             const int idx = tid + RBF_WG * e, p = idx / (4 * KS), r = idx % (4 * KS);
-            xpre[e] = (idx < XE && x0 + p < a.nx && r < a.rows_x) ? a.X[(x0 + p) * a.ldx + r] : T(0);
+            xpre[e] = (idx < XE && x0 + p < xend && r < a.rows_x) ? a.X[(x0 + p) * a.ldx + r] : T(0);
         }
 #pragma unroll
         for (int e = 0; e < BPT; ++e) {
             const int idx = tid + RBF_WG * e, col = idx / TP, p = idx % TP;
-            bpre[e] = (idx < BE && x0 + p < a.nx && col < a.n) ? a.B[(x0 + p) + (int64_t)col * a.ldb] : T(0);
+            bpre[e] = (idx < BE && x0 + p < xend && col < a.n) ? a.B[(x0 + p) + (int64_t)col * a.ldb] : T(0);
         }
-        npre = (tid < TP && x0 + tid < a.nx) ? a.xn[x0 + tid] : T(0);
+        npre = (tid < TP && x0 + tid < xend) ? a.xn[x0 + tid] : T(0);
     };
     auto stash = [&](T* buf) {          // registers -> LDS
         T* Xs = buf; T* Bs = buf + TP * XS; T* Ns = Bs + 16 * NT * BSP;
@@ -120,15 +131,15 @@ __global__ __launch_bounds__(RBF_WG) void rbf_fused_kernel(const RbfArgs<T> a) {
         if (tid < TP) Ns[tid] = npre;
     };
 
-    const int64_t ntiles = (a.nx + TP - 1) / TP;
-    fetch(0);
+    const int64_t ntiles = (xend - xbeg + TP - 1) / TP;
+    fetch(xbeg);
     stash(lds);
     __syncthreads();
     for (int64_t t = 0; t < ntiles; ++t) {
         const T* buf = lds + (t & 1) * BUF;
         const T* Xs = buf; const T* Bs = buf + TP * XS; const T* Ns = Bs + 16 * NT * BSP;
         const bool more = t + 1 < ntiles;
-        if (more) fetch((t + 1) * TP);
+        if (more) fetch(xbeg + (t + 1) * TP);
 
         auto first = [&](int st) {      // S^T of sub-tile st
             acc_t s = acc_t{0, 0, 0, 0};
@@ -169,6 +180,18 @@ __global__ __launch_bounds__(RBF_WG) void rbf_fused_kernel(const RbfArgs<T> a) {
         __syncthreads();
     }
 
+    if constexpr (SPLIT) {      // raw sums; the rows past mz of the last Z tile are stored too (mzp covers them) and never read
+        T* const pr = a.part + (int64_t)blockIdx.y * a.n * a.mzp + zp;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int col = 16 * nt + M::drow_g(g, r);
+                if (col < a.n) pr[(int64_t)col * a.mzp] = acc[nt][r];
+            }
+        }
+        return;
+    }
     if (!zok) return;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -193,12 +216,52 @@ __global__ void rbf_scale_kernel(int64_t m, int64_t n, T beta, T* __restrict__ C
     *q = beta == T(0) ? T(0) : beta * *q;
 }
 
+// C (mz x n) = alpha * (part[0] + part[1] + ... + part[g - 1]) + beta * C, the sum in that order; beta == 0 never reads C
+template <typename T>
+__global__ void rbf_reduce_kernel(int64_t mz, int64_t n, int64_t g, int64_t mzp, const T* __restrict__ part, T alpha, T beta, T* __restrict__ C,
+                                  int64_t ldc) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= mz * n) return;
+    const int64_t row = t % mz, col = t / mz;
+    const T* p = part + col * mzp + row;
+    const int64_t step = n * mzp;
+    T s = p[0];
+#pragma unroll 8
+    for (int64_t b = 1; b < g; ++b) s += p[b * step];
+    T* q = C + row + col * ldc;
+    const T v = alpha * s;
+    *q = beta == T(0) ? v : v + beta * *q;
+}
+
+// the split rule (include/rlhip.h), a function of the shape alone: the number of chunks, and in *ch the points of X per chunk -- a multiple
+// of 64, hence of every staged tile length (nx when there is one chunk)
+inline int64_t rbf_split_chunks(int64_t mz, int64_t nx, int64_t* ch) {
+    *ch = nx;
+    if (mz < 0 || nx < 0) return -1;
+    if (mz == 0 || nx == 0) return 1;
+    const int64_t ztiles = (mz + RBF_ZP - 1) / RBF_ZP;
+    const int64_t by_work = (RLHIP_RBF_SPLIT_W + ztiles - 1) / ztiles, by_len = nx / RLHIP_RBF_SPLIT_CH_MIN;
+    const int64_t g = by_work < by_len ? by_work : by_len;
+    if (g < 2) return 1;
+    *ch = 64 * ((nx + 64 * g - 1) / (64 * g));
+    return (nx + *ch - 1) / *ch;      // no chunk is empty
+}
+
 template <typename T, int KS, int NT, bool MATERN>
 int launch_fused(rlhip_ctx* c, const RbfArgs<T>& a) {
     constexpr size_t bytes = 2 * (size_t)rbf_tile_elems<T, KS, NT>(rbf_tp<T, KS, NT>()) * sizeof(T);
     static_assert(bytes <= (size_t)RBF_LDS_CAP, "fused RBF kernel: the two staging buffers exceed the LDS budget");
     const int64_t wgs = (a.mz + RBF_ZP - 1) / RBF_ZP;
-    hipLaunchKernelGGL((rbf_fused_kernel<T, KS, NT, MATERN>), dim3((unsigned)wgs), dim3(RBF_WG), bytes, c->stream, a);
+    if (a.part) {      // split: a.ch points of X per workgroup, then the ordered sum of the partials
+        const int64_t g = (a.nx + a.ch - 1) / a.ch;
+        hipLaunchKernelGGL((rbf_fused_kernel<T, KS, NT, MATERN, true>), dim3((unsigned)wgs, (unsigned)g), dim3(RBF_WG), bytes, c->stream, a);
+        RLHIP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(rbf_reduce_kernel<T>, dim3((unsigned)((a.mz * a.n + 255) / 256)), dim3(256), 0, c->stream, a.mz, a.n, g, a.mzp, a.part,
+                           a.alpha, a.beta, a.C, a.ldc);
+        RLHIP_LAUNCH_CHECK();
+        return 0;
+    }
+    hipLaunchKernelGGL((rbf_fused_kernel<T, KS, NT, MATERN, false>), dim3((unsigned)wgs), dim3(RBF_WG), bytes, c->stream, a);
     RLHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -315,7 +378,16 @@ int pdk_cross_apply(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_
     if (rc) return rc;
     if (fused) {
         c->rbf_path_count[0]++;
-        RbfArgs<T> a{rows_x, mz, nx, n, Z, ldz, X, ldx, nr, nr + mz, B, ldb, C, ldc, alpha, beta, f.scale, f.third};
+        RbfArgs<T> a{rows_x, mz, nx, n, Z, ldz, X, ldx, nr, nr + mz, B, ldb, C, ldc, alpha, beta, f.scale, f.third, nullptr, 0, 0};
+        int64_t ch = nx;
+        const int64_t g = route == 2 ? rbf_split_chunks(mz, nx, &ch) : 1;
+        if (g > 1) {
+            a.ch = ch;
+            a.mzp = (mz + RBF_ZP - 1) / RBF_ZP * RBF_ZP;
+            a.part = ws.alloc<T>((size_t)(g * a.n * a.mzp));
+            if (!a.part) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
+            c->rbf_split_count++;
+        }
         return f.matern ? launch_fused_rows<T, true>(c, a) : launch_fused_rows<T, false>(c, a);
     }
     c->rbf_path_count[1]++;
@@ -370,6 +442,11 @@ int rlhip_rbf_cross_apply_f32(rlhip_ctx* c, int64_t rows_x, int64_t mz, const fl
     }
 RLHIP_DEFINE_PDK_CROSS(f64, double)
 RLHIP_DEFINE_PDK_CROSS(f32, float)
+int64_t rlhip_rbf_split_count(rlhip_ctx* c) { return c ? c->rbf_split_count : -1; }
+int64_t rlhip_rbf_split_chunks(int64_t mz, int64_t nx) {
+    int64_t ch;
+    return rbf_split_chunks(mz, nx, &ch);
+}
 int64_t rlhip_rbf_path_count(rlhip_ctx* c, int which) { return (c && which >= 55 && which <= 57) ? c->rbf_path_count[which - 55] : -1; }
 
 }  // extern "C"

@@ -174,6 +174,7 @@ struct rlhip_ctx {
     // the routes of the two-point-set RBF kernels (rbf.hip), read through rlhip_rbf_path_count: [0] = 55 fused cross apply, [1] = 56 composed
     // cross apply, [2] = 57 sqexp_cross_submatrix calls
     int64_t rbf_path_count[3] = {};
+    int64_t rbf_split_count = 0;     // fused cross applies that ran split over X (RLHIP_OPT_RBF_FUSED = 2, rlhip_rbf_split_count)
 };
 
 // every host wait of the library goes through here: the epoch lets deferred read-backs know that an earlier wait already covered them

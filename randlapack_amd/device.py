@@ -208,6 +208,10 @@ class Context:
         (include/rlhip.h rlhip_rbf_path_count)"""
         return int(self.lib.rlhip_rbf_path_count(self.h, which))
 
+    def rbf_split_count(self) -> int:
+        """fused cross applies that ran split over X (options(rbf_fused=2); include/rlhip.h rlhip_rbf_split_count)"""
+        return int(self.lib.rlhip_rbf_split_count(self.h))
+
     # ---- options (include/rlhip.h: enum rlhip_option; -1 restores the default)
     OPT = dict(cholqrq_one_stream=0, gesdd_gram=1, jacobi_persist=2, trsm_xasm=3, saso_mode=4, hqrrp_tall_panel=5,
                bqrrp_lookahead_min_elems=6, bqrrp_cholqr_fallback=7, cqrrpt_fold_pivoting=8, cqrrpt_split_qrcp=9, sparse_sketch_densify=10, jacobi_clock_holders=11,
@@ -807,6 +811,12 @@ def rbf_apply(ctx: Context, X, rows_x, dim, bandwidth, B, n, alpha=1.0, beta=0.0
 
 # ---- the RBF kernel between two point sets and KRR prediction (rbf.hip).  Z (mz, ldz) and X (nx, ldx) are column-major point tensors like X
 #      above; B (n, ldb >= nx) and C (n, ldc >= mz) column-major.
+def rbf_split_chunks(mz: int, nx: int) -> int:
+    """chunks of X that options(rbf_fused=2) cuts a cross apply with mz points of Z and nx points of X into: a function of the shape alone
+    (rlhip_rbf_split_chunks); needs no context and no device"""
+    return int(_lib.load().rlhip_rbf_split_chunks(mz, nx))
+
+
 def rbf_cross_apply(ctx: Context, Z, X, rows_x, mz, nx, bandwidth, B, n, alpha=1.0, beta=0.0, C_=None):
     """C (mz x n) = alpha K(Z, X) B + beta C (rlhip_rbf_cross_apply_*); returns C, column-major (n, mz) when allocated here"""
     torch = _torch()
