@@ -6,6 +6,8 @@
 // are the centres, column i solves  min_x |K(:,S) x - h_i|^2 + mu_i x^T K(S,S) x  directly -- no iteration, no tolerance, no preconditioner,
 // k coefficients per right-hand side.  krill_restricted is the same fit with the centres given by the caller (the reference's second TODO),
 // krr_predict_restricted evaluates either model at new points with mz x k kernel evaluations instead of mz x n.  DESIGN 4.24.
+// krill_restricted_rpchol_cv and krill_restricted_cv are the two fits with the regularization of every column chosen from a grid by
+// leave-one-out or generalized cross-validation, after one factorization and one SVD.  DESIGN 4.26.
 //
 // G is a regularized kernel operator as linops::RBFKernelMatrix: G.q, G.num_ops, G.regs (HOST), G.set_eval_includes_reg(bool), the
 // operator() of pcg and the diag() / columns() of rp_cholesky.  H and X are DEVICE n x ell arrays with stride n.
@@ -28,6 +30,21 @@
 
 namespace RandLAPACK {
 
+/// how krill_restricted_rpchol_cv / krill_restricted_cv choose among the values of their grid: the leave-one-out sum of squares, or
+/// generalized cross-validation n rss / (n - dof)^2
+enum class KrillCriterion { LeaveOneOut = 0, GCV = 1 };
+
+/// The regularization path of a restricted fit, on the HOST.  loo(m, c) and rss(m, c), g x ell with stride g: the sum over the
+/// n points of the squared leave-one-out residuals, and of the squared residuals, of column c fitted with mu_grid[m]; dof[m] = sum_j
+/// sigma_j^2 / (sigma_j^2 + mu_grid[m]), the trace of the hat matrix; best[c] the index the criterion chose for column c, best_mu[c] =
+/// mu_grid[best[c]].
+struct KrillRidgePath {
+    int64_t g = 0, ell = 0;
+    std::vector<double> loo, rss, dof;
+    std::vector<int64_t> best;
+    std::vector<double> best_mu;
+};
+
 namespace _krill_impl {
 template <typename T>
 const T* regs_ptr(const T* r) { return r; }
@@ -47,6 +64,15 @@ inline int gather_cols(blas::Queue& q, int64_t m, int64_t cnt, const int64_t* id
 }
 inline int gather_cols(blas::Queue& q, int64_t m, int64_t cnt, const int64_t* idx, const float* A, int64_t lda, float* out, int64_t ldo) {
     return rlhip_gather_cols_f32(q.ctx(), m, cnt, idx, A, lda, out, ldo);
+}
+
+inline int ridge_loo(blas::Queue& q, int64_t n, int64_t k, int64_t ell, int64_t g, const double* U, int64_t ldu, const double* sigma, const double* C,
+                     int64_t ldc, const double* H, int64_t ldh, const double* mus, double rcond, double* loo, double* rss) {
+    return rlhip_ridge_loo_f64(q.ctx(), n, k, ell, g, U, ldu, sigma, C, ldc, H, ldh, mus, rcond, loo, rss);
+}
+inline int ridge_loo(blas::Queue& q, int64_t n, int64_t k, int64_t ell, int64_t g, const float* U, int64_t ldu, const float* sigma, const float* C,
+                     int64_t ldc, const float* H, int64_t ldh, const float* mus, float rcond, double* loo, double* rss) {
+    return rlhip_ridge_loo_f32(q.ctx(), n, k, ell, g, U, ldu, sigma, C, ldc, H, ldh, mus, rcond, loo, rss);
 }
 
 /// set_eval_includes_reg(false) for a factorization, back to true on every way out of the scope
@@ -79,31 +105,157 @@ std::vector<T> restricted_mus(FUNC& G, int64_t ell) {
 /// composed route takes: R = triu(M^T), R^-1 = I R^-1 by that trsm (k x k), alpha = R^-1 Y by one small product.
 /// F is destroyed.  O(n k^2) work; scratch: one n x k buffer for U (the footprint of rpchol_pc_data), four k x k and two k x ell blocks.
 /// alpha (DEVICE, k x ell, ldalpha).  Host steps: the copy of the mus, and the reads gesdd makes to choose its route.
+/// It is written in three pieces -- restricted_alloc, restricted_head (through C = U^T H) and restricted_finish (from the filter on) -- so
+/// that restricted_tail_cv can look at U, sigma and C between the two; restricted_tail issues them in the order it always did.
+template <typename T>
+struct RestrictedWork { T *M, *R, *Rinv, *U, *VT, *sigma, *C, *Y; };
+
+template <typename T>
+RestrictedWork<T> restricted_alloc(blas::Scratch& ws, int64_t n, int64_t k, int64_t ell) {
+    RestrictedWork<T> w;
+    w.M = ws.alloc<T>(k * k);
+    w.R = ws.alloc<T>(k * k);
+    w.Rinv = ws.alloc<T>(k * k);
+    w.U = ws.alloc<T>(n * k);
+    w.VT = ws.alloc<T>(k * k);
+    w.sigma = ws.alloc<T>(k);
+    w.C = ws.alloc<T>(k * ell);
+    w.Y = ws.alloc<T>(k * ell);
+    return w;
+}
+
+/// the tail in front of the filter: M, R = triu(M^T), the thin SVD of F (U n x k with stride n, sigma, VT) and C = U^T H (k x ell, stride k)
+template <typename T>
+void restricted_head(blas::Queue& q, int64_t n, int64_t k, T* F, int64_t ldf, const int64_t* S_dev, int64_t ell, const T* H, int64_t ldh,
+                     RestrictedWork<T> const& w) {
+    blas::check(_rpchol_impl::gather_rows(q, k, S_dev, k, F, ldf, w.M, k), "gather_rows");
+    util::transposition(k, k, w.M, k, w.R, k, 0, q);
+    util::get_U(k, k, w.R, k, q);                     // what lies above M's diagonal is rounding: it is not used
+    lapack::gesdd(Job::SomeVec, n, k, F, ldf, w.sigma, w.U, n, w.VT, k, q);
+    blas::gemm(Layout::ColMajor, Op::Trans, Op::NoTrans, k, ell, n, (T)1, w.U, n, H, ldh, (T)0, w.C, k, q);
+}
+
+/// the tail from the filter on, with the num_mus (1 or ell) regularizations mus_dev (DEVICE); C is overwritten
+template <typename T>
+void restricted_finish(blas::Queue& q, int64_t n, int64_t k, int64_t ell, RestrictedWork<T> const& w, const T* mus_dev, int64_t num_mus, T* alpha,
+                       int64_t ldalpha) {
+    blas::check(ridge_filter(q, k, ell, w.sigma, mus_dev, num_mus, (T)n * std::numeric_limits<T>::epsilon(), w.C, k), "ridge_filter");
+    blas::gemm(Layout::ColMajor, Op::Trans, Op::NoTrans, k, ell, k, (T)1, w.VT, k, w.C, k, (T)0, w.Y, k, q);
+    util::eye(k, k, w.Rinv, q);
+    blas::trsm(Layout::ColMajor, Side::Right, Uplo::Upper, Op::NoTrans, Diag::NonUnit, k, k, (T)1, w.R, k, w.Rinv, k, q);
+    blas::gemm(Layout::ColMajor, Op::NoTrans, Op::NoTrans, k, ell, k, (T)1, w.Rinv, k, w.Y, k, (T)0, alpha, ldalpha, q);
+}
+
 template <typename T>
 void restricted_tail(blas::Queue& q, int64_t n, int64_t k, T* F, int64_t ldf, const int64_t* S_dev, int64_t ell, const T* H, int64_t ldh,
                      std::vector<T> const& mus, T* alpha, int64_t ldalpha) {
     blas::Scratch ws(q);
-    T* M = ws.alloc<T>(k * k);
-    T* R = ws.alloc<T>(k * k);
-    T* Rinv = ws.alloc<T>(k * k);
-    T* U = ws.alloc<T>(n * k);
-    T* VT = ws.alloc<T>(k * k);
-    T* sigma = ws.alloc<T>(k);
-    T* C = ws.alloc<T>(k * ell);
-    T* Y = ws.alloc<T>(k * ell);
+    const RestrictedWork<T> w = restricted_alloc<T>(ws, n, k, ell);
     T* mus_dev = ws.alloc<T>((int64_t)mus.size());
     blas::copy_to_device((int64_t)mus.size(), mus.data(), mus_dev, q);
-    blas::check(_rpchol_impl::gather_rows(q, k, S_dev, k, F, ldf, M, k), "gather_rows");
-    util::transposition(k, k, M, k, R, k, 0, q);
-    util::get_U(k, k, R, k, q);                       // what lies above M's diagonal is rounding: it is not used
-    lapack::gesdd(Job::SomeVec, n, k, F, ldf, sigma, U, n, VT, k, q);
-    blas::gemm(Layout::ColMajor, Op::Trans, Op::NoTrans, k, ell, n, (T)1, U, n, H, ldh, (T)0, C, k, q);
-    blas::check(ridge_filter(q, k, ell, sigma, mus_dev, (int64_t)mus.size(), (T)n * std::numeric_limits<T>::epsilon(), C, k), "ridge_filter");
-    blas::gemm(Layout::ColMajor, Op::Trans, Op::NoTrans, k, ell, k, (T)1, VT, k, C, k, (T)0, Y, k, q);
-    util::eye(k, k, Rinv, q);
-    blas::trsm(Layout::ColMajor, Side::Right, Uplo::Upper, Op::NoTrans, Diag::NonUnit, k, k, (T)1, R, k, Rinv, k, q);
-    blas::gemm(Layout::ColMajor, Op::NoTrans, Op::NoTrans, k, ell, k, (T)1, Rinv, k, Y, k, (T)0, alpha, ldalpha, q);
+    restricted_head(q, n, k, F, ldf, S_dev, ell, H, ldh, w);
+    restricted_finish(q, n, k, ell, w, mus_dev, (int64_t)mus.size(), alpha, ldalpha);
 }
+
+/// dof[m] = sum_j d_jm with the d of rlhip_ridge_loo_*: sigma_j^2 / (sigma_j^2 + mu_m); mu_m == 0: 1, or 0 where sigma_j <= rcond sigma_0
+template <typename T>
+std::vector<double> ridge_dof(std::vector<T> const& sigma, int64_t g, const T* mu_grid, T rcond) {
+    std::vector<double> dof((size_t)g, 0.0);
+    const double cut = sigma.empty() ? 0.0 : (double)rcond * (double)sigma[0];
+    for (int64_t m = 0; m < g; ++m) {
+        const double mu = (double)mu_grid[m];
+        for (T sj : sigma) {
+            const double sg = (double)sj;
+            dof[(size_t)m] += mu == 0.0 ? (sg <= cut ? 0.0 : 1.0) : (sg * sg) / std::fma(sg, sg, mu);
+        }
+    }
+    return dof;
+}
+
+/// per column the index of the smallest finite criterion, the lower index on a tie; a column without a finite value throws
+inline void ridge_select(int64_t n, KrillCriterion criterion, KrillRidgePath& path) {
+    const int64_t g = path.g, ell = path.ell;
+    path.best.assign((size_t)ell, -1);
+    for (int64_t c = 0; c < ell; ++c) {
+        double best = 0;
+        for (int64_t m = 0; m < g; ++m) {
+            double v = path.loo[(size_t)(m + c * g)];
+            if (criterion == KrillCriterion::GCV) {
+                const double left = (double)n - path.dof[(size_t)m];
+                v = (double)n * path.rss[(size_t)(m + c * g)] / (left * left);
+            }
+            if (std::isfinite(v) && (path.best[(size_t)c] < 0 || v < best)) {
+                best = v;
+                path.best[(size_t)c] = m;
+            }
+        }
+        if (path.best[(size_t)c] < 0) throw Error("krill_restricted_cv: no value of the grid gives column " + std::to_string(c) + " a finite criterion");
+    }
+}
+
+template <typename T>
+void check_mu_grid(int64_t g, const T* mu_grid, KrillCriterion criterion) {
+    randlapack_require(g >= 1) << "g=" << g << ": the grid must hold at least one regularization";
+    randlapack_require(mu_grid != nullptr) << "mu_grid buffer must not be null";
+    for (int64_t m = 0; m < g; ++m) randlapack_require(mu_grid[m] >= (T)0) << "mu_grid[" << m << "]=" << mu_grid[m] << " must be >= 0";
+    randlapack_require(criterion == KrillCriterion::LeaveOneOut || criterion == KrillCriterion::GCV) << "unknown criterion";
+}
+
+/// restricted_tail with the regularization of every column chosen from the HOST grid mu_grid[g]: head, rlhip_ridge_loo_* on U, sigma and C,
+/// the selection on the host, then the filter with the ell chosen values and the rest of the tail as it is.
+template <typename T>
+void restricted_tail_cv(blas::Queue& q, int64_t n, int64_t k, T* F, int64_t ldf, const int64_t* S_dev, int64_t ell, const T* H, int64_t ldh, int64_t g,
+                        const T* mu_grid, KrillCriterion criterion, KrillRidgePath& path, T* alpha, int64_t ldalpha) {
+    blas::Scratch ws(q);
+    const RestrictedWork<T> w = restricted_alloc<T>(ws, n, k, ell);
+    T* grid_dev = ws.alloc<T>(g);
+    T* mus_dev = ws.alloc<T>(ell);
+    double* table = ws.alloc<double>(2 * g * ell);
+    const T rcond = (T)n * std::numeric_limits<T>::epsilon();
+    blas::copy_to_device(g, mu_grid, grid_dev, q);
+    restricted_head(q, n, k, F, ldf, S_dev, ell, H, ldh, w);
+    blas::check(ridge_loo(q, n, k, ell, g, w.U, n, w.sigma, w.C, k, H, ldh, grid_dev, rcond, table, table + g * ell), "ridge_loo");
+    path.g = g;
+    path.ell = ell;
+    path.loo.assign((size_t)(g * ell), 0.0);
+    path.rss.assign((size_t)(g * ell), 0.0);
+    std::vector<T> sigma((size_t)k);
+    blas::copy_to_host(g * ell, table, path.loo.data(), q);
+    blas::copy_to_host(g * ell, table + g * ell, path.rss.data(), q);
+    blas::copy_to_host(k, w.sigma, sigma.data(), q);
+    q.sync();
+    path.dof = ridge_dof(sigma, g, mu_grid, rcond);
+    ridge_select(n, criterion, path);
+    std::vector<T> mus((size_t)ell);
+    path.best_mu.assign((size_t)ell, 0.0);
+    for (int64_t c = 0; c < ell; ++c) {
+        mus[(size_t)c] = mu_grid[path.best[(size_t)c]];
+        path.best_mu[(size_t)c] = (double)mus[(size_t)c];
+    }
+    blas::copy_to_device(ell, mus.data(), mus_dev, q);
+    restricted_finish(q, n, k, ell, w, mus_dev, ell, alpha, ldalpha);
+}
+
+/// what the two pairs of fits differ in: where the regularizations come from (checked by prepare()) and the tail that uses them
+template <typename T, typename FUNC>
+struct FixedRidge {
+    std::vector<T> mus;
+    void prepare(FUNC& G, int64_t ell) { mus = restricted_mus<T>(G, ell); }
+    void tail(blas::Queue& q, int64_t n, int64_t k, T* F, const int64_t* S_dev, int64_t ell, const T* H, int64_t ldh, T* alpha, int64_t ldalpha) {
+        restricted_tail(q, n, k, F, n, S_dev, ell, H, ldh, mus, alpha, ldalpha);
+    }
+};
+template <typename T, typename FUNC>
+struct GridRidge {
+    int64_t g;
+    const T* mu_grid;
+    KrillCriterion criterion;
+    KrillRidgePath& path;
+    void prepare(FUNC&, int64_t) { check_mu_grid(g, mu_grid, criterion); }
+    void tail(blas::Queue& q, int64_t n, int64_t k, T* F, const int64_t* S_dev, int64_t ell, const T* H, int64_t ldh, T* alpha, int64_t ldalpha) {
+        restricted_tail_cv(q, n, k, F, n, S_dev, ell, H, ldh, g, mu_grid, criterion, path, alpha, ldalpha);
+    }
+};
 }  // namespace _krill_impl
 
 template <typename T, typename FUNC, typename SEMINORM, typename STATE>
@@ -159,21 +311,18 @@ void krr_predict(linops::RBFCrossKernel<T>& Kzx, int64_t s, const T* coeffs, int
 /// block (0; 1: the residual diagonal is exhausted; 2: it has a negative or NaN entry) and potrf's info of the block that broke down
 struct KrillRestrictedInfo { int w_status = 0, c_status = 0; };
 
-/// Restricted kernel ridge regression on the pivots of randomly pivoted Cholesky (see the head of this file and _krill_impl::restricted_tail).
-/// k: in = the number of centres asked for (< 0: sqrt(n)), out = the achieved rank.  S (HOST, k_in) receives the centres in selection
-/// order, alpha (DEVICE, k_in x ell, ldalpha) the coefficients: the fitted function of column i is sum_j alpha(j, i) K(., x_S[j]).  When the
-/// factorization stops early, rows k_out .. k_in of alpha are zero and S[k_out ..] is -1; an achieved rank of 0 throws.  H (DEVICE, n x ell,
-/// ldh).  O(n k^2) as rp_cholesky itself; scratch: the n x k factor and one more n x k buffer for the SVD's U.  Returns the advanced state.
-template <typename T, typename FUNC, typename STATE>
-STATE krill_restricted_rpchol(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t& k, int64_t* S, T* alpha, int64_t ldalpha,
-                              STATE state, int64_t rpchol_block_size = -1, KrillRestrictedInfo* info = nullptr) {
+namespace _krill_impl {
+/// krill_restricted_rpchol and krill_restricted_rpchol_cv: RIDGE is FixedRidge or GridRidge
+template <typename T, typename FUNC, typename STATE, typename RIDGE>
+STATE restricted_rpchol(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t& k, int64_t* S, T* alpha, int64_t ldalpha, STATE state,
+                        int64_t rpchol_block_size, KrillRestrictedInfo* info, RIDGE& ridge) {
     randlapack_require(n > 0) << "n=" << n << " must be > 0";
     randlapack_require(ell > 0) << "ell=" << ell << " must be > 0";
     randlapack_require(H != nullptr) << "H buffer must not be null";
     randlapack_require(ldh >= n) << "ldh=" << ldh << " < n=" << n;
     randlapack_require(S != nullptr) << "S buffer must not be null";
     randlapack_require(alpha != nullptr) << "alpha buffer must not be null";
-    const std::vector<T> mus = _krill_impl::restricted_mus<T>(G, ell);
+    ridge.prepare(G, ell);
     if (rpchol_block_size < 0) rpchol_block_size = std::max<int64_t>(1, std::min((int64_t)64, n / 4));
     if (k < 0) k = (int64_t)std::sqrt(n);
     randlapack_require(k >= 1 && k <= n) << "k=" << k << " must be in [1, n=" << n << "]";
@@ -186,7 +335,7 @@ STATE krill_restricted_rpchol(int64_t n, FUNC& G, int64_t ell, const T* H, int64
     int64_t* S_dev = ws.alloc<int64_t>(k_in);
     _rpchol_impl::Status st;
     {
-        _krill_impl::UnregularizedScope<FUNC> unreg(G);
+        UnregularizedScope<FUNC> unreg(G);
         st = _rpchol_impl::run(n, G, k, S, F, n, rpchol_block_size, state);
     }
     if (info) {
@@ -199,15 +348,13 @@ STATE krill_restricted_rpchol(int64_t n, FUNC& G, int64_t ell, const T* H, int64
     std::fill(S + k, S + k_in, (int64_t)-1);
     lapack::laset(MatrixType::General, k_in, ell, (T)0, (T)0, alpha, ldalpha, q);
     blas::copy_to_device(k, S, S_dev, q);
-    _krill_impl::restricted_tail(q, n, k, F, n, S_dev, ell, H, ldh, mus, alpha, ldalpha);
+    ridge.tail(q, n, k, F, S_dev, ell, H, ldh, alpha, ldalpha);
     return state;
 }
 
-/// The same fit with the k centres S (HOST, distinct, each in [0, n)) given: one forced-pivot block of randomly pivoted Cholesky -- A =
-/// K(:, S), potrf(Upper) of A(S, :), F = A U^-1 -- in front of the same tail.  Returns potrf's info of K(S,S): 0, or the 1-based position of
-/// the first centre that depends on the ones before it; then alpha is untouched (nothing is truncated silently).
-template <typename T, typename FUNC>
-int64_t krill_restricted(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t k, const int64_t* S, T* alpha, int64_t ldalpha) {
+/// krill_restricted and krill_restricted_cv
+template <typename T, typename FUNC, typename RIDGE>
+int64_t restricted_given(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t k, const int64_t* S, T* alpha, int64_t ldalpha, RIDGE& ridge) {
     randlapack_require(n > 0) << "n=" << n << " must be > 0";
     randlapack_require(ell > 0) << "ell=" << ell << " must be > 0";
     randlapack_require(H != nullptr) << "H buffer must not be null";
@@ -217,7 +364,7 @@ int64_t krill_restricted(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ld
     randlapack_require(k >= 1 && k <= n) << "k=" << k << " must be in [1, n=" << n << "]";
     randlapack_require(ldalpha >= k) << "ldalpha=" << ldalpha << " < k=" << k;
     for (int64_t j = 0; j < k; ++j) randlapack_require(S[j] >= 0 && S[j] < n) << "S[" << j << "]=" << S[j] << " must be in [0, n=" << n << ")";
-    const std::vector<T> mus = _krill_impl::restricted_mus<T>(G, ell);
+    ridge.prepare(G, ell);
 
     blas::Queue& q = G.q;
     blas::Scratch ws(q);
@@ -226,7 +373,7 @@ int64_t krill_restricted(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ld
     int64_t* S_dev = ws.alloc<int64_t>(k);
     blas::copy_to_device(k, S, S_dev, q);
     {
-        _krill_impl::UnregularizedScope<FUNC> unreg(G);
+        UnregularizedScope<FUNC> unreg(G);
         G.columns(k, S_dev, F, n);
     }
     blas::check(_rpchol_impl::gather_rows(q, k, S_dev, k, F, n, W, k), "gather_rows");
@@ -234,8 +381,51 @@ int64_t krill_restricted(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ld
     if (info) return info;
     util::get_U(k, k, W, k, q);
     blas::trsm(Layout::ColMajor, Side::Right, Uplo::Upper, Op::NoTrans, Diag::NonUnit, n, k, (T)1, W, k, F, n, q);
-    _krill_impl::restricted_tail(q, n, k, F, n, S_dev, ell, H, ldh, mus, alpha, ldalpha);
+    ridge.tail(q, n, k, F, S_dev, ell, H, ldh, alpha, ldalpha);
     return 0;
+}
+}  // namespace _krill_impl
+
+/// Restricted kernel ridge regression on the pivots of randomly pivoted Cholesky (see the head of this file and _krill_impl::restricted_tail).
+/// k: in = the number of centres asked for (< 0: sqrt(n)), out = the achieved rank.  S (HOST, k_in) receives the centres in selection
+/// order, alpha (DEVICE, k_in x ell, ldalpha) the coefficients: the fitted function of column i is sum_j alpha(j, i) K(., x_S[j]).  When the
+/// factorization stops early, rows k_out .. k_in of alpha are zero and S[k_out ..] is -1; an achieved rank of 0 throws.  H (DEVICE, n x ell,
+/// ldh).  O(n k^2) as rp_cholesky itself; scratch: the n x k factor and one more n x k buffer for the SVD's U.  Returns the advanced state.
+template <typename T, typename FUNC, typename STATE>
+STATE krill_restricted_rpchol(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t& k, int64_t* S, T* alpha, int64_t ldalpha,
+                              STATE state, int64_t rpchol_block_size = -1, KrillRestrictedInfo* info = nullptr) {
+    _krill_impl::FixedRidge<T, FUNC> ridge;
+    return _krill_impl::restricted_rpchol(n, G, ell, H, ldh, k, S, alpha, ldalpha, state, rpchol_block_size, info, ridge);
+}
+
+/// The same fit with the k centres S (HOST, distinct, each in [0, n)) given: one forced-pivot block of randomly pivoted Cholesky -- A =
+/// K(:, S), potrf(Upper) of A(S, :), F = A U^-1 -- in front of the same tail.  Returns potrf's info of K(S,S): 0, or the 1-based position of
+/// the first centre that depends on the ones before it; then alpha is untouched (nothing is truncated silently).
+template <typename T, typename FUNC>
+int64_t krill_restricted(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t k, const int64_t* S, T* alpha, int64_t ldalpha) {
+    _krill_impl::FixedRidge<T, FUNC> ridge;
+    return _krill_impl::restricted_given(n, G, ell, H, ldh, k, S, alpha, ldalpha, ridge);
+}
+
+/// krill_restricted_rpchol with the regularization of every column chosen from a grid: mu_grid (HOST, g >= 1 values >= 0) takes
+/// the place of G.regs, which is not read.  One factorization and one thin SVD serve the whole grid: rlhip_ridge_loo_* returns, for every grid
+/// value and column, the sum of squared leave-one-out residuals and of squared residuals over the n points (for a centre the centre stays
+/// and its target is left out).  Column c is then fitted with the grid value of the smallest finite criterion (the lower index on a tie); a
+/// column without a finite value throws.  path receives the tables and the choice; everything else is as in krill_restricted_rpchol.
+template <typename T, typename FUNC, typename STATE>
+STATE krill_restricted_rpchol_cv(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t g, const T* mu_grid, KrillCriterion criterion,
+                                 int64_t& k, int64_t* S, T* alpha, int64_t ldalpha, KrillRidgePath& path, STATE state, int64_t rpchol_block_size = -1,
+                                 KrillRestrictedInfo* info = nullptr) {
+    _krill_impl::GridRidge<T, FUNC> ridge{g, mu_grid, criterion, path};
+    return _krill_impl::restricted_rpchol(n, G, ell, H, ldh, k, S, alpha, ldalpha, state, rpchol_block_size, info, ridge);
+}
+
+/// krill_restricted with the regularizations chosen from mu_grid in the same way.  A non-zero return (potrf's info) leaves alpha and path untouched.
+template <typename T, typename FUNC>
+int64_t krill_restricted_cv(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t g, const T* mu_grid, KrillCriterion criterion, int64_t k,
+                            const int64_t* S, T* alpha, int64_t ldalpha, KrillRidgePath& path) {
+    _krill_impl::GridRidge<T, FUNC> ridge{g, mu_grid, criterion, path};
+    return _krill_impl::restricted_given(n, G, ell, H, ldh, k, S, alpha, ldalpha, ridge);
 }
 
 /// Prediction with the coefficients of a restricted fit: Y (mz x s, ldy) = K(Z, X(:, S)) alpha (k x s, ldalpha), with G's points, kernel

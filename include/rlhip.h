@@ -579,6 +579,24 @@ int rlhip_ridge_filter_f64(rlhip_ctx* ctx, int64_t k, int64_t s, const double* s
                            double* C, int64_t ldc);
 int rlhip_ridge_filter_f32(rlhip_ctx* ctx, int64_t k, int64_t s, const float* sigma_dev, const float* mus_dev, int64_t num_mus, float rcond,
                            float* C, int64_t ldc);
+/* rlhip_ridge_loo_*: leave-one-out and residual sums of restricted kernel ridge regression over a grid of regularizations (rl_krill.hh,
+ * krill_restricted_rpchol_cv).  U (n x k, ldu), sigma_dev (k, decreasing) are the thin SVD of the factor, C = U^T H (k x ell,
+ * ldc), H the targets (n x ell, ldh), mus_dev g regularizations >= 0, all DEVICE and of type T.  With d_jm = sigma_j^2 / (sigma_j^2 + mu_m)
+ * (mu_m == 0: 1, or 0 where sigma_j <= rcond * sigma_0), s_im = sum_j U_ij^2 d_jm and yhat_imc = sum_j U_ij d_jm C_jc:
+ *   loo_dev(m, c) = sum_i ((h_ic - yhat_imc) / (1 - s_im))^2,   rss_dev(m, c) = sum_i (h_ic - yhat_imc)^2,
+ * both g x ell with leading dimension g, double in both precisions.  d, every sum over j and every sum over i are taken in double.  A row
+ * with 1 - s_im == 0 makes its entry of loo inf (or NaN); nothing is filtered.  No atomics: one partial per workgroup of 256 rows in the
+ * scratch arena (2 ceil(n / 256) g ell doubles) and a second launch that adds them in a fixed order, so the bits depend on the shapes and
+ * the data alone.  n, k, ell or g == 0 returns 0 and writes nothing.  Rows beyond n (k) of U and H (C) are never read.  Argument codes,
+ * checked before anything is enqueued: -2 n < 0, -3 k < 0, -4 ell < 0, -5 g < 0, -7 ldu < max(1, n), -10 ldc < max(1, k), -12 ldh <
+ * max(1, n); then, when no size is 0: -6 U NULL, -8 sigma_dev NULL, -9 C NULL, -11 H NULL, -13 mus_dev NULL, -14 rcond < 0 or NaN, -15
+ * loo_dev NULL, -16 rss_dev NULL, -100 more than 65535 chunks of 8 grid values or of 4 columns. */
+int rlhip_ridge_loo_f64(rlhip_ctx* ctx, int64_t n, int64_t k, int64_t ell, int64_t g, const double* U, int64_t ldu, const double* sigma_dev,
+                        const double* C, int64_t ldc, const double* H, int64_t ldh, const double* mus_dev, double rcond, double* loo_dev,
+                        double* rss_dev);
+int rlhip_ridge_loo_f32(rlhip_ctx* ctx, int64_t n, int64_t k, int64_t ell, int64_t g, const float* U, int64_t ldu, const float* sigma_dev,
+                        const float* C, int64_t ldc, const float* H, int64_t ldh, const float* mus_dev, float rcond, double* loo_dev,
+                        double* rss_dev);
 /* The routes of the two update kernels, one count per call: 43 a fused rlhip_pcg_update_xr, 44 a fused rlhip_pcg_update_p, 45 either one on
  * the composed route (s > 64).  They continue the numbering of rlhip_path_count below but are read here: that function's range ends at 42
  * and answers -1 beyond it.  -1 for any other index. */

@@ -314,6 +314,29 @@ int rlhip_drv_krill_restricted_pdk_f64(rlhip_ctx* ctx, const double* X_pts, int6
 int rlhip_drv_krill_restricted_pdk_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, float bandwidth,
                                        const float* regs_host, int64_t num_ops, const float* H, int64_t ldh, int64_t s, int64_t k, const int64_t* S_host,
                                        float* alpha, int64_t ldalpha, int64_t* info);
+/* krill_restricted_rpchol_cv and krill_restricted_cv: the two fits above with the regularization of every column chosen from the
+ * HOST grid mu_grid_host[g] (g >= 1, every value >= 0) in place of regs_host.  criterion: 0 leave-one-out, 1 generalized cross-validation
+ * n rss / (n - dof)^2; per column the smallest finite value wins, the lower index on a tie.  HOST outputs, each may be NULL: loo_host and
+ * rss_host (g x s, stride g: the sums over the n points of the squared leave-one-out residuals and of the squared residuals), dof_host (g),
+ * best_host (s indices into the grid), best_mu_host (s).  alpha is the fit with best_mu_host.  An empty grid, a negative grid value, an
+ * unknown criterion, a NULL buffer or a column without a finite criterion return -100 with rlhip_last_error().  With *info != 0
+ * krill_restricted_cv leaves alpha and the HOST outputs untouched. */
+int rlhip_drv_krill_restricted_rpchol_cv_pdk_f64(rlhip_ctx* ctx, const double* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, double bandwidth,
+                                                 const double* mu_grid_host, int64_t g, int criterion, const double* H, int64_t ldh, int64_t s, int64_t* k,
+                                                 int64_t b, int64_t* S_host, double* alpha, int64_t ldalpha, uint32_t state[6], int status[2],
+                                                 double* loo_host, double* rss_host, double* dof_host, int64_t* best_host, double* best_mu_host);
+int rlhip_drv_krill_restricted_rpchol_cv_pdk_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, float bandwidth,
+                                                 const float* mu_grid_host, int64_t g, int criterion, const float* H, int64_t ldh, int64_t s, int64_t* k,
+                                                 int64_t b, int64_t* S_host, float* alpha, int64_t ldalpha, uint32_t state[6], int status[2],
+                                                 double* loo_host, double* rss_host, double* dof_host, int64_t* best_host, double* best_mu_host);
+int rlhip_drv_krill_restricted_cv_pdk_f64(rlhip_ctx* ctx, const double* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, double bandwidth,
+                                          const double* mu_grid_host, int64_t g, int criterion, const double* H, int64_t ldh, int64_t s, int64_t k,
+                                          const int64_t* S_host, double* alpha, int64_t ldalpha, int64_t* info, double* loo_host, double* rss_host,
+                                          double* dof_host, int64_t* best_host, double* best_mu_host);
+int rlhip_drv_krill_restricted_cv_pdk_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, float bandwidth,
+                                          const float* mu_grid_host, int64_t g, int criterion, const float* H, int64_t ldh, int64_t s, int64_t k,
+                                          const int64_t* S_host, float* alpha, int64_t ldalpha, int64_t* info, double* loo_host, double* rss_host,
+                                          double* dof_host, int64_t* best_host, double* best_mu_host);
 /* krr_predict_restricted: Y (mz x s, ldy) = K(Z, X_pts(:, S)) alpha -- the k centre columns are gathered and krr_predict runs on them: mz x k
  * kernel evaluations.  Z is rows_x x mz (ldz), X_pts rows_x x n (ldx); k <= 65535. */
 int rlhip_drv_krr_predict_restricted_pdk_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t n, const double* X_pts,

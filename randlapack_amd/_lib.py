@@ -302,6 +302,16 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # restricted kernel ridge
                                                                  c_i64, c_vp, c_i64]),
     })
 
+for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the regularization path of the restricted fits (pcg.hip rlhip_ridge_loo_*, rl_krill.hh)
+    _Tp, _dp = C.POINTER(_T), C.POINTER(c_dbl)
+    SIGNATURES.update({
+        f"rlhip_ridge_loo_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, _T, c_vp, c_vp]),
+        f"rlhip_drv_krill_restricted_rpchol_cv_pdk_{_suf}": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, _T, _Tp, c_i64, c_int, c_vp, c_i64, c_i64, i64p,
+                                                                     c_i64, i64p, c_vp, c_i64, u32p, intp, _dp, _dp, _dp, i64p, _dp]),
+        f"rlhip_drv_krill_restricted_cv_pdk_{_suf}": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, _T, _Tp, c_i64, c_int, c_vp, c_i64, c_i64, c_i64, i64p,
+                                                              c_vp, c_i64, i64p, _dp, _dp, _dp, i64p, _dp]),
+    })
+
 _lib = None
 
 

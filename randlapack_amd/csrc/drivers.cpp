@@ -934,6 +934,54 @@ int drv_krill_restricted(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t ro
         return 0;
     });
 }
+inline void store_path(RandLAPACK::KrillRidgePath const& path, double* loo, double* rss, double* dof, int64_t* best, double* best_mu) {
+    if (loo) std::copy(path.loo.begin(), path.loo.end(), loo);
+    if (rss) std::copy(path.rss.begin(), path.rss.end(), rss);
+    if (dof) std::copy(path.dof.begin(), path.dof.end(), dof);
+    if (best) std::copy(path.best.begin(), path.best.end(), best);
+    if (best_mu) std::copy(path.best_mu.begin(), path.best_mu.end(), best_mu);
+}
+template <typename T>
+int drv_krill_restricted_rpchol_cv(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth, const T* mu_grid_host,
+                                   int64_t g, int criterion, const T* H, int64_t ldh, int64_t s, int64_t* k, int64_t b, int64_t* S_host, T* alpha,
+                                   int64_t ldalpha, uint32_t state[6], int status[2], double* loo, double* rss, double* dof, int64_t* best,
+                                   double* best_mu) {
+    if (!pdk_known(kernel)) return -6;
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (!k || !state || !status) throw RandLAPACK::Error("krill_restricted_rpchol_cv: k, state and status must not be null");
+        std::vector<T> regs{(T)0};                                      // the operator's own regularization is not read
+        lo::RBFKernelMatrix<T> G(n, X_pts, rows_x, bandwidth, regs, q, ldx);
+        G.set_kernel((RandLAPACK::PDKernel)kernel);
+        State st = load_state(state);
+        RandLAPACK::KrillRestrictedInfo info;
+        RandLAPACK::KrillRidgePath path;
+        st = RandLAPACK::krill_restricted_rpchol_cv(n, G, s, H, ldh, g, mu_grid_host, (RandLAPACK::KrillCriterion)criterion, *k, S_host, alpha, ldalpha,
+                                                    path, st, b, &info);
+        store_state(st, state);
+        status[0] = info.w_status;
+        status[1] = info.c_status;
+        store_path(path, loo, rss, dof, best, best_mu);
+        return 0;
+    });
+}
+template <typename T>
+int drv_krill_restricted_cv(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth, const T* mu_grid_host,
+                            int64_t g, int criterion, const T* H, int64_t ldh, int64_t s, int64_t k, const int64_t* S_host, T* alpha, int64_t ldalpha,
+                            int64_t* info, double* loo, double* rss, double* dof, int64_t* best, double* best_mu) {
+    if (!pdk_known(kernel)) return -6;
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (!info) throw RandLAPACK::Error("krill_restricted_cv: info must not be null");
+        std::vector<T> regs{(T)0};
+        lo::RBFKernelMatrix<T> G(n, X_pts, rows_x, bandwidth, regs, q, ldx);
+        G.set_kernel((RandLAPACK::PDKernel)kernel);
+        RandLAPACK::KrillRidgePath path;
+        *info = RandLAPACK::krill_restricted_cv(n, G, s, H, ldh, g, mu_grid_host, (RandLAPACK::KrillCriterion)criterion, k, S_host, alpha, ldalpha, path);
+        if (*info == 0) store_path(path, loo, rss, dof, best, best_mu);
+        return 0;
+    });
+}
 template <typename T>
 int drv_krr_predict_restricted(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts, int64_t ldx, int kernel,
                                T bandwidth, int64_t k, const int64_t* S_host, int64_t s, const T* alpha, int64_t ldalpha, T* Y, int64_t ldy) {
@@ -1031,6 +1079,21 @@ extern "C" {
                                                    const T* X_pts, int64_t ldx, int kernel, T bandwidth, int64_t k, const int64_t* S_host,        \
                                                    int64_t s, const T* alpha, int64_t ldalpha, T* Y, int64_t ldy) {                               \
         return drv_krr_predict_restricted<T>(ctx, rows_x, mz, Z, ldz, n, X_pts, ldx, kernel, bandwidth, k, S_host, s, alpha, ldalpha, Y, ldy);    \
+    }                                                                                                                                             \
+    int rlhip_drv_krill_restricted_rpchol_cv_pdk_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel,        \
+                                                       T bandwidth, const T* mu_grid_host, int64_t g, int criterion, const T* H, int64_t ldh,     \
+                                                       int64_t s, int64_t* k, int64_t b, int64_t* S_host, T* alpha, int64_t ldalpha,              \
+                                                       uint32_t state[6], int status[2], double* loo_host, double* rss_host, double* dof_host,    \
+                                                       int64_t* best_host, double* best_mu_host) {                                                \
+        return drv_krill_restricted_rpchol_cv<T>(ctx, X_pts, ldx, rows_x, n, kernel, bandwidth, mu_grid_host, g, criterion, H, ldh, s, k, b, S_host,\
+                                                 alpha, ldalpha, state, status, loo_host, rss_host, dof_host, best_host, best_mu_host);           \
+    }                                                                                                                                             \
+    int rlhip_drv_krill_restricted_cv_pdk_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth,  \
+                                                const T* mu_grid_host, int64_t g, int criterion, const T* H, int64_t ldh, int64_t s, int64_t k,   \
+                                                const int64_t* S_host, T* alpha, int64_t ldalpha, int64_t* info, double* loo_host,                \
+                                                double* rss_host, double* dof_host, int64_t* best_host, double* best_mu_host) {                   \
+        return drv_krill_restricted_cv<T>(ctx, X_pts, ldx, rows_x, n, kernel, bandwidth, mu_grid_host, g, criterion, H, ldh, s, k, S_host, alpha, \
+                                          ldalpha, info, loo_host, rss_host, dof_host, best_host, best_mu_host);                                  \
     }
 RLHIP_DEFINE_PCG_DRIVERS(f64, double)
 RLHIP_DEFINE_PCG_DRIVERS(f32, float)

@@ -9,6 +9,8 @@
 //                          kernel and one axpby kernel, then the squared column norms of the result.
 //   ridge_filter           the filter of restricted kernel ridge regression (include/RandLAPACK_amd/rl_krill.hh, restricted_tail): one
 //                          element-wise kernel between the two small products of that tail.
+//   ridge_loo              the leave-one-out and residual sums of that fit for a grid of regularizations (rl_krill.hh, ridge_path; DESIGN
+//                          4.26): one pass over the U of the thin SVD, a thread owns a row, every sum in double.
 //
 // No kernel here waits for another workgroup and none uses a floating-point atomic: a sum over rows goes through one partial per
 // workgroup and column in the scratch arena (wave sums by shuffles, the four waves added in order) and a one-workgroup kernel that adds the
@@ -247,6 +249,100 @@ __global__ __launch_bounds__(256) void ridge_filter_kernel(int64_t k, int64_t s,
     }
 }
 
+// ---- (f) the leave-one-out table of restricted kernel ridge regression.  With d_jm = sigma_j^2 / (sigma_j^2 + mu_m), row i has
+// the leverage s_im = sum_j U_ij^2 d_jm and the fitted value yhat_imc = sum_j U_ij d_jm C_jc; its leave-one-out residual is
+// (h_ic - yhat_imc) / (1 - s_im).  A thread owns a row of U and walks its k columns once per (grid chunk, column chunk): LOO_GC grid values
+// and LC columns, so LOO_GC (1 + LC) sums in registers, all in double.  The tables d_jm and d_jm C_jc of a slab of LOO_JS columns sit in
+// LDS, where every lane reads the same address.  One partial per workgroup and entry goes to scratch (wave sums by shuffles, the four waves
+// added in order); ridge_loo_final_kernel adds the partials in a fixed order.  A workgroup always owns LOO_ROWS rows, so the bits depend on
+// the shapes alone.
+constexpr int LOO_ROWS = 256, LOO_JS = 64, LOO_GC = 8, LOO_LC = 4;
+
+template <typename T, int LC>
+__global__ __launch_bounds__(LOO_ROWS) void ridge_loo_partial_kernel(int64_t n, int64_t k, int64_t ell, int64_t g, const T* __restrict__ U, int64_t ldu,
+                                                                     const T* __restrict__ sigma, const T* __restrict__ C, int64_t ldc,
+                                                                     const T* __restrict__ H, int64_t ldh, const T* __restrict__ mus, T rcond,
+                                                                     double* __restrict__ part) {
+    constexpr int NQ = LOO_GC * LC;
+    __shared__ double dt[LOO_JS * LOO_GC];
+    __shared__ double ct[LOO_JS * NQ];
+    __shared__ double wsum[4 * 2 * NQ];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t i = (int64_t)blockIdx.x * LOO_ROWS + tid;
+    const bool live = i < n;
+    const int64_t m0 = (int64_t)blockIdx.y * LOO_GC, c0 = (int64_t)blockIdx.z * LC;
+    const double cut = (double)rcond * (double)sigma[0];
+    double sa[LOO_GC], ya[NQ];
+#pragma unroll
+    for (int m = 0; m < LOO_GC; ++m) sa[m] = 0.0;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) ya[q] = 0.0;
+    for (int64_t j0 = 0; j0 < k; j0 += LOO_JS) {
+        const int cnt = (int)((k - j0) < LOO_JS ? (k - j0) : LOO_JS);
+        __syncthreads();                                                                     // the previous slab has been read
+        for (int t = tid; t < LOO_JS * LOO_GC; t += LOO_ROWS) {
+            const int jj = t / LOO_GC, m = t % LOO_GC;
+            double d = 0.0;
+            if (jj < cnt && m0 + m < g) {                                                    // beyond the slab or the grid: 0, which adds nothing
+                const double sg = (double)sigma[j0 + jj], mu = (double)mus[m0 + m];
+                d = mu == 0.0 ? (sg <= cut ? 0.0 : 1.0) : (sg * sg) / fma(sg, sg, mu);
+            }
+            dt[t] = d;
+#pragma unroll
+            for (int c = 0; c < LC; ++c) ct[t * LC + c] = (jj < cnt && c0 + c < ell) ? d * (double)C[(j0 + jj) + (c0 + c) * ldc] : 0.0;
+        }
+        __syncthreads();
+        const T* up = U + (live ? i : 0) + j0 * ldu;
+#pragma unroll 4
+        for (int jj = 0; jj < cnt; ++jj) {
+            const double u = live ? (double)up[(int64_t)jj * ldu] : 0.0;
+            const double u2 = u * u;
+#pragma unroll
+            for (int m = 0; m < LOO_GC; ++m) sa[m] = fma(u2, dt[jj * LOO_GC + m], sa[m]);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) ya[q] = fma(u, ct[jj * NQ + q], ya[q]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < LC; ++c) {
+        const bool col = live && c0 + c < ell;
+        const double h = col ? (double)H[i + (c0 + c) * ldh] : 0.0;
+#pragma unroll
+        for (int m = 0; m < LOO_GC; ++m) {
+            const bool on = col && m0 + m < g;
+            const double r = h - ya[m * LC + c];
+            const double e = r / (1.0 - sa[m]);                                              // 1 - s == 0: inf or NaN, reported as it is
+            const double lo = wave_sum(on ? e * e : 0.0), rs = wave_sum(on ? r * r : 0.0);
+            if (lane == 0) {
+                wsum[(wave * 2 + 0) * NQ + m * LC + c] = lo;
+                wsum[(wave * 2 + 1) * NQ + m * LC + c] = rs;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < 2 * NQ) {
+        const int which = tid / NQ, q = tid % NQ, m = q / LC, c = q % LC;
+        if (m0 + m < g && c0 + c < ell) {
+            const double v = ((wsum[which * NQ + q] + wsum[(2 + which) * NQ + q]) + wsum[(4 + which) * NQ + q]) + wsum[(6 + which) * NQ + q];
+            part[((int64_t)which * gridDim.x + blockIdx.x) * (g * ell) + (m0 + m) + (c0 + c) * g] = v;
+        }
+    }
+}
+
+// entry e of (loo | rss), each g x ell: lane l of the wave that owns it adds the partials l, l + 64, ... in order, then the 64 lanes are
+// added by shuffles
+__global__ __launch_bounds__(256) void ridge_loo_final_kernel(int64_t nblk, int64_t ge, const double* __restrict__ part, double* __restrict__ loo,
+                                                              double* __restrict__ rss) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t e = (int64_t)blockIdx.x * 4 + wave;
+    if (e >= 2 * ge) return;
+    const int64_t which = e / ge, q = e % ge;
+    double acc = 0.0;
+    for (int64_t b = lane; b < nblk; b += 64) acc += part[(which * nblk + b) * ge + q];
+    acc = wave_sum(acc);
+    if (lane == 0) (which ? rss : loo)[q] = acc;
+}
+
 inline unsigned stream_grid(rlhip_ctx* c, int64_t total) {
     const int64_t want = (total + 255) / 256, cap = (int64_t)c->num_cu * 8;
     return (unsigned)(want < 1 ? 1 : (want < cap ? want : cap));
@@ -429,6 +525,43 @@ int ridge_filter(rlhip_ctx* c, int64_t k, int64_t s, const T* sigma, const T* mu
     return 0;
 }
 
+template <typename T>
+int ridge_loo(rlhip_ctx* c, int64_t n, int64_t k, int64_t ell, int64_t g, const T* U, int64_t ldu, const T* sigma, const T* C, int64_t ldc, const T* H,
+              int64_t ldh, const T* mus, T rcond, double* loo, double* rss) {
+    if (!c) return -1;
+    if (n < 0) return -2;
+    if (k < 0) return -3;
+    if (ell < 0) return -4;
+    if (g < 0) return -5;
+    if (ldu < (n > 1 ? n : 1)) return -7;
+    if (ldc < (k > 1 ? k : 1)) return -10;
+    if (ldh < (n > 1 ? n : 1)) return -12;
+    if (n == 0 || k == 0 || ell == 0 || g == 0) return 0;
+    if (!U) return -6;
+    if (!sigma) return -8;
+    if (!C) return -9;
+    if (!H) return -11;
+    if (!mus) return -13;
+    if (!(rcond >= T(0))) return -14;
+    if (!loo) return -15;
+    if (!rss) return -16;
+    const int64_t nblk = (n + LOO_ROWS - 1) / LOO_ROWS, gchunks = (g + LOO_GC - 1) / LOO_GC;
+    const int lc = ell == 1 ? 1 : LOO_LC;
+    const int64_t cchunks = (ell + lc - 1) / lc;
+    if (nblk > 0x7fffffff || gchunks > 65535 || cchunks > 65535) return -100;
+    ws_scope ws(c);
+    double* part = ws.alloc<double>((size_t)(2 * nblk * g * ell));
+    if (!part) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
+    const dim3 grid((unsigned)nblk, (unsigned)gchunks, (unsigned)cchunks), blk(LOO_ROWS);
+    if (lc == 1)
+        hipLaunchKernelGGL((ridge_loo_partial_kernel<T, 1>), grid, blk, 0, c->stream, n, k, ell, g, U, ldu, sigma, C, ldc, H, ldh, mus, rcond, part);
+    else
+        hipLaunchKernelGGL((ridge_loo_partial_kernel<T, LOO_LC>), grid, blk, 0, c->stream, n, k, ell, g, U, ldu, sigma, C, ldc, H, ldh, mus, rcond, part);
+    hipLaunchKernelGGL(ridge_loo_final_kernel, dim3(grid1(2 * g * ell, 4)), dim3(256), 0, c->stream, nblk, g * ell, part, loo, rss);
+    RLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -457,6 +590,10 @@ int64_t rlhip_pcg_path_count(rlhip_ctx* c, int which) { return (c && which >= 43
     int rlhip_ridge_filter_##SUF(rlhip_ctx* c, int64_t k, int64_t s, const T* sigma_dev, const T* mus_dev, int64_t num_mus, T rcond, T* C,   \
                                  int64_t ldc) {                                                                                              \
         return ridge_filter<T>(c, k, s, sigma_dev, mus_dev, num_mus, rcond, C, ldc);                                                         \
+    }                                                                                                                                        \
+    int rlhip_ridge_loo_##SUF(rlhip_ctx* c, int64_t n, int64_t k, int64_t ell, int64_t g, const T* U, int64_t ldu, const T* sigma_dev,       \
+                              const T* C, int64_t ldc, const T* H, int64_t ldh, const T* mus_dev, T rcond, double* loo_dev, double* rss_dev) { \
+        return ridge_loo<T>(c, n, k, ell, g, U, ldu, sigma_dev, C, ldc, H, ldh, mus_dev, rcond, loo_dev, rss_dev);                           \
     }
 RLHIP_DEFINE_PCG(f64, double)
 RLHIP_DEFINE_PCG(f32, float)

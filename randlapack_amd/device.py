@@ -1230,6 +1230,79 @@ def krr_predict_restricted_pdk(ctx: Context, Z, mz, Xp, rows_x, n, kernel, bandw
     return Y
 
 
+# ---- the regularization path of the restricted fits: leave-one-out and residual sums for a grid of regularizations after one
+#      factorization and one SVD, and the fits that choose from the grid
+CV_LOO, CV_GCV = 0, 1
+
+
+def ridge_loo(ctx: Context, U, sigma, C_, H, mus, n, k, ell, rcond=0.0, ldu=None, ldc=None, ldh=None):
+    """(loo, rss) of rlhip_ridge_loo_*: float64 device tensors (ell, g), column-major g x ell.  U (k, ldu >= n), C_ (ell, ldc >= k) and
+    H (ell, ldh >= n) are column-major blocks, sigma (k) and mus (g) vectors, all of one dtype."""
+    torch = _torch()
+    suf, _ = _suf(U)
+    g = int(mus.numel())
+    loo = torch.full((ell, g), float("nan"), dtype=torch.float64, device=U.device)
+    rss = torch.full((ell, g), float("nan"), dtype=torch.float64, device=U.device)
+    rc = getattr(ctx.lib, f"rlhip_ridge_loo_{suf}")(ctx.h, n, k, ell, g, U.data_ptr(), _ldc(U) if ldu is None else ldu, _ptr(sigma), C_.data_ptr(),
+                                                   _ldc(C_) if ldc is None else ldc, H.data_ptr(), _ldc(H) if ldh is None else ldh, _ptr(mus), rcond,
+                                                   loo.data_ptr(), rss.data_ptr())
+    _lib.check(rc, "ridge_loo")
+    return loo, rss
+
+
+def _path_buffers(g, s):
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    bufs = dict(loo=np.full((s, g), np.nan), rss=np.full((s, g), np.nan), dof=np.full(g, np.nan), best=np.full(s, -1, dtype=np.int64),
+                best_mu=np.full(s, np.nan))
+    ptrs = [bufs[name].ctypes.data_as(ip if name == "best" else dp) for name in ("loo", "rss", "dof", "best", "best_mu")]
+    return bufs, ptrs
+
+
+def krill_restricted_rpchol_cv_pdk(ctx: Context, Xp, rows_x, n, kernel, bandwidth, mu_grid, criterion, H, s, k=-1, b=-1, ctr=(0, 0, 0, 0), key=(0, 0),
+                                   ldalpha=None):
+    """krill_restricted_rpchol_cv: the dict of krill_restricted_rpchol_pdk and the path on the host -- loo, rss (numpy (s, g): row c is
+    column c of the g x s table), dof (g), best (s indices into mu_grid), best_mu (s).  criterion: CV_LOO or CV_GCV."""
+    torch = _torch()
+    suf, T = _suf(Xp)
+    k_in = int(np.sqrt(n)) if k < 0 else k
+    lda = max(k_in, 1) if ldalpha is None else ldalpha
+    alpha = torch.full((s, lda), float("nan"), dtype=Xp.dtype, device=Xp.device)
+    S = np.full(max(k_in, 1), -1, dtype=np.int64)
+    g = len(mu_grid)
+    mg = (T * max(g, 1))(*mu_grid)
+    kk = C.c_int64(k)
+    st = _state_arr(ctr, key)
+    status = (C.c_int * 2)()
+    bufs, ptrs = _path_buffers(max(g, 1), s)
+    rc = getattr(ctx.lib, f"rlhip_drv_krill_restricted_rpchol_cv_pdk_{suf}")(ctx.h, Xp.data_ptr(), _ldc(Xp), rows_x, n, kernel, bandwidth, mg, g, criterion,
+                                                                            H.data_ptr(), _ldc(H), s, C.byref(kk), b,
+                                                                            S.ctypes.data_as(C.POINTER(C.c_int64)), alpha.data_ptr(), lda, st, status, *ptrs)
+    _drv_check(ctx, rc, "krill_restricted_rpchol_cv_pdk")
+    kf = int(kk.value)
+    return dict(bufs, alpha=alpha, S=S[:kf].copy(), S_all=S, k=kf, status=int(status[0]), c_status=int(status[1]),
+                next_ctr=tuple(int(x) for x in st[:4]))
+
+
+def krill_restricted_cv_pdk(ctx: Context, Xp, rows_x, n, kernel, bandwidth, mu_grid, criterion, H, s, S, alpha=None):
+    """krill_restricted_cv with the centres S: (info, alpha, path) with path = dict(loo, rss, dof, best, best_mu) as above; with info != 0
+    alpha and the path are as they were handed in (the path: NaN and -1)."""
+    torch = _torch()
+    suf, T = _suf(Xp)
+    S = np.ascontiguousarray(S, dtype=np.int64)
+    k = int(S.size)
+    if alpha is None:
+        alpha = torch.full((s, max(k, 1)), float("nan"), dtype=Xp.dtype, device=Xp.device)
+    g = len(mu_grid)
+    mg = (T * max(g, 1))(*mu_grid)
+    info = C.c_int64(0)
+    bufs, ptrs = _path_buffers(max(g, 1), s)
+    rc = getattr(ctx.lib, f"rlhip_drv_krill_restricted_cv_pdk_{suf}")(ctx.h, Xp.data_ptr(), _ldc(Xp), rows_x, n, kernel, bandwidth, mg, g, criterion,
+                                                                     H.data_ptr(), _ldc(H), s, k, S.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                                     alpha.data_ptr(), _ldc(alpha), C.byref(info), *ptrs)
+    _drv_check(ctx, rc, "krill_restricted_cv_pdk")
+    return int(info.value), alpha, bufs
+
+
 # ---- matrix-vector layer, pcg_saddle and the sketched least-squares preconditioners (lsq.hip; include/RandLAPACK_amd/rl_determiter.hh,
 #      rl_preconditioners.hh, rl_lstsq.hh).  A matrix is a column-major tensor (cols, ld) as everywhere in this module, a vector a 1-D tensor
 #      that may be longer than the length in use.
