@@ -45,6 +45,16 @@ struct KrillRidgePath {
     std::vector<double> best_mu;
 };
 
+/// The basis a restricted fit leaves behind for krr_predict_restricted_var, DEVICE buffers owned by the caller: G (k_in x
+/// k_in, ldg >= k_in) receives M^-T W and sigma (k_in) the singular values, where F = U diag(sigma) W^T is the thin SVD of the fit's factor
+/// and M = F(S, :).  Behind the achieved rank the rows and columns of G and the entries of sigma are zero.
+template <typename T>
+struct KrillRestrictedBasis {
+    T* G;
+    int64_t ldg;
+    T* sigma;
+};
+
 namespace _krill_impl {
 template <typename T>
 const T* regs_ptr(const T* r) { return r; }
@@ -66,6 +76,17 @@ inline int gather_cols(blas::Queue& q, int64_t m, int64_t cnt, const int64_t* id
     return rlhip_gather_cols_f32(q.ctx(), m, cnt, idx, A, lda, out, ldo);
 }
 
+inline int cross_var(blas::Queue& q, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t k, const double* Xs, int64_t ldx, int kernel,
+                     double bandwidth, const double* G, int64_t ldg, const double* sigma, int64_t s, const double* mus, int64_t num_mus, double rcond,
+                     double* V, int64_t ldv) {
+    return rlhip_pdk_cross_var_f64(q.ctx(), rows_x, mz, Z, ldz, k, Xs, ldx, kernel, bandwidth, G, ldg, sigma, s, mus, num_mus, rcond, V, ldv);
+}
+inline int cross_var(blas::Queue& q, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t k, const float* Xs, int64_t ldx, int kernel,
+                     float bandwidth, const float* G, int64_t ldg, const float* sigma, int64_t s, const float* mus, int64_t num_mus, float rcond,
+                     float* V, int64_t ldv) {
+    return rlhip_pdk_cross_var_f32(q.ctx(), rows_x, mz, Z, ldz, k, Xs, ldx, kernel, bandwidth, G, ldg, sigma, s, mus, num_mus, rcond, V, ldv);
+}
+
 inline int ridge_loo(blas::Queue& q, int64_t n, int64_t k, int64_t ell, int64_t g, const double* U, int64_t ldu, const double* sigma, const double* C,
                      int64_t ldc, const double* H, int64_t ldh, const double* mus, double rcond, double* loo, double* rss) {
     return rlhip_ridge_loo_f64(q.ctx(), n, k, ell, g, U, ldu, sigma, C, ldc, H, ldh, mus, rcond, loo, rss);
@@ -74,6 +95,16 @@ inline int ridge_loo(blas::Queue& q, int64_t n, int64_t k, int64_t ell, int64_t 
                      int64_t ldc, const float* H, int64_t ldh, const float* mus, float rcond, double* loo, double* rss) {
     return rlhip_ridge_loo_f32(q.ctx(), n, k, ell, g, U, ldu, sigma, C, ldc, H, ldh, mus, rcond, loo, rss);
 }
+
+/// rlhip_pdk_var_set_fused(on) on q's context while alive; the value found is put back
+struct VarFusedScope {
+    rlhip_ctx* ctx;
+    int found;
+    VarFusedScope(blas::Queue& q, bool on) : ctx(q.ctx()), found(rlhip_pdk_var_set_fused(q.ctx(), on ? 1 : 0)) {}
+    ~VarFusedScope() { rlhip_pdk_var_set_fused(ctx, found > 0 ? 1 : 0); }
+    VarFusedScope(VarFusedScope const&) = delete;
+    VarFusedScope& operator=(VarFusedScope const&) = delete;
+};
 
 /// set_eval_includes_reg(false) for a factorization, back to true on every way out of the scope
 template <typename FUNC>
@@ -135,26 +166,43 @@ void restricted_head(blas::Queue& q, int64_t n, int64_t k, T* F, int64_t ldf, co
     blas::gemm(Layout::ColMajor, Op::Trans, Op::NoTrans, k, ell, n, (T)1, w.U, n, H, ldh, (T)0, w.C, k, q);
 }
 
-/// the tail from the filter on, with the num_mus (1 or ell) regularizations mus_dev (DEVICE); C is overwritten
+/// the tail from the filter on, with the num_mus (1 or ell) regularizations mus_dev (DEVICE); C is overwritten.  With a basis (k_in x k_in,
+/// k_in >= k): G = Rinv VT^T = M^-T W and sigma, zero behind k -- issued after everything alpha depends on, from blocks nothing else writes.
 template <typename T>
 void restricted_finish(blas::Queue& q, int64_t n, int64_t k, int64_t ell, RestrictedWork<T> const& w, const T* mus_dev, int64_t num_mus, T* alpha,
-                       int64_t ldalpha) {
+                       int64_t ldalpha, KrillRestrictedBasis<T>* basis = nullptr, int64_t k_in = 0) {
     blas::check(ridge_filter(q, k, ell, w.sigma, mus_dev, num_mus, (T)n * std::numeric_limits<T>::epsilon(), w.C, k), "ridge_filter");
     blas::gemm(Layout::ColMajor, Op::Trans, Op::NoTrans, k, ell, k, (T)1, w.VT, k, w.C, k, (T)0, w.Y, k, q);
     util::eye(k, k, w.Rinv, q);
     blas::trsm(Layout::ColMajor, Side::Right, Uplo::Upper, Op::NoTrans, Diag::NonUnit, k, k, (T)1, w.R, k, w.Rinv, k, q);
     blas::gemm(Layout::ColMajor, Op::NoTrans, Op::NoTrans, k, ell, k, (T)1, w.Rinv, k, w.Y, k, (T)0, alpha, ldalpha, q);
+    if (basis) {
+        if (k < k_in) {
+            lapack::laset(MatrixType::General, k_in, k_in, (T)0, (T)0, basis->G, basis->ldg, q);
+            blas::device_memset(basis->sigma, 0, k_in, q);
+        }
+        blas::gemm(Layout::ColMajor, Op::NoTrans, Op::Trans, k, k, k, (T)1, w.Rinv, k, w.VT, k, (T)0, basis->G, basis->ldg, q);
+        blas::device_copy_vector(k, w.sigma, basis->sigma, q);
+    }
+}
+
+/// the basis argument of a fit, checked before anything is enqueued
+template <typename T>
+void check_basis(const KrillRestrictedBasis<T>* basis, int64_t k_in) {
+    if (!basis) return;
+    randlapack_require(basis->G != nullptr && basis->sigma != nullptr) << "basis: G and sigma must not be null";
+    randlapack_require(basis->ldg >= k_in) << "basis: ldg=" << basis->ldg << " < k=" << k_in;
 }
 
 template <typename T>
 void restricted_tail(blas::Queue& q, int64_t n, int64_t k, T* F, int64_t ldf, const int64_t* S_dev, int64_t ell, const T* H, int64_t ldh,
-                     std::vector<T> const& mus, T* alpha, int64_t ldalpha) {
+                     std::vector<T> const& mus, T* alpha, int64_t ldalpha, KrillRestrictedBasis<T>* basis = nullptr, int64_t k_in = 0) {
     blas::Scratch ws(q);
     const RestrictedWork<T> w = restricted_alloc<T>(ws, n, k, ell);
     T* mus_dev = ws.alloc<T>((int64_t)mus.size());
     blas::copy_to_device((int64_t)mus.size(), mus.data(), mus_dev, q);
     restricted_head(q, n, k, F, ldf, S_dev, ell, H, ldh, w);
-    restricted_finish(q, n, k, ell, w, mus_dev, (int64_t)mus.size(), alpha, ldalpha);
+    restricted_finish(q, n, k, ell, w, mus_dev, (int64_t)mus.size(), alpha, ldalpha, basis, k_in);
 }
 
 /// dof[m] = sum_j d_jm with the d of rlhip_ridge_loo_*: sigma_j^2 / (sigma_j^2 + mu_m); mu_m == 0: 1, or 0 where sigma_j <= rcond sigma_0
@@ -205,7 +253,8 @@ void check_mu_grid(int64_t g, const T* mu_grid, KrillCriterion criterion) {
 /// the selection on the host, then the filter with the ell chosen values and the rest of the tail as it is.
 template <typename T>
 void restricted_tail_cv(blas::Queue& q, int64_t n, int64_t k, T* F, int64_t ldf, const int64_t* S_dev, int64_t ell, const T* H, int64_t ldh, int64_t g,
-                        const T* mu_grid, KrillCriterion criterion, KrillRidgePath& path, T* alpha, int64_t ldalpha) {
+                        const T* mu_grid, KrillCriterion criterion, KrillRidgePath& path, T* alpha, int64_t ldalpha,
+                        KrillRestrictedBasis<T>* basis = nullptr, int64_t k_in = 0) {
     blas::Scratch ws(q);
     const RestrictedWork<T> w = restricted_alloc<T>(ws, n, k, ell);
     T* grid_dev = ws.alloc<T>(g);
@@ -233,7 +282,7 @@ void restricted_tail_cv(blas::Queue& q, int64_t n, int64_t k, T* F, int64_t ldf,
         path.best_mu[(size_t)c] = (double)mus[(size_t)c];
     }
     blas::copy_to_device(ell, mus.data(), mus_dev, q);
-    restricted_finish(q, n, k, ell, w, mus_dev, ell, alpha, ldalpha);
+    restricted_finish(q, n, k, ell, w, mus_dev, ell, alpha, ldalpha, basis, k_in);
 }
 
 /// what the two pairs of fits differ in: where the regularizations come from (checked by prepare()) and the tail that uses them
@@ -241,8 +290,9 @@ template <typename T, typename FUNC>
 struct FixedRidge {
     std::vector<T> mus;
     void prepare(FUNC& G, int64_t ell) { mus = restricted_mus<T>(G, ell); }
-    void tail(blas::Queue& q, int64_t n, int64_t k, T* F, const int64_t* S_dev, int64_t ell, const T* H, int64_t ldh, T* alpha, int64_t ldalpha) {
-        restricted_tail(q, n, k, F, n, S_dev, ell, H, ldh, mus, alpha, ldalpha);
+    void tail(blas::Queue& q, int64_t n, int64_t k, T* F, const int64_t* S_dev, int64_t ell, const T* H, int64_t ldh, T* alpha, int64_t ldalpha,
+              KrillRestrictedBasis<T>* basis, int64_t k_in) {
+        restricted_tail(q, n, k, F, n, S_dev, ell, H, ldh, mus, alpha, ldalpha, basis, k_in);
     }
 };
 template <typename T, typename FUNC>
@@ -252,8 +302,9 @@ struct GridRidge {
     KrillCriterion criterion;
     KrillRidgePath& path;
     void prepare(FUNC&, int64_t) { check_mu_grid(g, mu_grid, criterion); }
-    void tail(blas::Queue& q, int64_t n, int64_t k, T* F, const int64_t* S_dev, int64_t ell, const T* H, int64_t ldh, T* alpha, int64_t ldalpha) {
-        restricted_tail_cv(q, n, k, F, n, S_dev, ell, H, ldh, g, mu_grid, criterion, path, alpha, ldalpha);
+    void tail(blas::Queue& q, int64_t n, int64_t k, T* F, const int64_t* S_dev, int64_t ell, const T* H, int64_t ldh, T* alpha, int64_t ldalpha,
+              KrillRestrictedBasis<T>* basis, int64_t k_in) {
+        restricted_tail_cv(q, n, k, F, n, S_dev, ell, H, ldh, g, mu_grid, criterion, path, alpha, ldalpha, basis, k_in);
     }
 };
 }  // namespace _krill_impl
@@ -315,7 +366,7 @@ namespace _krill_impl {
 /// krill_restricted_rpchol and krill_restricted_rpchol_cv: RIDGE is FixedRidge or GridRidge
 template <typename T, typename FUNC, typename STATE, typename RIDGE>
 STATE restricted_rpchol(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t& k, int64_t* S, T* alpha, int64_t ldalpha, STATE state,
-                        int64_t rpchol_block_size, KrillRestrictedInfo* info, RIDGE& ridge) {
+                        int64_t rpchol_block_size, KrillRestrictedInfo* info, RIDGE& ridge, KrillRestrictedBasis<T>* basis) {
     randlapack_require(n > 0) << "n=" << n << " must be > 0";
     randlapack_require(ell > 0) << "ell=" << ell << " must be > 0";
     randlapack_require(H != nullptr) << "H buffer must not be null";
@@ -328,6 +379,7 @@ STATE restricted_rpchol(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh
     randlapack_require(k >= 1 && k <= n) << "k=" << k << " must be in [1, n=" << n << "]";
     randlapack_require(ldalpha >= k) << "ldalpha=" << ldalpha << " < k=" << k;
     const int64_t k_in = k;
+    check_basis(basis, k_in);
 
     blas::Queue& q = G.q;
     blas::Scratch ws(q);
@@ -348,13 +400,14 @@ STATE restricted_rpchol(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh
     std::fill(S + k, S + k_in, (int64_t)-1);
     lapack::laset(MatrixType::General, k_in, ell, (T)0, (T)0, alpha, ldalpha, q);
     blas::copy_to_device(k, S, S_dev, q);
-    ridge.tail(q, n, k, F, S_dev, ell, H, ldh, alpha, ldalpha);
+    ridge.tail(q, n, k, F, S_dev, ell, H, ldh, alpha, ldalpha, basis, k_in);
     return state;
 }
 
 /// krill_restricted and krill_restricted_cv
 template <typename T, typename FUNC, typename RIDGE>
-int64_t restricted_given(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t k, const int64_t* S, T* alpha, int64_t ldalpha, RIDGE& ridge) {
+int64_t restricted_given(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t k, const int64_t* S, T* alpha, int64_t ldalpha, RIDGE& ridge,
+                         KrillRestrictedBasis<T>* basis) {
     randlapack_require(n > 0) << "n=" << n << " must be > 0";
     randlapack_require(ell > 0) << "ell=" << ell << " must be > 0";
     randlapack_require(H != nullptr) << "H buffer must not be null";
@@ -365,6 +418,7 @@ int64_t restricted_given(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ld
     randlapack_require(ldalpha >= k) << "ldalpha=" << ldalpha << " < k=" << k;
     for (int64_t j = 0; j < k; ++j) randlapack_require(S[j] >= 0 && S[j] < n) << "S[" << j << "]=" << S[j] << " must be in [0, n=" << n << ")";
     ridge.prepare(G, ell);
+    check_basis(basis, k);
 
     blas::Queue& q = G.q;
     blas::Scratch ws(q);
@@ -381,7 +435,7 @@ int64_t restricted_given(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ld
     if (info) return info;
     util::get_U(k, k, W, k, q);
     blas::trsm(Layout::ColMajor, Side::Right, Uplo::Upper, Op::NoTrans, Diag::NonUnit, n, k, (T)1, W, k, F, n, q);
-    ridge.tail(q, n, k, F, S_dev, ell, H, ldh, alpha, ldalpha);
+    ridge.tail(q, n, k, F, S_dev, ell, H, ldh, alpha, ldalpha, basis, k);
     return 0;
 }
 }  // namespace _krill_impl
@@ -393,18 +447,20 @@ int64_t restricted_given(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ld
 /// ldh).  O(n k^2) as rp_cholesky itself; scratch: the n x k factor and one more n x k buffer for the SVD's U.  Returns the advanced state.
 template <typename T, typename FUNC, typename STATE>
 STATE krill_restricted_rpchol(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t& k, int64_t* S, T* alpha, int64_t ldalpha,
-                              STATE state, int64_t rpchol_block_size = -1, KrillRestrictedInfo* info = nullptr) {
+                              STATE state, int64_t rpchol_block_size = -1, KrillRestrictedInfo* info = nullptr,
+                              KrillRestrictedBasis<T>* basis = nullptr) {
     _krill_impl::FixedRidge<T, FUNC> ridge;
-    return _krill_impl::restricted_rpchol(n, G, ell, H, ldh, k, S, alpha, ldalpha, state, rpchol_block_size, info, ridge);
+    return _krill_impl::restricted_rpchol(n, G, ell, H, ldh, k, S, alpha, ldalpha, state, rpchol_block_size, info, ridge, basis);
 }
 
 /// The same fit with the k centres S (HOST, distinct, each in [0, n)) given: one forced-pivot block of randomly pivoted Cholesky -- A =
 /// K(:, S), potrf(Upper) of A(S, :), F = A U^-1 -- in front of the same tail.  Returns potrf's info of K(S,S): 0, or the 1-based position of
 /// the first centre that depends on the ones before it; then alpha is untouched (nothing is truncated silently).
 template <typename T, typename FUNC>
-int64_t krill_restricted(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t k, const int64_t* S, T* alpha, int64_t ldalpha) {
+int64_t krill_restricted(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t k, const int64_t* S, T* alpha, int64_t ldalpha,
+                         KrillRestrictedBasis<T>* basis = nullptr) {
     _krill_impl::FixedRidge<T, FUNC> ridge;
-    return _krill_impl::restricted_given(n, G, ell, H, ldh, k, S, alpha, ldalpha, ridge);
+    return _krill_impl::restricted_given(n, G, ell, H, ldh, k, S, alpha, ldalpha, ridge, basis);
 }
 
 /// krill_restricted_rpchol with the regularization of every column chosen from a grid: mu_grid (HOST, g >= 1 values >= 0) takes
@@ -415,17 +471,17 @@ int64_t krill_restricted(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ld
 template <typename T, typename FUNC, typename STATE>
 STATE krill_restricted_rpchol_cv(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t g, const T* mu_grid, KrillCriterion criterion,
                                  int64_t& k, int64_t* S, T* alpha, int64_t ldalpha, KrillRidgePath& path, STATE state, int64_t rpchol_block_size = -1,
-                                 KrillRestrictedInfo* info = nullptr) {
+                                 KrillRestrictedInfo* info = nullptr, KrillRestrictedBasis<T>* basis = nullptr) {
     _krill_impl::GridRidge<T, FUNC> ridge{g, mu_grid, criterion, path};
-    return _krill_impl::restricted_rpchol(n, G, ell, H, ldh, k, S, alpha, ldalpha, state, rpchol_block_size, info, ridge);
+    return _krill_impl::restricted_rpchol(n, G, ell, H, ldh, k, S, alpha, ldalpha, state, rpchol_block_size, info, ridge, basis);
 }
 
 /// krill_restricted with the regularizations chosen from mu_grid in the same way.  A non-zero return (potrf's info) leaves alpha and path untouched.
 template <typename T, typename FUNC>
 int64_t krill_restricted_cv(int64_t n, FUNC& G, int64_t ell, const T* H, int64_t ldh, int64_t g, const T* mu_grid, KrillCriterion criterion, int64_t k,
-                            const int64_t* S, T* alpha, int64_t ldalpha, KrillRidgePath& path) {
+                            const int64_t* S, T* alpha, int64_t ldalpha, KrillRidgePath& path, KrillRestrictedBasis<T>* basis = nullptr) {
     _krill_impl::GridRidge<T, FUNC> ridge{g, mu_grid, criterion, path};
-    return _krill_impl::restricted_given(n, G, ell, H, ldh, k, S, alpha, ldalpha, ridge);
+    return _krill_impl::restricted_given(n, G, ell, H, ldh, k, S, alpha, ldalpha, ridge, basis);
 }
 
 /// Prediction with the coefficients of a restricted fit: Y (mz x s, ldy) = K(Z, X(:, S)) alpha (k x s, ldalpha), with G's points, kernel
@@ -451,6 +507,45 @@ void krr_predict_restricted(linops::RBFKernelMatrix<T>& G, int64_t k, const int6
     Kzs.set_kernel(G.kernel);
     Kzs.set_split_x(G._split_x);
     krr_predict(Kzs, s, alpha, ldalpha > 0 ? ldalpha : 1, Y, ldy);
+}
+
+/// The predictive variance of a restricted fit at new points: the fit is the subset-of-regressors / DTC approximation of a
+/// Gaussian process with the kernel of G and noise mu_c, and V (DEVICE, mz x s, ldv) receives the variance of its latent function at the
+/// points Z (DEVICE, rows_x x mz, ldz) for the s regularizations mus (HOST, num_mus = 1 or s values >= 0 -- an argument, because the _cv fits
+/// choose them: path.best_mu):
+///   V(i, c) = (1 - sum_j t_ij^2) + sum_j mus_c / (sigma_j^2 + mus_c) t_ij^2,   t_i = K(Z(:, i), X(:, S)) basis.G,
+/// the Nystrom residual at the point, clamped at 0, plus the weighted part; k(z, z) = 1 for every kernel kind.  basis is what the fit on the
+/// centres S (HOST, k) left; k the achieved rank or the k_in of the fit (the basis is zero behind the rank).  mu == 0 follows the fit's
+/// pseudo-inverse with its cut-off G.dim eps.  The centre columns are gathered as krr_predict_restricted gathers them; the rest is one call
+/// of rlhip_pdk_cross_var_*.  By default that is its composed route (blocks of t in scratch); fused_kernel = true asks for its fused kernel,
+/// which keeps neither the kernel entries nor t in memory and gives every row the same bits whatever mz is, but measured slower.
+template <typename T>
+void krr_predict_restricted_var(linops::RBFKernelMatrix<T>& G, int64_t k, const int64_t* S, KrillRestrictedBasis<T> const& basis, int64_t mz,
+                                const T* Z, int64_t ldz, int64_t s, const T* mus, int64_t num_mus, T* V, int64_t ldv, bool fused_kernel = false) {
+    randlapack_require(k >= 0 && k <= 65535) << "k=" << k << " must be in [0, 65535]";
+    randlapack_require(S != nullptr || k == 0) << "S buffer must not be null";
+    randlapack_require(s >= 0) << "s=" << s << " must be >= 0";
+    randlapack_require(mus != nullptr || s == 0) << "mus buffer must not be null";
+    randlapack_require(s == 0 || num_mus == 1 || num_mus == s) << "num_mus=" << num_mus << " must equal 1 or s=" << s;
+    for (int64_t c = 0; c < (s == 0 ? 0 : num_mus); ++c) randlapack_require(mus[c] >= (T)0) << "regularization mu=" << mus[c] << " must be >= 0";
+    randlapack_require((basis.G != nullptr && basis.sigma != nullptr) || k == 0) << "basis: G and sigma must not be null";
+    randlapack_require(basis.ldg >= k || k == 0) << "basis: ldg=" << basis.ldg << " < k=" << k;
+    for (int64_t j = 0; j < k; ++j) randlapack_require(S[j] >= 0 && S[j] < G.dim) << "S[" << j << "]=" << S[j] << " must be in [0, " << G.dim << ")";
+    if (s == 0) return;
+    blas::Queue& q = G.q;
+    blas::Scratch ws(q);
+    T* Xs = ws.alloc<T>(G.rows_x * k);
+    int64_t* S_dev = ws.alloc<int64_t>(k);
+    T* mus_dev = ws.alloc<T>(num_mus);
+    if (k > 0) {
+        blas::copy_to_device(k, S, S_dev, q);
+        blas::check(_krill_impl::gather_cols(q, G.rows_x, k, S_dev, G.X, G.ldx, Xs, G.rows_x), "gather_cols");
+    }
+    blas::copy_to_device(num_mus, mus, mus_dev, q);
+    _krill_impl::VarFusedScope fused(q, fused_kernel);
+    blas::check(_krill_impl::cross_var(q, G.rows_x, mz, Z, ldz, k, Xs, G.rows_x, (int)G.kernel, G.bandwidth, basis.G, k > 0 ? basis.ldg : 1, basis.sigma,
+                                       s, mus_dev, num_mus, (T)G.dim * std::numeric_limits<T>::epsilon(), V, ldv),
+                "pdk_cross_var");
 }
 
 }  // namespace RandLAPACK

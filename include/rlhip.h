@@ -753,6 +753,49 @@ int64_t rlhip_rbf_split_chunks(int64_t mz, int64_t nx);
 /* Fused cross applies of this context that ran split over X (each counted under 55 as well); -1 for a NULL context. */
 int64_t rlhip_rbf_split_count(rlhip_ctx* ctx);
 
+/* rlhip_pdk_cross_var_*: the predictive variance of restricted kernel ridge regression as a row-wise weighted quadratic form of the cross
+ * kernel (rbf_var.hip; RandLAPACK::krr_predict_restricted_var, rl_krill.hh).  Z rows_x x mz (ldz) evaluation points, Xs
+ * rows_x x k (ldx) the centres, G k x k (ldg) and sigma_dev (k, decreasing) the basis of a restricted fit (KrillRestrictedBasis), mus_dev
+ * num_mus regularizations >= 0, all DEVICE and of type T; kernel and bandwidth as in rlhip_pdk_cross_apply_*.  With
+ *   t_i = K(Z(:, i), Xs) * G (k numbers),   e_jc = mu_c / (sigma_j^2 + mu_c),   mu_c = mus_dev[num_mus == 1 ? 0 : c],
+ *   V(i, c) = max(0, 1 - sum_j t_ij^2) + sum_j e_jc t_ij^2            (mz x s, ldv).
+ * e is formed in double as mu / fma(sigma, sigma, mu) for both precisions; mu_c == 0 is the pseudo-inverse of rlhip_ridge_filter_*: e = 0
+ * where sigma_j > rcond * sigma_0 and 1 where that singular value is cut.  The kernel entries are those of the cross apply (the same
+ * constants, the same clamp for the Matern kinds), t is accumulated in T, the squares and both sums are taken in double.  No atomics.
+ *   Fused route (opt-in: rlhip_pdk_var_set_fused(ctx, 1), and rlhip_pdk_var_fused(rows_x, k, s) != 0; it keeps no mz x k block in
+ *   memory, but measured slower than the composed route's products on the shapes of DESIGN 4.27, so no shape takes it by default): ONE
+ *   launch beside the norms and the table of e; neither K nor t reaches memory.  A workgroup owns 64 points of Z and walks the columns of G
+ *   in panels of 64, for each panel all k centres; at the end of a panel a lane squares its 16 accumulators and adds them, in the order
+ *   of j, to its sums; the four lane groups of a point are added in the order 0, 1, 2, 3.  Scratch: mz + k norms and 64 ceil(k / 64) s
+ *   doubles.  Bit contract: row i of V is a function of Z(:, i), Xs, G, sigma, mus and rcond alone -- not of mz, of the row's place in Z,
+ *   of the grid or of the device.
+ *   Composed route (the default, and every other shape): row blocks of Z sized as rlhip_pdk_cross_apply_* sizes its own (at most
+ *   max(2^26 / k, 1) points, a multiple of 256 when there are several, never more than mz); per block t (rows x k) in the scratch arena
+ *   by rlhip_pdk_cross_apply_*, then one thread per row adds the squares with j ascending.  This route has NO per-row bit contract: the
+ *   GEMMs behind the cross apply choose their kernel and their split of the contraction by the shape and the CU count, so the bits of a
+ *   row may change with mz and the device; two calls with the same arguments on the same device give the same bits.  The two routes
+ *   differ in the order of the sums.
+ * mz == 0 or s == 0: returns 0 and launches nothing.  k == 0: every entry of V is the prior variance 1.
+ * Returns 0, or -(position of the first bad argument): -2 rows_x < 1, -3 mz < 0, -5 ldz < rows_x, -6 k < 0, -8 ldx < rows_x, -9 kernel,
+ * -10 bandwidth not > 0, -12 ldg < max(k, 1), -14 s < 0, -19 ldv < max(mz, 1); then, when mz > 0 and s > 0: -100 num_mus neither 1 nor s,
+ * -17 rcond < 0 or NaN, -18 V NULL, and with k > 0: -4 Z, -7 Xs, -11 G, -13 sigma_dev, -15 mus_dev NULL.  Nothing is launched on an
+ * argument error. */
+#define RLHIP_PDK_VAR_FUSED_MAX_S 8      /* regularizations whose sums the fused kernel carries in registers */
+int rlhip_pdk_cross_var_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t k, const double* Xs, int64_t ldx,
+                            int kernel, double bandwidth, const double* G, int64_t ldg, const double* sigma_dev, int64_t s, const double* mus_dev,
+                            int64_t num_mus, double rcond, double* V, int64_t ldv);
+int rlhip_pdk_cross_var_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t k, const float* Xs, int64_t ldx,
+                            int kernel, float bandwidth, const float* G, int64_t ldg, const float* sigma_dev, int64_t s, const float* mus_dev,
+                            int64_t num_mus, float rcond, float* V, int64_t ldv);
+/* The shapes the fused kernel serves when it is asked for, a function of the shape alone: 1 where rows_x <=
+ * RLHIP_RBF_FUSED_MAX_ROWS_X, 1 <= s <= RLHIP_PDK_VAR_FUSED_MAX_S and k >= 1, else 0. */
+int rlhip_pdk_var_fused(int64_t rows_x, int64_t k, int64_t s);
+/* on != 0: rlhip_pdk_cross_var_* on this context takes its fused kernel wherever rlhip_pdk_var_fused says so; 0 (the default): always the
+ * composed route.  A switch of its own: RLHIP_OPT_RBF_FUSED steers the cross apply alone.  Returns the value found, -1 for a NULL context. */
+int rlhip_pdk_var_set_fused(rlhip_ctx* ctx, int on);
+/* The routes of rlhip_pdk_cross_var_*, one count per call that reached a route: 58 fused, 59 composed.  -1 for any other index. */
+int64_t rlhip_pdk_var_path_count(rlhip_ctx* ctx, int which);
+
 /* ---- row-block sharding across the GPUs of a node (new design; the reference has no
  *      distributed code).  One process per GPU.  Sum all-reduces run on the context's stream through RCCL
  *      (bound at run time), or through a host-installed hook.  With no communicator every call is a no-op,

@@ -345,6 +345,38 @@ int rlhip_drv_krr_predict_restricted_pdk_f64(rlhip_ctx* ctx, int64_t rows_x, int
 int rlhip_drv_krr_predict_restricted_pdk_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t n, const float* X_pts,
                                              int64_t ldx, int kernel, float bandwidth, int64_t k, const int64_t* S_host, int64_t s, const float* alpha,
                                              int64_t ldalpha, float* Y, int64_t ldy);
+/* The predictive variance of a restricted fit.  rlhip_drv_krill_restricted_rpchol_gp_pdk_* and rlhip_drv_krill_restricted_gp_pdk_*
+ * are the two fits above with three more arguments: G_out (DEVICE, k_in x k_in, ldg >= k_in) and sigma_out (DEVICE, k_in) receive the fit's
+ * basis (RandLAPACK::KrillRestrictedBasis), zero behind the achieved rank; alpha, S_host, state and status are bit for bit those of the fit
+ * without them; with *info != 0 the basis is untouched, as alpha is.
+ * rlhip_drv_krr_predict_restricted_var_pdk_*: V (DEVICE, mz x s, ldv) = the variance of the latent function at the mz points Z for the
+ * regularizations mus_host (HOST, num_mus = 1 or s values >= 0), from the k centres S_host and the basis (G_basis, ldg, sigma) of their
+ * fit: RandLAPACK::krr_predict_restricted_var, one call of rlhip_pdk_cross_var_*; fused_kernel != 0 asks for its fused kernel
+ * (rlhip_pdk_var_set_fused for the length of the call).  An unknown kind returns -9. */
+int rlhip_drv_krill_restricted_rpchol_gp_pdk_f64(rlhip_ctx* ctx, const double* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, double bandwidth,
+                                                 const double* regs_host, int64_t num_ops, const double* H, int64_t ldh, int64_t s, int64_t* k, int64_t b,
+                                                 int64_t* S_host, double* alpha, int64_t ldalpha, uint32_t state[6], int status[2], double* G_out,
+                                                 int64_t ldg, double* sigma_out);
+int rlhip_drv_krill_restricted_rpchol_gp_pdk_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, float bandwidth,
+                                                 const float* regs_host, int64_t num_ops, const float* H, int64_t ldh, int64_t s, int64_t* k, int64_t b,
+                                                 int64_t* S_host, float* alpha, int64_t ldalpha, uint32_t state[6], int status[2], float* G_out,
+                                                 int64_t ldg, float* sigma_out);
+int rlhip_drv_krill_restricted_gp_pdk_f64(rlhip_ctx* ctx, const double* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, double bandwidth,
+                                          const double* regs_host, int64_t num_ops, const double* H, int64_t ldh, int64_t s, int64_t k,
+                                          const int64_t* S_host, double* alpha, int64_t ldalpha, int64_t* info, double* G_out, int64_t ldg,
+                                          double* sigma_out);
+int rlhip_drv_krill_restricted_gp_pdk_f32(rlhip_ctx* ctx, const float* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, float bandwidth,
+                                          const float* regs_host, int64_t num_ops, const float* H, int64_t ldh, int64_t s, int64_t k,
+                                          const int64_t* S_host, float* alpha, int64_t ldalpha, int64_t* info, float* G_out, int64_t ldg,
+                                          float* sigma_out);
+int rlhip_drv_krr_predict_restricted_var_pdk_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t n, const double* X_pts,
+                                                 int64_t ldx, int kernel, double bandwidth, int64_t k, const int64_t* S_host, const double* G_basis,
+                                                 int64_t ldg, const double* sigma, int64_t s, const double* mus_host, int64_t num_mus, double* V,
+                                                 int64_t ldv, int fused_kernel);
+int rlhip_drv_krr_predict_restricted_var_pdk_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t n, const float* X_pts,
+                                                 int64_t ldx, int kernel, float bandwidth, int64_t k, const int64_t* S_host, const float* G_basis,
+                                                 int64_t ldg, const float* sigma, int64_t s, const float* mus_host, int64_t num_mus, float* V,
+                                                 int64_t ldv, int fused_kernel);
 /* posm_square (comps/rl_determiter.hh:231-282) as the C++ layer runs it: rlhip_posm_square_* and, after a failed pivot, the eigenvalue fallback on
  * the host.  LHS, RHS: s x s DEVICE, ld s.  *code = rank(LHS), -(s + 1) not positive semidefinite, -(s + 2) zero up to rounding. */
 int rlhip_drv_posm_square_f64(rlhip_ctx* ctx, int64_t s, const double* LHS, double* RHS, int diag_only, int64_t* code);

@@ -312,6 +312,21 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the regularization path
                                                               c_vp, c_i64, i64p, _dp, _dp, _dp, i64p, _dp]),
     })
 
+SIGNATURES["rlhip_pdk_var_fused"] = (c_int, [c_i64, c_i64, c_i64])      # the shape rule of the fused variance kernel
+SIGNATURES["rlhip_pdk_var_path_count"] = (c_i64, [c_vp, c_int])
+SIGNATURES["rlhip_pdk_var_set_fused"] = (c_int, [c_vp, c_int])
+for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the predictive variance of the restricted fits (rbf_var.hip, rl_krill.hh)
+    _Tp = C.POINTER(_T)
+    _fit, _given = (SIGNATURES[f"rlhip_drv_krill_restricted_{_n}pdk_{_suf}"] for _n in ("rpchol_", ""))
+    SIGNATURES.update({
+        f"rlhip_pdk_cross_var_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, _T, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, _T,
+                                                c_vp, c_i64]),
+        f"rlhip_drv_krill_restricted_rpchol_gp_pdk_{_suf}": (_fit[0], _fit[1] + [c_vp, c_i64, c_vp]),      # the fit's arguments, then G_out, ldg, sigma_out
+        f"rlhip_drv_krill_restricted_gp_pdk_{_suf}": (_given[0], _given[1] + [c_vp, c_i64, c_vp]),
+        f"rlhip_drv_krr_predict_restricted_var_pdk_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, _T, c_i64, i64p, c_vp,
+                                                                     c_i64, c_vp, c_i64, _Tp, c_i64, c_vp, c_i64, c_int]),
+    })
+
 _lib = None
 
 

@@ -900,7 +900,7 @@ int drv_krr_predict(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int6
 template <typename T>
 int drv_krill_restricted_rpchol(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth, const T* regs_host,
                                 int64_t num_ops, const T* H, int64_t ldh, int64_t s, int64_t* k, int64_t b, int64_t* S_host, T* alpha, int64_t ldalpha,
-                                uint32_t state[6], int status[2]) {
+                                uint32_t state[6], int status[2], RandLAPACK::KrillRestrictedBasis<T>* basis = nullptr) {
     if (!pdk_known(kernel)) return -6;
     return guarded([&] {
         blas::Queue q(ctx);
@@ -911,7 +911,7 @@ int drv_krill_restricted_rpchol(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int
         G.set_kernel((RandLAPACK::PDKernel)kernel);
         State st = load_state(state);
         RandLAPACK::KrillRestrictedInfo info;
-        st = RandLAPACK::krill_restricted_rpchol(n, G, s, H, ldh, *k, S_host, alpha, ldalpha, st, b, &info);
+        st = RandLAPACK::krill_restricted_rpchol(n, G, s, H, ldh, *k, S_host, alpha, ldalpha, st, b, &info, basis);
         store_state(st, state);
         status[0] = info.w_status;
         status[1] = info.c_status;
@@ -921,7 +921,7 @@ int drv_krill_restricted_rpchol(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int
 template <typename T>
 int drv_krill_restricted(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth, const T* regs_host,
                          int64_t num_ops, const T* H, int64_t ldh, int64_t s, int64_t k, const int64_t* S_host, T* alpha, int64_t ldalpha,
-                         int64_t* info) {
+                         int64_t* info, RandLAPACK::KrillRestrictedBasis<T>* basis = nullptr) {
     if (!pdk_known(kernel)) return -6;
     return guarded([&] {
         blas::Queue q(ctx);
@@ -930,7 +930,7 @@ int drv_krill_restricted(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t ro
         std::vector<T> mus(regs_host, regs_host + num_ops);
         lo::RBFKernelMatrix<T> G(n, X_pts, rows_x, bandwidth, mus, q, ldx);
         G.set_kernel((RandLAPACK::PDKernel)kernel);
-        *info = RandLAPACK::krill_restricted(n, G, s, H, ldh, k, S_host, alpha, ldalpha);
+        *info = RandLAPACK::krill_restricted(n, G, s, H, ldh, k, S_host, alpha, ldalpha, basis);
         return 0;
     });
 }
@@ -992,6 +992,21 @@ int drv_krr_predict_restricted(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const
         lo::RBFKernelMatrix<T> G(n, X_pts, rows_x, bandwidth, regs, q, ldx);
         G.set_kernel((RandLAPACK::PDKernel)kernel);
         RandLAPACK::krr_predict_restricted(G, k, S_host, mz, Z, ldz, s, alpha, ldalpha, Y, ldy);
+        return 0;
+    });
+}
+template <typename T>
+int drv_krr_predict_restricted_var(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts, int64_t ldx,
+                                   int kernel, T bandwidth, int64_t k, const int64_t* S_host, const T* G_basis, int64_t ldg, const T* sigma,
+                                   int64_t s, const T* mus_host, int64_t num_mus, T* V, int64_t ldv, int fused_kernel) {
+    if (!pdk_known(kernel)) return -9;
+    return guarded([&] {
+        blas::Queue q(ctx);
+        std::vector<T> regs{(T)0};
+        lo::RBFKernelMatrix<T> G(n, X_pts, rows_x, bandwidth, regs, q, ldx);
+        G.set_kernel((RandLAPACK::PDKernel)kernel);
+        const RandLAPACK::KrillRestrictedBasis<T> basis{const_cast<T*>(G_basis), ldg, const_cast<T*>(sigma)};
+        RandLAPACK::krr_predict_restricted_var(G, k, S_host, basis, mz, Z, ldz, s, mus_host, num_mus, V, ldv, fused_kernel != 0);
         return 0;
     });
 }
@@ -1094,6 +1109,29 @@ extern "C" {
                                                 double* rss_host, double* dof_host, int64_t* best_host, double* best_mu_host) {                   \
         return drv_krill_restricted_cv<T>(ctx, X_pts, ldx, rows_x, n, kernel, bandwidth, mu_grid_host, g, criterion, H, ldh, s, k, S_host, alpha, \
                                           ldalpha, info, loo_host, rss_host, dof_host, best_host, best_mu_host);                                  \
+    }                                                                                                                                             \
+    int rlhip_drv_krill_restricted_rpchol_gp_pdk_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel,        \
+                                                       T bandwidth, const T* regs_host, int64_t num_ops, const T* H, int64_t ldh, int64_t s,      \
+                                                       int64_t* k, int64_t b, int64_t* S_host, T* alpha, int64_t ldalpha, uint32_t state[6],      \
+                                                       int status[2], T* G_out, int64_t ldg, T* sigma_out) {                                      \
+        RandLAPACK::KrillRestrictedBasis<T> basis{G_out, ldg, sigma_out};                                                                         \
+        return drv_krill_restricted_rpchol<T>(ctx, X_pts, ldx, rows_x, n, kernel, bandwidth, regs_host, num_ops, H, ldh, s, k, b, S_host, alpha,  \
+                                              ldalpha, state, status, &basis);                                                                    \
+    }                                                                                                                                             \
+    int rlhip_drv_krill_restricted_gp_pdk_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth,  \
+                                                const T* regs_host, int64_t num_ops, const T* H, int64_t ldh, int64_t s, int64_t k,               \
+                                                const int64_t* S_host, T* alpha, int64_t ldalpha, int64_t* info, T* G_out, int64_t ldg,           \
+                                                T* sigma_out) {                                                                                   \
+        RandLAPACK::KrillRestrictedBasis<T> basis{G_out, ldg, sigma_out};                                                                         \
+        return drv_krill_restricted<T>(ctx, X_pts, ldx, rows_x, n, kernel, bandwidth, regs_host, num_ops, H, ldh, s, k, S_host, alpha, ldalpha,   \
+                                       info, &basis);                                                                                             \
+    }                                                                                                                                             \
+    int rlhip_drv_krr_predict_restricted_var_pdk_##SUF(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n,            \
+                                                       const T* X_pts, int64_t ldx, int kernel, T bandwidth, int64_t k, const int64_t* S_host,    \
+                                                       const T* G_basis, int64_t ldg, const T* sigma, int64_t s, const T* mus_host,               \
+                                                       int64_t num_mus, T* V, int64_t ldv, int fused_kernel) {                                    \
+        return drv_krr_predict_restricted_var<T>(ctx, rows_x, mz, Z, ldz, n, X_pts, ldx, kernel, bandwidth, k, S_host, G_basis, ldg, sigma, s,    \
+                                                 mus_host, num_mus, V, ldv, fused_kernel);                                                        \
     }
 RLHIP_DEFINE_PCG_DRIVERS(f64, double)
 RLHIP_DEFINE_PCG_DRIVERS(f32, float)

@@ -115,6 +115,27 @@ __device__ __forceinline__ T matern_of_s(T s, T c, T third) {
     return pdk_fma(a, pdk_fma(a, third, T(1)), T(1)) * pdk_exp(-a);
 }
 
+// ---- the fused two-point-set kernels (rbf.hip rbf_fused_kernel, rbf_var.hip pdk_var_fused_kernel): workgroup shape and the layout of
+//      the tiles they stage in LDS
+constexpr int RBF_WG = 256;
+constexpr int RBF_ZP = 64;                  // points of Z per workgroup
+constexpr int RBF_LDS_CAP = 64 * 1024;      // both buffers; no raised dynamic-LDS limit is needed below it
+
+__device__ __forceinline__ double rbf_exp(double x) { return exp(x); }
+__device__ __forceinline__ float rbf_exp(float x) { return expf(x); }
+
+// strides of the staged tiles, in elements.  X tile [point][row]: 4 KS + 1 spreads the 16 points x 4 rows of one A-operand read over
+// the banks.  B tile [column][point], as B lies in memory: the staging stores are consecutive, and the four X points drow_g(g, 0..3)
+// that a lane needs of one column are one 16-byte read in fp32 (4 g + r) and four reads 4 apart in fp64 (g + 4 r); TP + 4 keeps the 16
+// columns of one read off each other's banks.
+template <typename T, int KS> constexpr int rbf_xs() { return 4 * KS + 1; }
+constexpr int rbf_bsp(int tp) { return tp + 4; }
+template <typename T, int KS, int NT> constexpr int rbf_tile_elems(int tp) { return tp * rbf_xs<T, KS>() + 16 * NT * rbf_bsp(tp) + tp; }
+// points of X per staged tile: the largest of 64, 32, 16 whose two buffers fit RBF_LDS_CAP
+template <typename T, int KS, int NT> constexpr int rbf_tp() {
+    return 2 * rbf_tile_elems<T, KS, NT>(64) * (int)sizeof(T) <= RBF_LDS_CAP ? 64 : (2 * rbf_tile_elems<T, KS, NT>(32) * (int)sizeof(T) <= RBF_LDS_CAP ? 32 : 16);
+}
+
 // an integer as a type: the argument of a generic lambda that needs it at compile time
 template <int N> struct IntC { static constexpr int value = N; };
 

@@ -175,6 +175,9 @@ struct rlhip_ctx {
     // cross apply, [2] = 57 sqexp_cross_submatrix calls
     int64_t rbf_path_count[3] = {};
     int64_t rbf_split_count = 0;     // fused cross applies that ran split over X (RLHIP_OPT_RBF_FUSED = 2, rlhip_rbf_split_count)
+    // the routes of the kernel quadratic form (rbf_var.hip), read through rlhip_pdk_var_path_count: [0] = 58 fused, [1] = 59 composed
+    int64_t var_path_count[2] = {};
+    int var_fused = 0;               // rlhip_pdk_var_set_fused: 1 = rlhip_pdk_cross_var_* takes its fused kernel where the shape allows
 };
 
 // every host wait of the library goes through here: the epoch lets deferred read-backs know that an earlier wait already covered them

@@ -212,6 +212,24 @@ class Context:
         """fused cross applies that ran split over X (options(rbf_fused=2); include/rlhip.h rlhip_rbf_split_count)"""
         return int(self.lib.rlhip_rbf_split_count(self.h))
 
+    def var_path_count(self, which: int) -> int:
+        """routes of rlhip_pdk_cross_var_*: 58 fused, 59 composed (include/rlhip.h rlhip_pdk_var_path_count)"""
+        return int(self.lib.rlhip_pdk_var_path_count(self.h, which))
+
+    def var_fused(self, on: bool = True):
+        """context manager: rlhip_pdk_cross_var_* on this context takes its fused kernel where the shape allows (rlhip_pdk_var_set_fused);
+        the value found is put back"""
+        import contextlib
+
+        @contextlib.contextmanager
+        def _cm():
+            was = int(self.lib.rlhip_pdk_var_set_fused(self.h, int(bool(on))))
+            try:
+                yield self
+            finally:
+                self.lib.rlhip_pdk_var_set_fused(self.h, was)
+        return _cm()
+
     # ---- options (include/rlhip.h: enum rlhip_option; -1 restores the default)
     OPT = dict(cholqrq_one_stream=0, gesdd_gram=1, jacobi_persist=2, trsm_xasm=3, saso_mode=4, hqrrp_tall_panel=5,
                bqrrp_lookahead_min_elems=6, bqrrp_cholqr_fallback=7, cqrrpt_fold_pivoting=8, cqrrpt_split_qrcp=9, sparse_sketch_densify=10, jacobi_clock_holders=11,
@@ -1301,6 +1319,90 @@ def krill_restricted_cv_pdk(ctx: Context, Xp, rows_x, n, kernel, bandwidth, mu_g
                                                                      alpha.data_ptr(), _ldc(alpha), C.byref(info), *ptrs)
     _drv_check(ctx, rc, "krill_restricted_cv_pdk")
     return int(info.value), alpha, bufs
+
+
+# ---- the predictive variance of the restricted fits (rbf_var.hip, rl_krill.hh): the fits that keep their basis, and the
+#      variance at new points from it.  G (k, ldg) is a column-major k x k block, V (s, ldv) a column-major mz x s block.
+def pdk_cross_var(ctx: Context, Z, mz, Xs, rows_x, k, kernel, bandwidth, G, sigma, mus, s, rcond=0.0, V=None, ldz=None, ldx=None, ldg=None, ldv=None):
+    """V(i, c) = max(0, 1 - sum_j t_ij^2) + sum_j mus_c / (sigma_j^2 + mus_c) t_ij^2 with t = K(Z, Xs) G (rlhip_pdk_cross_var_*).  Z (mz, ldz)
+    and Xs (k, ldx) are point sets, sigma (k) and mus (1 or s) device vectors.  Returns V (s, ldv)."""
+    torch = _torch()
+    suf, _ = _suf(Z)
+    if V is None:
+        V = torch.full((max(s, 1), max(mz, 1) if ldv is None else ldv), float("nan"), dtype=Z.dtype, device=Z.device)
+    rc = getattr(ctx.lib, f"rlhip_pdk_cross_var_{suf}")(ctx.h, rows_x, mz, _ptr(Z), (_ldc(Z) if Z is not None else rows_x) if ldz is None else ldz, k, _ptr(Xs),
+                                                       (_ldc(Xs) if Xs is not None else rows_x) if ldx is None else ldx, kernel, bandwidth, _ptr(G),
+                                                       (max(_ldc(G), 1) if G is not None else max(k, 1)) if ldg is None else ldg, _ptr(sigma), s,
+                                                       _ptr(mus), int(mus.numel()) if mus is not None else 1, rcond, V.data_ptr(),
+                                                       _ldc(V) if ldv is None else ldv)
+    _lib.check(rc, "pdk_cross_var")
+    return V
+
+
+def _basis_buffers(torch, k_in, like, ldg):
+    ldg = max(k_in, 1) if ldg is None else ldg
+    G = torch.full((max(k_in, 1), ldg), float("nan"), dtype=like.dtype, device=like.device)
+    sigma = torch.full((max(k_in, 1),), float("nan"), dtype=like.dtype, device=like.device)
+    return G, sigma, ldg
+
+
+def krill_restricted_rpchol_gp_pdk(ctx: Context, Xp, rows_x, n, kernel, bandwidth, regs, H, s, k=-1, b=-1, ctr=(0, 0, 0, 0), key=(0, 0), ldalpha=None,
+                                   ldg=None):
+    """krill_restricted_rpchol_pdk that keeps the fit's basis: the same dict and G (k_in, ldg), sigma (k_in) on the device, zero behind the
+    achieved rank"""
+    torch = _torch()
+    suf, T = _suf(Xp)
+    k_in = int(np.sqrt(n)) if k < 0 else k
+    lda = max(k_in, 1) if ldalpha is None else ldalpha
+    alpha = torch.full((s, lda), float("nan"), dtype=Xp.dtype, device=Xp.device)
+    G, sigma, ldg = _basis_buffers(torch, k_in, Xp, ldg)
+    S = np.full(max(k_in, 1), -1, dtype=np.int64)
+    rg = (T * len(regs))(*regs)
+    kk = C.c_int64(k)
+    st = _state_arr(ctr, key)
+    status = (C.c_int * 2)()
+    rc = getattr(ctx.lib, f"rlhip_drv_krill_restricted_rpchol_gp_pdk_{suf}")(ctx.h, Xp.data_ptr(), _ldc(Xp), rows_x, n, kernel, bandwidth, rg, len(regs),
+                                                                            H.data_ptr(), _ldc(H), s, C.byref(kk), b,
+                                                                            S.ctypes.data_as(C.POINTER(C.c_int64)), alpha.data_ptr(), lda, st, status,
+                                                                            G.data_ptr(), ldg, sigma.data_ptr())
+    _drv_check(ctx, rc, "krill_restricted_rpchol_gp_pdk")
+    kf = int(kk.value)
+    return dict(alpha=alpha, S=S[:kf].copy(), S_all=S, k=kf, status=int(status[0]), c_status=int(status[1]), next_ctr=tuple(int(x) for x in st[:4]),
+                G=G, sigma=sigma)
+
+
+def krill_restricted_gp_pdk(ctx: Context, Xp, rows_x, n, kernel, bandwidth, regs, H, s, S, alpha=None):
+    """krill_restricted_pdk that keeps the fit's basis: (info, alpha, G (k, k), sigma (k)); with info != 0 all three are as handed in (NaN)"""
+    torch = _torch()
+    suf, T = _suf(Xp)
+    S = np.ascontiguousarray(S, dtype=np.int64)
+    k = int(S.size)
+    if alpha is None:
+        alpha = torch.full((s, max(k, 1)), float("nan"), dtype=Xp.dtype, device=Xp.device)
+    G, sigma, ldg = _basis_buffers(torch, k, Xp, None)
+    rg = (T * len(regs))(*regs)
+    info = C.c_int64(0)
+    rc = getattr(ctx.lib, f"rlhip_drv_krill_restricted_gp_pdk_{suf}")(ctx.h, Xp.data_ptr(), _ldc(Xp), rows_x, n, kernel, bandwidth, rg, len(regs),
+                                                                     H.data_ptr(), _ldc(H), s, k, S.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                                     alpha.data_ptr(), _ldc(alpha), C.byref(info), G.data_ptr(), ldg, sigma.data_ptr())
+    _drv_check(ctx, rc, "krill_restricted_gp_pdk")
+    return int(info.value), alpha, G, sigma
+
+
+def krr_predict_restricted_var_pdk(ctx: Context, Z, mz, Xp, rows_x, n, kernel, bandwidth, S, G, sigma, mus, s, fused_kernel=False):
+    """krr_predict_restricted_var: V (mz x s), column-major (s, mz), for the k = len(S) centres, their fit's basis (G, sigma) and the
+    regularizations mus (a host sequence of 1 or s values); fused_kernel: ask for the fused kernel of rlhip_pdk_cross_var_*"""
+    torch = _torch()
+    suf, T = _suf(Xp)
+    S = np.ascontiguousarray(S, dtype=np.int64)
+    V = torch.full((max(s, 1), max(mz, 1)), float("nan"), dtype=Xp.dtype, device=Xp.device)
+    mh = (T * max(len(mus), 1))(*mus)
+    rc = getattr(ctx.lib, f"rlhip_drv_krr_predict_restricted_var_pdk_{suf}")(ctx.h, rows_x, mz, Z.data_ptr(), _ld(Z), n, Xp.data_ptr(), _ld(Xp), kernel,
+                                                                            bandwidth, int(S.size), S.ctypes.data_as(C.POINTER(C.c_int64)), G.data_ptr(),
+                                                                            max(_ldc(G), 1), sigma.data_ptr(), s, mh, len(mus), V.data_ptr(), max(mz, 1),
+                                                                            int(bool(fused_kernel)))
+    _drv_check(ctx, rc, "krr_predict_restricted_var_pdk")
+    return V
 
 
 # ---- matrix-vector layer, pcg_saddle and the sketched least-squares preconditioners (lsq.hip; include/RandLAPACK_amd/rl_determiter.hh,
