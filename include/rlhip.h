@@ -850,6 +850,13 @@ int rlhip_allreduce_sum_host_f64(rlhip_ctx* ctx, double* x_host, int64_t n);   /
  * counting sort over chunks.
  * -1 for an unknown index.  Tests use it to assert that the kernel / route under test is the one that ran. */
 int64_t rlhip_path_count(rlhip_ctx* ctx, int which);
+/* The routes of the LU layer (lu.hip), counted on the host where the launch is enqueued; they continue the numbering above but are read
+ * here (7, the column-at-a-time panel, stays with rlhip_path_count).  A panel of rlhip_getrf_* / rlhip_getrf_piv_* factored by 60 the LDS
+ * kernel (getrf_panel_kernel, fewer than 1024 rows on and below the diagonal), 61 the fast step of the type (at most 64 workgroups),
+ * 62 the general register kernel (getrf_panel_reg_kernel); 63 a getrf call that ran with an outer block wider than a panel (two-level
+ * blocking, m >= 49152 and n >= 256); 64 a launch of unit_lower_solve_kernel (the forward substitution right of such an outer block);
+ * rlhip_luqrcp_piv served by 65 the LDS walk (min(sd, cols) <= 2048) or 66 the serial kernel.  -1 for any other index. */
+int64_t rlhip_lu_path_count(rlhip_ctx* ctx, int which);
 /* the host layers above this ABI (include/RandLAPACK_amd/) report their own route decisions into the same counters */
 int rlhip_path_note(rlhip_ctx* ctx, int which, int64_t delta);
 /* Profiler phase markers (the reference brackets every phase of BQRRP_GPU with NVTX ranges, drivers/rl_bqrrp_gpu.hh:11,335-403; these are the

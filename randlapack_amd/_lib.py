@@ -327,6 +327,8 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the predictive variance
                                                                      c_i64, c_vp, c_i64, _Tp, c_i64, c_vp, c_i64, c_int]),
     })
 
+SIGNATURES["rlhip_lu_path_count"] = (c_i64, [c_vp, c_int])      # the routes of getrf / luqrcp_piv, 60 .. 66 (lu.hip)
+
 _lib = None
 
 

@@ -606,10 +606,12 @@ int getrf_panel(rlhip_ctx* c, ws_scope& ws, LuArgs<T> g, int64_t rows, int64_t r
         g.tag_base = (unsigned)(g.j0 / PB + 1) * 64u;
         if (G_reg <= 64) launch_getrf_panel_fast(g, (unsigned)G_reg, c->stream);
         else hipLaunchKernelGGL((getrf_panel_reg_kernel<T, RPT>), dim3((unsigned)G_reg), dim3(256), 0, c->stream, g);
+        c->lu_path_count[G_reg <= 64 ? 1 : 2]++;
     } else {
         // short panels (< 1024 rows, at most 4 workgroups): the LDS-resident kernel
         const int64_t G = (rows + g.rpw - 1) / g.rpw;
         hipLaunchKernelGGL(getrf_panel_kernel<T>, dim3((unsigned)G), dim3(256), (size_t)g.pb * g.rpw * sizeof(T), c->stream, g);
+        c->lu_path_count[0]++;
     }
     RLHIP_LAUNCH_CHECK();
     return 0;
@@ -664,6 +666,7 @@ int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_d
     // default: with the faster fp32 panel step the HBM-bound K = 32 updates of a very tall matrix are worth saving again -- 65536 x 2048
     // fp32: 32.1 ms (outer = panel), 27.0 (64), 25.0 (128), 25.1 (256); 32768 rows: 20.7 / 20.4 / 20.5 / 21.5; 8192 rows: 16.4 / 17.1 / 17.9
     const int64_t nbo = (m >= 49152 && n >= 256) ? 128 : PB;
+    if (nbo > PB) c->lu_path_count[3]++;
     // resident capacity of the general register kernel
     static int64_t reg_cap[64] = {};
     if (!reg_cap[c->device & 63]) {
@@ -723,6 +726,7 @@ int getrf(rlhip_ctx* c, int64_t m, int64_t n, T* A, int64_t lda, int64_t* ipiv_d
             for (int64_t s0 = J0; s0 < Jend && !one_panel; s0 += PB) {
                 const int sb = (int)((Jend - s0 < PB) ? (Jend - s0) : PB);
                 hipLaunchKernelGGL(unit_lower_solve_kernel<T>, dim3(gs), dim3(256), 0, c->stream, Cin, n, s0, sb, A, lda);
+                c->lu_path_count[4]++;
                 RLHIP_LAUNCH_CHECK();
                 const int64_t below = Jend - (s0 + sb);
                 if (below > 0) {
@@ -779,8 +783,12 @@ int luqrcp_piv(rlhip_ctx* c, int64_t sd, int64_t cols, const int64_t* ipiv_dev, 
     if (lim <= LQ_MAX && cols < ((int64_t)1 << 31)) {
         hipLaunchKernelGGL(luqrcp_iota_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, c->stream, cols, J_dev);
         hipLaunchKernelGGL(luqrcp_piv_lds_kernel, dim3(1), dim3(256), 0, c->stream, sd, cols, ipiv_dev, J_dev);
+        c->lu_path_count[5]++;
     }
-    else hipLaunchKernelGGL(luqrcp_piv_kernel, dim3(1), dim3(256), 0, c->stream, sd, cols, ipiv_dev, J_dev);
+    else {
+        hipLaunchKernelGGL(luqrcp_piv_kernel, dim3(1), dim3(256), 0, c->stream, sd, cols, ipiv_dev, J_dev);
+        c->lu_path_count[6]++;
+    }
     RLHIP_LAUNCH_CHECK();
     return 0;
 }

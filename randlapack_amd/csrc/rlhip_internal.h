@@ -177,6 +177,10 @@ struct rlhip_ctx {
     int64_t rbf_split_count = 0;     // fused cross applies that ran split over X (RLHIP_OPT_RBF_FUSED = 2, rlhip_rbf_split_count)
     // the routes of the kernel quadratic form (rbf_var.hip), read through rlhip_pdk_var_path_count: [0] = 58 fused, [1] = 59 composed
     int64_t var_path_count[2] = {};
+    // the routes of the LU layer (lu.hip), read through rlhip_lu_path_count: [0] = 60 a panel on the LDS kernel, [1] = 61 on the fast step,
+    // [2] = 62 on the general register kernel, [3] = 63 getrf calls with an outer block wider than a panel, [4] = 64 launches of
+    // unit_lower_solve_kernel, [5] = 65 luqrcp_piv on the LDS walk, [6] = 66 on the serial kernel
+    int64_t lu_path_count[7] = {};
     int var_fused = 0;               // rlhip_pdk_var_set_fused: 1 = rlhip_pdk_cross_var_* takes its fused kernel where the shape allows
 };
 

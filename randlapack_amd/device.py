@@ -216,6 +216,12 @@ class Context:
         """routes of rlhip_pdk_cross_var_*: 58 fused, 59 composed (include/rlhip.h rlhip_pdk_var_path_count)"""
         return int(self.lib.rlhip_pdk_var_path_count(self.h, which))
 
+    def lu_path_count(self, which: int) -> int:
+        """routes of the LU layer: a panel on 60 the LDS kernel, 61 the fast step, 62 the general register kernel; 63 getrf calls with an
+        outer block wider than a panel, 64 unit_lower_solve_kernel launches; luqrcp_piv on 65 the LDS walk, 66 the serial kernel
+        (include/rlhip.h rlhip_lu_path_count)"""
+        return int(self.lib.rlhip_lu_path_count(self.h, which))
+
     def var_fused(self, on: bool = True):
         """context manager: rlhip_pdk_cross_var_* on this context takes its fused kernel where the shape allows (rlhip_pdk_var_set_fused);
         the value found is put back"""
