@@ -857,6 +857,13 @@ int64_t rlhip_path_count(rlhip_ctx* ctx, int which);
  * blocking, m >= 49152 and n >= 256); 64 a launch of unit_lower_solve_kernel (the forward substitution right of such an outer block);
  * rlhip_luqrcp_piv served by 65 the LDS walk (min(sd, cols) <= 2048) or 66 the serial kernel.  -1 for any other index. */
 int64_t rlhip_lu_path_count(rlhip_ctx* ctx, int which);
+/* The routes of the triangular layer (tri.hip) that 2, 3, 4 and 11 above do not tell apart, counted on the host where the launch is enqueued,
+ * one per launch: a 256-column block of rlhip_trsm_* solved by 67 the per-block MFMA kernel with one row tile per wavefront
+ * (trsm_blk_kernel<T, 1>) or 68 with two (m >= 65536); 69 a fused launch that took the twelve-wavefront instantiation (fp32 in place, beside 2);
+ * 70 a fused out-of-place solve that ran on the identity-column twin (no pivot vector; beside 4, only when the solve succeeded); 71 a
+ * rlhip_trsm_gather_* call served by the column gather + the in-place solver; 72 a rlhip_trmm_* call with side Right, 73 with side Left.
+ * -1 for any other index. */
+int64_t rlhip_tri_path_count(rlhip_ctx* ctx, int which);
 /* the host layers above this ABI (include/RandLAPACK_amd/) report their own route decisions into the same counters */
 int rlhip_path_note(rlhip_ctx* ctx, int which, int64_t delta);
 /* Profiler phase markers (the reference brackets every phase of BQRRP_GPU with NVTX ranges, drivers/rl_bqrrp_gpu.hh:11,335-403; these are the

@@ -328,6 +328,7 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the predictive variance
     })
 
 SIGNATURES["rlhip_lu_path_count"] = (c_i64, [c_vp, c_int])      # the routes of getrf / luqrcp_piv, 60 .. 66 (lu.hip)
+SIGNATURES["rlhip_tri_path_count"] = (c_i64, [c_vp, c_int])     # the routes of trsm / trsm_gather / trmm, 67 .. 73 (tri.hip)
 
 _lib = None
 

@@ -758,6 +758,7 @@ extern "C" int64_t rlhip_path_count(rlhip_ctx* c, int which) {
     return (c && which >= 0 && which < RLHIP_NPATH) ? c->path_count[which] : -1;
 }
 extern "C" int64_t rlhip_lu_path_count(rlhip_ctx* c, int which) { return (c && which >= 60 && which <= 66) ? c->lu_path_count[which - 60] : -1; }
+extern "C" int64_t rlhip_tri_path_count(rlhip_ctx* c, int which) { return (c && which >= 67 && which <= 73) ? c->tri_path_count[which - 67] : -1; }
 extern "C" int rlhip_path_note(rlhip_ctx* c, int which, int64_t delta) {
     if (!c || which < 0 || which >= RLHIP_NPATH) return -1;
     c->path_count[which] += delta;

@@ -181,6 +181,11 @@ struct rlhip_ctx {
     // [2] = 62 on the general register kernel, [3] = 63 getrf calls with an outer block wider than a panel, [4] = 64 launches of
     // unit_lower_solve_kernel, [5] = 65 luqrcp_piv on the LDS walk, [6] = 66 on the serial kernel
     int64_t lu_path_count[7] = {};
+    // the routes of the triangular layer (tri.hip) that path_count 2, 3, 4 and 11 do not tell apart, read through rlhip_tri_path_count:
+    // [0] = 67 a 256-block on trsm_blk_kernel<T, 1>, [1] = 68 on trsm_blk_kernel<T, 2>, [2] = 69 a fused launch of the twelve-wavefront
+    // instantiation, [3] = 70 a fused out-of-place solve on the identity twin (OOP = 2), [4] = 71 a trsm_gather call served by gather-copy +
+    // the in-place solver, [5] = 72 trmm_right_upper calls, [6] = 73 trmm_left_upper calls
+    int64_t tri_path_count[7] = {};
     int var_fused = 0;               // rlhip_pdk_var_set_fused: 1 = rlhip_pdk_cross_var_* takes its fused kernel where the shape allows
 };
 

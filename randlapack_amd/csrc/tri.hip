@@ -787,7 +787,11 @@ int tf_launch(rlhip_ctx* c, const TfArgs<T>& a) {
     if constexpr (sizeof(T) == 4 && OOP == 0) {
         const int64_t ncu = c->num_cu > 0 ? c->num_cu : 256;
         auto cost = [&](int64_t nw) { const int64_t wg = (a.m + 16 * nw - 1) / (16 * nw); return ((wg + ncu - 1) / ncu) * nw; };
-        if (cost(12) < cost(8)) return xasm ? tf_launch_one<T, 12, OOP, true>(c, a) : tf_launch_one<T, 12, OOP, false>(c, a);
+        if (cost(12) < cost(8)) {
+            const int rc = xasm ? tf_launch_one<T, 12, OOP, true>(c, a) : tf_launch_one<T, 12, OOP, false>(c, a);
+            if (!rc) c->tri_path_count[2]++;
+            return rc;
+        }
     }
     return xasm ? tf_launch_one<T, 8, OOP, true>(c, a) : tf_launch_one<T, 8, OOP, false>(c, a);
 }
@@ -903,6 +907,7 @@ int trsm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
             else
                 hipLaunchKernelGGL((trsm_blk_kernel<T, 1>), dim3((unsigned)((m + 63) / 64)), dim3(256), 0, c->stream, m, nb, a, Upk_b, Dinv_b, B + j0 * ldb, ldb, 0, 0);
             RLHIP_LAUNCH_CHECK();
+            c->tri_path_count[m >= 65536 ? 1 : 0]++;
             continue;
         }
         for (int s0 = 0; s0 < nb; s0 += SB) {
@@ -957,12 +962,13 @@ static int trsm_oop_fused(rlhip_ctx* c, int diag, int64_t m, int64_t nsrc, T alp
     RLHIP_CHECK(hipMemcpyAsync(c->h_mail + MAIL_TRSM_VERDICT, bad_dev, TF_VERDICT_WORDS * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     RLHIP_CHECK(hipEventRecord(c->ev_flag, c->stream));
     RLHIP_CHECK(tf_enqueue_neg_pack<T>(c, n, n, A, lda, Uneg));
+    bool ident = false;
     {
         TfArgs<T> a{m, n, n, alpha, Uneg, Dinv_all, B, ldb, (int)(col0 / BW), (int)nblk, 0, fdump};
         a.Bsrc = Bsrc; a.ldsrc = ldsrc;
         a.perm = perm_dev; a.pbase = 1;
         a.gate = bad_dev; a.ngate = TF_VERDICT_WORDS;
-        const bool ident = may_ident && !perm_dev && tf_offsets_fit(ldsrc, m);
+        ident = may_ident && !perm_dev && tf_offsets_fit(ldsrc, m);
         const int lrc = ident ? tf_launch<T, 2>(c, a) : tf_launch<T, 1>(c, a);
         if (lrc) return lrc;
     }
@@ -971,6 +977,7 @@ static int trsm_oop_fused(rlhip_ctx* c, int diag, int64_t m, int64_t nsrc, T alp
     for (int64_t b = 0; b < nblk; ++b)
         if (verdict[b] != 0) return 1;                          // the gated launch did nothing
     c->path_count[4]++;
+    if (ident) c->tri_path_count[3]++;
     return 0;
 }
 
@@ -1007,6 +1014,7 @@ int trsm_right_upper_oop(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, 
         if (gx < 1) gx = 1;
         hipLaunchKernelGGL(gather_cols_kernel<T>, dim3(gx, (unsigned)n), dim3(256), 0, c->stream, m, n, Bsrc, ldsrc, perm_dev, (int64_t)1, B, ldb);
         RLHIP_LAUNCH_CHECK();
+        c->tri_path_count[4]++;
     }
     return trsm_right_upper<T>(c, diag, m, n, alpha, A, lda, B, ldb);
 }
@@ -1051,6 +1059,7 @@ int trmm_right_upper(rlhip_ctx* c, int diag, int64_t m, int64_t n, T alpha, cons
     RLHIP_LAUNCH_CHECK();
     int rc = lacpy<T>(c, 2, m, n, B, ldb, Bc, m);
     if (!rc) rc = gemm_impl<T>(c, 0, 0, m, n, n, alpha, Bc, m, W, n, T(0), B, ldb, 0);
+    if (!rc) c->tri_path_count[5]++;
     return rc;
 }
 
@@ -1071,6 +1080,7 @@ int trmm_left_upper(rlhip_ctx* c, int trans, int diag, int64_t m, int64_t n, T a
     RLHIP_LAUNCH_CHECK();
     int rc = lacpy<T>(c, 2, m, n, B, ldb, Bc, m);
     if (!rc) rc = gemm_impl<T>(c, trans ? 1 : 0, 0, m, n, m, alpha, W, m, Bc, m, T(0), B, ldb, 0);
+    if (!rc) c->tri_path_count[6]++;
     return rc;
 }
 template int trmm_left_upper<double>(rlhip_ctx*, int, int, int64_t, int64_t, double, const double*, int64_t, double*, int64_t);

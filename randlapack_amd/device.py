@@ -222,6 +222,12 @@ class Context:
         (include/rlhip.h rlhip_lu_path_count)"""
         return int(self.lib.rlhip_lu_path_count(self.h, which))
 
+    def tri_path_count(self, which: int) -> int:
+        """routes of the triangular layer: a 256-block of trsm on 67 the per-block MFMA kernel, 68 its two-row-tile form; 69 a fused launch
+        with twelve wavefronts; 70 a fused out-of-place solve on the identity twin; 71 trsm_gather by gather-copy + the in-place solver;
+        72 trmm side Right, 73 side Left (include/rlhip.h rlhip_tri_path_count)"""
+        return int(self.lib.rlhip_tri_path_count(self.h, which))
+
     def var_fused(self, on: bool = True):
         """context manager: rlhip_pdk_cross_var_* on this context takes its fused kernel where the shape allows (rlhip_pdk_var_set_fused);
         the value found is put back"""
