@@ -358,6 +358,18 @@ void krr_predict(linops::RBFCrossKernel<T>& Kzx, int64_t s, const T* coeffs, int
     Kzx(blas::Layout::ColMajor, blas::Op::NoTrans, s, (T)1, coeffs, ldcoef, (T)0, Y, ldy);
 }
 
+/// The gradients of krr_predict's fitted functions with respect to the evaluation point: G (rows_x x (mz s), ldg >= rows_x),
+/// column c * mz + i = the gradient at Z(:, i) of the fitted function of the c-th regularization, laid out like Z.  One call of
+/// RBFCrossKernel::grad: no kernel matrix is formed, and the gradient is exact and smooth at coincident points for every kernel kind.
+/// All arrays on the DEVICE.
+template <typename T>
+void krr_predict_grad(linops::RBFCrossKernel<T>& Kzx, int64_t s, const T* coeffs, int64_t ldcoef, T* G, int64_t ldg) {
+    randlapack_require(s >= 0) << "s=" << s << " must be >= 0";
+    randlapack_require(coeffs != nullptr || s == 0 || Kzx.n_cols == 0) << "coeffs buffer must not be null";
+    randlapack_require(G != nullptr || s == 0 || Kzx.n_rows == 0) << "G buffer must not be null";
+    Kzx.grad(s, (T)1, coeffs, ldcoef, G, ldg);
+}
+
 /// what the factorization inside krill_restricted_rpchol reported, as rlhip_drv_rpchol_* report it: the sampler's status after the last
 /// block (0; 1: the residual diagonal is exhausted; 2: it has a negative or NaN entry) and potrf's info of the block that broke down
 struct KrillRestrictedInfo { int w_status = 0, c_status = 0; };
@@ -507,6 +519,29 @@ void krr_predict_restricted(linops::RBFKernelMatrix<T>& G, int64_t k, const int6
     Kzs.set_kernel(G.kernel);
     Kzs.set_split_x(G._split_x);
     krr_predict(Kzs, s, alpha, ldalpha > 0 ? ldalpha : 1, Y, ldy);
+}
+
+/// The gradients of a restricted fit's functions with respect to the evaluation point: Grad (rows_x x (mz s), ldgrad >=
+/// rows_x), laid out as krr_predict_grad lays it out.  The centres are gathered as krr_predict_restricted gathers them; the arguments are
+/// its arguments and are checked as it checks them.
+template <typename T>
+void krr_predict_restricted_grad(linops::RBFKernelMatrix<T>& G, int64_t k, const int64_t* S, int64_t mz, const T* Z, int64_t ldz, int64_t s,
+                                 const T* alpha, int64_t ldalpha, T* Grad, int64_t ldgrad) {
+    randlapack_require(k >= 0 && k <= 65535) << "k=" << k << " must be in [0, 65535]";
+    randlapack_require(S != nullptr || k == 0) << "S buffer must not be null";
+    randlapack_require(ldalpha >= k) << "ldalpha=" << ldalpha << " < k=" << k;
+    for (int64_t j = 0; j < k; ++j) randlapack_require(S[j] >= 0 && S[j] < G.dim) << "S[" << j << "]=" << S[j] << " must be in [0, " << G.dim << ")";
+    blas::Queue& q = G.q;
+    blas::Scratch ws(q);
+    T* Xs = ws.alloc<T>(G.rows_x * k);
+    int64_t* S_dev = ws.alloc<int64_t>(k);
+    if (k > 0) {
+        blas::copy_to_device(k, S, S_dev, q);
+        blas::check(_krill_impl::gather_cols(q, G.rows_x, k, S_dev, G.X, G.ldx, Xs, G.rows_x), "gather_cols");
+    }
+    linops::RBFCrossKernel<T> Kzs(G.rows_x, mz, Z, k, Xs, G.bandwidth, q, ldz, G.rows_x);
+    Kzs.set_kernel(G.kernel);
+    krr_predict_grad(Kzs, s, alpha, ldalpha > 0 ? ldalpha : 1, Grad, ldgrad);
 }
 
 /// The predictive variance of a restricted fit at new points: the fit is the subset-of-regressors / DTC approximation of a

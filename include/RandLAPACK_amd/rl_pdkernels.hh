@@ -9,7 +9,7 @@
 //   - the host functor operator()(i, j) cannot run on the device: rp_cholesky reads the operator through diag() and columns() instead,
 //     which evaluate the same entries by differences (rlhip_sqexp_columns_*), so the diagonal is exactly 1 (+ reg).
 // Extensions (the reference has neither):
-//   linops::RBFCrossKernel         the rectangular kernel K(Z, X) between two DEVICE point sets: operator(), matvec, submatrix
+//   linops::RBFCrossKernel         the rectangular kernel K(Z, X) between two DEVICE point sets: operator(), matvec, submatrix, grad
 //                                  (rlhip_rbf_cross_apply_*, rlhip_sqexp_cross_submatrix_*) -- what KRR prediction multiplies by;
 //   RBFKernelMatrix::set_matrix_free(true): operator() through the same kernels with Z = X (K never in memory); off by default.
 // Extension: set_split_x(true) on either operator runs its cross apply with the fused kernel split over X; off by default.
@@ -71,6 +71,14 @@ inline int cross_apply(blas::Queue& q, int64_t rx, int64_t mz, const float* Z, i
                        float h, int64_t n, float a, const float* B, int64_t ldb, float b, float* C, int64_t ldc) {
     return kf == PDKernel::SquaredExp ? rlhip_rbf_cross_apply_f32(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, h, n, a, B, ldb, b, C, ldc)
                                       : rlhip_pdk_cross_apply_f32(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, (int)kf, h, n, a, B, ldb, b, C, ldc);
+}
+inline int cross_grad(blas::Queue& q, int64_t rx, int64_t mz, const double* Z, int64_t ldz, int64_t nx, const double* X, int64_t ldx, PDKernel kf,
+                      double h, int64_t n, double a, const double* B, int64_t ldb, double* G, int64_t ldg) {
+    return rlhip_pdk_cross_grad_f64(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, (int)kf, h, n, a, B, ldb, G, ldg);
+}
+inline int cross_grad(blas::Queue& q, int64_t rx, int64_t mz, const float* Z, int64_t ldz, int64_t nx, const float* X, int64_t ldx, PDKernel kf,
+                      float h, int64_t n, float a, const float* B, int64_t ldb, float* G, int64_t ldg) {
+    return rlhip_pdk_cross_grad_f32(q.ctx(), rx, mz, Z, ldz, nx, X, ldx, (int)kf, h, n, a, B, ldb, G, ldg);
 }
 /// while alive and `on`: RLHIP_OPT_RBF_FUSED = 2 (the fused cross apply split over X) on q's context; the value found is put back
 struct split_x_scope {
@@ -249,6 +257,15 @@ struct RBFCrossKernel {
         blas::check(tr ? _pdk_impl::cross_apply(q, rows_x, n_cols, X, ldx, n_rows, Z, ldz, kernel, bandwidth, n, alpha, B, ldb1, beta, C, ldc1)
                        : _pdk_impl::cross_apply(q, rows_x, n_rows, Z, ldz, n_cols, X, ldx, kernel, bandwidth, n, alpha, B, ldb1, beta, C, ldc1),
                     "RBFCrossKernel");
+    }
+
+    /// G (rows_x x (mz n), ldg >= rows_x; DEVICE) = the gradients with respect to the points of Z of alpha * K(Z, X) * B, B nx x n: column
+    /// r * mz + i is the gradient at Z(:, i) of right-hand side r, laid out like Z (rlhip_pdk_cross_grad_*).  G is not read.
+    void grad(int64_t n, T alpha, const T* B, int64_t ldb, T* G, int64_t ldg) {
+        randlapack_require(ldb >= n_cols) << "ldb=" << ldb << " < " << n_cols << " (ldb must be >= the columns of K)";
+        randlapack_require(ldg >= rows_x) << "ldg=" << ldg << " < rows_x=" << rows_x;
+        blas::check(_pdk_impl::cross_grad(q, rows_x, n_rows, Z, ldz, n_cols, X, ldx, kernel, bandwidth, n, alpha, B, ldb > 0 ? ldb : 1, G, ldg),
+                    "RBFCrossKernel::grad");
     }
 
     /// y = alpha * op(K) * x + beta * y

@@ -796,6 +796,46 @@ int rlhip_pdk_var_set_fused(rlhip_ctx* ctx, int on);
 /* The routes of rlhip_pdk_cross_var_*, one count per call that reached a route: 58 fused, 59 composed.  -1 for any other index. */
 int64_t rlhip_pdk_var_path_count(rlhip_ctx* ctx, int which);
 
+/* rlhip_pdk_cross_grad_*: the gradient of a kernel expansion with respect to the evaluation point (rbf_grad.hip;
+ * RandLAPACK::krr_predict_grad, rl_krill.hh).  Z rows_x x mz (ldz) evaluation points, X rows_x x nx (ldx), B nx x n (ldb), all
+ * DEVICE; kernel and bandwidth as in rlhip_pdk_cross_apply_*.  G is rows_x x (mz n) (ldg >= rows_x); its column r mz + i holds
+ *   alpha * sum_j w(s_ij) (Z(:, i) - X(:, j)) B(j, r),   s_ij = |Z(:, i) - X(:, j)|^2,   w(s) = 2 dk/ds,
+ * the gradient at point i of right-hand side r, laid out like Z.  w(s) = w(0) u(s):
+ *        RLHIP_PDK_SQEXP     w(0) = -1 / l^2        u = exp(-s / (2 l^2))
+ *        RLHIP_PDK_MATERN32  w(0) = -3 / l^2        u = exp(-a)
+ *        RLHIP_PDK_MATERN52  w(0) = -5 / (3 l^2)    u = (1 + a) exp(-a)          a as for the kernel itself
+ * with the kernels' constants, the cross apply's s = (|z|^2 + |x|^2) - 2 z.x and, for the Matern kinds, its clamp of s at 0, so the
+ * gradient is finite and smooth at coincident points.  Coordinate c is evaluated as alpha * (w(0) * fma(z_c, T_0, -T_c)) with
+ * T_0 = sum_j u_ij B(j, r) and T_c = sum_j u_ij (X(c, j) B(j, r)): a cross apply with rows_x + 1 times as many columns.  Its error is of
+ * the order eps (|z_c| + |x_c|) sum_j |w_ij| |B(j, r)|, the class of the norm expansion's own.
+ * G is written, never read.  alpha == 0, nx == 0: exact zeros, X and B are not read.  mz == 0 or n == 0: returns 0 and touches nothing.
+ * Rows of G past rows_x and columns past mz n are not touched.
+ *   Composed route (the default): B' = [B, x_1 o B, ..., x_d o B] per right-hand side (nx x n (rows_x + 1)) in the scratch arena, the
+ *   cross apply's own machinery on it with u in place of the kernel function -- its fused kernel for n (rows_x + 1) <=
+ *   RLHIP_RBF_FUSED_MAX_N and RLHIP_OPT_RBF_FUSED != 0, row blocks of the weight matrix otherwise, never split over X -- into an
+ *   mz x n (rows_x + 1) block of scratch, and one thread per entry of G.  Z is cut into blocks of at most max(2^26 / (n (rows_x + 1)), 1)
+ *   points, a multiple of 256 when there are several.
+ *   Fused route (opt-in: rlhip_pdk_grad_set_fused(ctx, 1), and rlhip_pdk_grad_fused(rows_x, n) != 0): ONE launch beside the norms; B'
+ *   is formed in LDS from the staged tiles of X and B, T in the accumulators of the cross apply's tile walk, and the combination is
+ *   the kernel's epilogue.  The sums over j run in the order of j, sixteen at a time; no atomics.  Bit contract: column r mz + i of G is
+ *   a function of Z(:, i), X, B and alpha alone -- not of mz, of the point's place in Z, of the grid or of the device.
+ * Returns 0, or -(position of the first bad argument): -2 rows_x < 1, -3 mz < 0, -4 Z NULL, -5 ldz < rows_x, -6 nx < 0, -7 X NULL,
+ * -8 ldx < rows_x, -9 kernel, -10 bandwidth not > 0, -11 n < 0, -13 B NULL, -14 ldb < max(nx, 1), -15 G NULL, -16 ldg < rows_x; a NULL
+ * array is an error only where the call would read (or write) it.  Nothing is launched on an argument error. */
+#define RLHIP_PDK_GRAD_FUSED_MAX_COLS 64      /* n (rows_x + 1) the fused kernel carries: four 16-column accumulator tiles, the cross apply's width */
+int rlhip_pdk_cross_grad_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t nx, const double* X, int64_t ldx,
+                             int kernel, double bandwidth, int64_t n, double alpha, const double* B, int64_t ldb, double* G, int64_t ldg);
+int rlhip_pdk_cross_grad_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t nx, const float* X, int64_t ldx,
+                             int kernel, float bandwidth, int64_t n, float alpha, const float* B, int64_t ldb, float* G, int64_t ldg);
+/* The shapes the fused kernel serves when it is asked for, a function of the shape alone: 1 where 1 <= rows_x <=
+ * RLHIP_RBF_FUSED_MAX_ROWS_X and 1 <= n (rows_x + 1) <= RLHIP_PDK_GRAD_FUSED_MAX_COLS, else 0. */
+int rlhip_pdk_grad_fused(int64_t rows_x, int64_t n);
+/* on != 0: rlhip_pdk_cross_grad_* on this context takes its fused kernel wherever rlhip_pdk_grad_fused says so; 0 (the default): always
+ * the composed route.  Returns the value found, -1 for a NULL context. */
+int rlhip_pdk_grad_set_fused(rlhip_ctx* ctx, int on);
+/* The routes of rlhip_pdk_cross_grad_*, one count per call that reached a route: 74 fused, 75 composed.  -1 for any other index. */
+int64_t rlhip_pdk_grad_path_count(rlhip_ctx* ctx, int which);
+
 /* ---- row-block sharding across the GPUs of a node (new design; the reference has no
  *      distributed code).  One process per GPU.  Sum all-reduces run on the context's stream through RCCL
  *      (bound at run time), or through a host-installed hook.  With no communicator every call is a no-op,

@@ -345,6 +345,19 @@ int rlhip_drv_krr_predict_restricted_pdk_f64(rlhip_ctx* ctx, int64_t rows_x, int
 int rlhip_drv_krr_predict_restricted_pdk_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t n, const float* X_pts,
                                              int64_t ldx, int kernel, float bandwidth, int64_t k, const int64_t* S_host, int64_t s, const float* alpha,
                                              int64_t ldalpha, float* Y, int64_t ldy);
+/* Gradients of the fitted functions with respect to the evaluation point: krr_predict_grad and krr_predict_restricted_grad,
+ * the arguments of rlhip_drv_krr_predict_pdk_* and rlhip_drv_krr_predict_restricted_pdk_* with G (DEVICE, rows_x x (mz s), ldg >= rows_x)
+ * in the place of Y: column c * mz + i is the gradient at Z(:, i) of the function of the c-th regularization, laid out like Z. */
+int rlhip_drv_krr_predict_grad_pdk_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t n, const double* X_pts,
+                                       int64_t ldx, int kernel, double bandwidth, int64_t s, const double* coeffs, int64_t ldcoef, double* G, int64_t ldg);
+int rlhip_drv_krr_predict_grad_pdk_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t n, const float* X_pts,
+                                       int64_t ldx, int kernel, float bandwidth, int64_t s, const float* coeffs, int64_t ldcoef, float* G, int64_t ldg);
+int rlhip_drv_krr_predict_restricted_grad_pdk_f64(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t n,
+                                                  const double* X_pts, int64_t ldx, int kernel, double bandwidth, int64_t k, const int64_t* S_host,
+                                                  int64_t s, const double* alpha, int64_t ldalpha, double* Grad, int64_t ldgrad);
+int rlhip_drv_krr_predict_restricted_grad_pdk_f32(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const float* Z, int64_t ldz, int64_t n,
+                                                  const float* X_pts, int64_t ldx, int kernel, float bandwidth, int64_t k, const int64_t* S_host,
+                                                  int64_t s, const float* alpha, int64_t ldalpha, float* Grad, int64_t ldgrad);
 /* The predictive variance of a restricted fit.  rlhip_drv_krill_restricted_rpchol_gp_pdk_* and rlhip_drv_krill_restricted_gp_pdk_*
  * are the two fits above with three more arguments: G_out (DEVICE, k_in x k_in, ldg >= k_in) and sigma_out (DEVICE, k_in) receive the fit's
  * basis (RandLAPACK::KrillRestrictedBasis), zero behind the achieved rank; alpha, S_host, state and status are bit for bit those of the fit

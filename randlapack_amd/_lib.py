@@ -327,7 +327,17 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the predictive variance
                                                                      c_i64, c_vp, c_i64, _Tp, c_i64, c_vp, c_i64, c_int]),
     })
 
-SIGNATURES["rlhip_lu_path_count"] = (c_i64, [c_vp, c_int])      # the routes of getrf / luqrcp_piv, 60 .. 66 (lu.hip)
+SIGNATURES["rlhip_pdk_grad_fused"] = (c_int, [c_i64, c_i64])      # the shape rule of the fused gradient kernel
+SIGNATURES["rlhip_pdk_grad_path_count"] = (c_i64, [c_vp, c_int])
+SIGNATURES["rlhip_pdk_grad_set_fused"] = (c_int, [c_vp, c_int])
+for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # gradients of KRR predictions (rbf_grad.hip, rl_krill.hh)
+    SIGNATURES.update({
+        f"rlhip_pdk_cross_grad_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, _T, c_i64, _T, c_vp, c_i64, c_vp, c_i64]),
+        f"rlhip_drv_krr_predict_grad_pdk_{_suf}": SIGNATURES[f"rlhip_drv_krr_predict_pdk_{_suf}"],                            # G, ldg in the place of Y, ldy
+        f"rlhip_drv_krr_predict_restricted_grad_pdk_{_suf}": SIGNATURES[f"rlhip_drv_krr_predict_restricted_pdk_{_suf}"],
+    })
+
+SIGNATURES["rlhip_lu_path_count"] =(c_i64, [c_vp, c_int])      # the routes of getrf / luqrcp_piv, 60 .. 66 (lu.hip)
 SIGNATURES["rlhip_tri_path_count"] = (c_i64, [c_vp, c_int])     # the routes of trsm / trsm_gather / trmm, 67 .. 73 (tri.hip)
 
 _lib = None

@@ -898,6 +898,32 @@ int drv_krr_predict(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int6
     });
 }
 template <typename T>
+int drv_krr_predict_grad(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts, int64_t ldx, int kernel,
+                         T bandwidth, int64_t s, const T* coeffs, int64_t ldcoef, T* G, int64_t ldg) {
+    if (!pdk_known(kernel)) return -9;
+    return guarded([&] {
+        blas::Queue q(ctx);
+        lo::RBFCrossKernel<T> Kzx(rows_x, mz, Z, n, X_pts, bandwidth, q, ldz, ldx);
+        Kzx.set_kernel((RandLAPACK::PDKernel)kernel);
+        RandLAPACK::krr_predict_grad(Kzx, s, coeffs, ldcoef, G, ldg);
+        return 0;
+    });
+}
+template <typename T>
+int drv_krr_predict_restricted_grad(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts, int64_t ldx,
+                                    int kernel, T bandwidth, int64_t k, const int64_t* S_host, int64_t s, const T* alpha, int64_t ldalpha, T* Grad,
+                                    int64_t ldgrad) {
+    if (!pdk_known(kernel)) return -9;
+    return guarded([&] {
+        blas::Queue q(ctx);
+        std::vector<T> regs{(T)0};
+        lo::RBFKernelMatrix<T> G(n, X_pts, rows_x, bandwidth, regs, q, ldx);
+        G.set_kernel((RandLAPACK::PDKernel)kernel);
+        RandLAPACK::krr_predict_restricted_grad(G, k, S_host, mz, Z, ldz, s, alpha, ldalpha, Grad, ldgrad);
+        return 0;
+    });
+}
+template <typename T>
 int drv_krill_restricted_rpchol(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t n, int kernel, T bandwidth, const T* regs_host,
                                 int64_t num_ops, const T* H, int64_t ldh, int64_t s, int64_t* k, int64_t b, int64_t* S_host, T* alpha, int64_t ldalpha,
                                 uint32_t state[6], int status[2], RandLAPACK::KrillRestrictedBasis<T>* basis = nullptr) {
@@ -1061,6 +1087,17 @@ extern "C" {
     int rlhip_drv_krr_predict_pdk_##SUF(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts,           \
                                         int64_t ldx, int kernel, T bandwidth, int64_t s, const T* coeffs, int64_t ldcoef, T* Y, int64_t ldy) {    \
         return drv_krr_predict<T>(ctx, rows_x, mz, Z, ldz, n, X_pts, ldx, kernel, bandwidth, s, coeffs, ldcoef, Y, ldy);                          \
+    }                                                                                                                                             \
+    int rlhip_drv_krr_predict_grad_pdk_##SUF(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n, const T* X_pts,      \
+                                             int64_t ldx, int kernel, T bandwidth, int64_t s, const T* coeffs, int64_t ldcoef, T* G,              \
+                                             int64_t ldg) {                                                                                       \
+        return drv_krr_predict_grad<T>(ctx, rows_x, mz, Z, ldz, n, X_pts, ldx, kernel, bandwidth, s, coeffs, ldcoef, G, ldg);                     \
+    }                                                                                                                                             \
+    int rlhip_drv_krr_predict_restricted_grad_pdk_##SUF(rlhip_ctx* ctx, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t n,           \
+                                                        const T* X_pts, int64_t ldx, int kernel, T bandwidth, int64_t k, const int64_t* S_host,   \
+                                                        int64_t s, const T* alpha, int64_t ldalpha, T* Grad, int64_t ldgrad) {                    \
+        return drv_krr_predict_restricted_grad<T>(ctx, rows_x, mz, Z, ldz, n, X_pts, ldx, kernel, bandwidth, k, S_host, s, alpha, ldalpha, Grad,  \
+                                                  ldgrad);                                                                                        \
     }                                                                                                                                             \
     int rlhip_drv_rbf_kernel_apply_##SUF(rlhip_ctx* ctx, const T* X_pts, int64_t ldx, int64_t rows_x, int64_t dim, T bandwidth,                   \
                                          const T* regs_host, int64_t num_ops, int eval_includes_reg, int matrix_free, int64_t n, T alpha,         \

@@ -10,6 +10,8 @@
 //   rlhip_pdk_cross_submatrix_*, rlhip_pdk_cross_apply_*: the same two routines with the kernel function as an argument.  The
 //       Matern kinds evaluate matern_of_s (rlhip_device.h) where the squared exponential evaluates exp, on both routes: the squared distance
 //       clamped at 0, a sqrt, two fused multiply-adds, an exp.
+//   rlhip::pdk_cross_apply_fn: the apply behind its argument checks with the scalar function as a PdkFn, for rbf_grad.hip, whose gradient
+//       weights run through the same two routes: the Matern weights as WEIGHT instantiations of the kernels, never split over X.
 //
 // The fused kernel.  A 256-thread workgroup owns 64 points of Z, 16 per wave; lane (g = lane >> 4, c = lane & 15) of a wave holds, for
 // its wave's point c, the Z rows 4 kk + g (times -2, exact) in registers for the whole loop.  X is walked in tiles of TP points that are
@@ -56,7 +58,8 @@ struct RbfArgs {
 // MATERN = false is the squared exponential, true the two Matern kinds (told apart by a.third alone, matern_of_s): the squared exponential
 // keeps an instantiation of its own, so the sqrt and the polynomial cost it no register.
 // SPLIT = false walks all of X and writes C; SPLIT = true walks chunk blockIdx.y of X and writes its partial (see the header comment).
-template <typename T, int KS, int NT, bool MATERN, bool SPLIT>
+// WEIGHT = true (MATERN = true, SPLIT = false only): pdk_weight_of_s in place of matern_of_s, the gradient weight of DESIGN 4.30.
+template <typename T, int KS, int NT, bool MATERN, bool SPLIT, bool WEIGHT = false>
 __global__ __launch_bounds__(RBF_WG) void rbf_fused_kernel(const RbfArgs<T> a) {
     using M = Mfma16x4<T>;
     using acc_t = typename M::acc_t;
@@ -141,7 +144,8 @@ __global__ __launch_bounds__(RBF_WG) void rbf_fused_kernel(const RbfArgs<T> a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const T sq = (znorm + Ns[16 * st + M::drow_g(g, r)]) + s[r];
-                if constexpr (MATERN) p[r] = matern_of_s(sq, a.scale, a.third);
+                if constexpr (WEIGHT) p[r] = pdk_weight_of_s(sq, a.scale, a.third);
+                else if constexpr (MATERN) p[r] = matern_of_s(sq, a.scale, a.third);
                 else p[r] = rbf_exp(a.scale * sq);
             }
 #pragma unroll
@@ -231,11 +235,16 @@ inline int64_t rbf_split_chunks(int64_t mz, int64_t nx, int64_t* ch) {
     return (nx + *ch - 1) / *ch;      // no chunk is empty
 }
 
-template <typename T, int KS, int NT, bool MATERN>
+template <typename T, int KS, int NT, bool MATERN, bool WEIGHT = false>
 int launch_fused(rlhip_ctx* c, const RbfArgs<T>& a) {
     constexpr size_t bytes = 2 * (size_t)rbf_tile_elems<T, KS, NT>(rbf_tp<T, KS, NT>()) * sizeof(T);
     static_assert(bytes <= (size_t)RBF_LDS_CAP, "fused RBF kernel: the two staging buffers exceed the LDS budget");
     const int64_t wgs = (a.mz + RBF_ZP - 1) / RBF_ZP;
+    if constexpr (WEIGHT) {
+        hipLaunchKernelGGL((rbf_fused_kernel<T, KS, NT, true, false, true>), dim3((unsigned)wgs), dim3(RBF_WG), bytes, c->stream, a);
+        RLHIP_LAUNCH_CHECK();
+        return 0;
+    }
     if (a.part) {      // split: a.ch points of X per workgroup, then the ordered sum of the partials
         const int64_t g = (a.nx + a.ch - 1) / a.ch;
         hipLaunchKernelGGL((rbf_fused_kernel<T, KS, NT, MATERN, true>), dim3((unsigned)wgs, (unsigned)g), dim3(RBF_WG), bytes, c->stream, a);
@@ -249,20 +258,20 @@ int launch_fused(rlhip_ctx* c, const RbfArgs<T>& a) {
     RLHIP_LAUNCH_CHECK();
     return 0;
 }
-template <typename T, int KS, bool MATERN>
+template <typename T, int KS, bool MATERN, bool WEIGHT = false>
 int launch_fused_n(rlhip_ctx* c, const RbfArgs<T>& a) {
-    if (a.n <= 16) return launch_fused<T, KS, 1, MATERN>(c, a);
-    if (a.n <= 32) return launch_fused<T, KS, 2, MATERN>(c, a);
-    return launch_fused<T, KS, 4, MATERN>(c, a);
+    if (a.n <= 16) return launch_fused<T, KS, 1, MATERN, WEIGHT>(c, a);
+    if (a.n <= 32) return launch_fused<T, KS, 2, MATERN, WEIGHT>(c, a);
+    return launch_fused<T, KS, 4, MATERN, WEIGHT>(c, a);
 }
-template <typename T, bool MATERN>
+template <typename T, bool MATERN, bool WEIGHT = false>
 int launch_fused_rows(rlhip_ctx* c, const RbfArgs<T>& a) {      // KS = rows_x / 4 rounded up to a power of two (zero rows add exactly 0)
-    if (a.rows_x <= 4) return launch_fused_n<T, 1, MATERN>(c, a);
-    if (a.rows_x <= 8) return launch_fused_n<T, 2, MATERN>(c, a);
-    if (a.rows_x <= 16) return launch_fused_n<T, 4, MATERN>(c, a);
-    if (a.rows_x <= 32) return launch_fused_n<T, 8, MATERN>(c, a);
-    if (a.rows_x <= 64) return launch_fused_n<T, 16, MATERN>(c, a);
-    return launch_fused_n<T, 32, MATERN>(c, a);
+    if (a.rows_x <= 4) return launch_fused_n<T, 1, MATERN, WEIGHT>(c, a);
+    if (a.rows_x <= 8) return launch_fused_n<T, 2, MATERN, WEIGHT>(c, a);
+    if (a.rows_x <= 16) return launch_fused_n<T, 4, MATERN, WEIGHT>(c, a);
+    if (a.rows_x <= 32) return launch_fused_n<T, 8, MATERN, WEIGHT>(c, a);
+    if (a.rows_x <= 64) return launch_fused_n<T, 16, MATERN, WEIGHT>(c, a);
+    return launch_fused_n<T, 32, MATERN, WEIGHT>(c, a);
 }
 
 inline unsigned grid1(int64_t work, int per) { return (unsigned)((work + per - 1) / per); }
@@ -351,9 +360,17 @@ int pdk_cross_apply(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_
         }
         return 0;
     }
+    return rlhip::pdk_cross_apply_fn<T>(c, rows_x, mz, Z, ldz, nx, X, ldx, rlhip::pdk_fn<T>(kernel, bandwidth), n, alpha, B, ldb, beta, C, ldc);
+}
+
+}  // namespace
+
+namespace rlhip {
+template <typename T>
+int pdk_cross_apply_fn(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t nx, const T* X, int64_t ldx, PdkFn<T> f, int64_t n,
+                       T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc) {
     const int64_t route = c->opt[RLHIP_OPT_RBF_FUSED];
     const bool fused = route != 0 && n <= RLHIP_RBF_FUSED_MAX_N && rows_x <= RLHIP_RBF_FUSED_MAX_ROWS_X;
-    const PdkFn<T> f = rlhip::pdk_fn<T>(kernel, bandwidth);
     ws_scope ws(c);
     T* nr = ws.alloc<T>((size_t)(mz + nx));                    // the fused route's whole scratch
     if (!nr) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
@@ -364,7 +381,7 @@ int pdk_cross_apply(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_
         c->rbf_path_count[0]++;
         RbfArgs<T> a{rows_x, mz, nx, n, Z, ldz, X, ldx, nr, nr + mz, B, ldb, C, ldc, alpha, beta, f.scale, f.third, nullptr, 0, 0};
         int64_t ch = nx;
-        const int64_t g = route == 2 ? rbf_split_chunks(mz, nx, &ch) : 1;
+        const int64_t g = route == 2 && !f.weight ? rbf_split_chunks(mz, nx, &ch) : 1;
         if (g > 1) {
             a.ch = ch;
             a.mzp = (mz + RBF_ZP - 1) / RBF_ZP * RBF_ZP;
@@ -372,6 +389,7 @@ int pdk_cross_apply(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_
             if (!a.part) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
             c->rbf_split_count++;
         }
+        if (f.weight) return launch_fused_rows<T, true, true>(c, a);
         return f.matern ? launch_fused_rows<T, true>(c, a) : launch_fused_rows<T, false>(c, a);
     }
     c->rbf_path_count[1]++;
@@ -387,8 +405,11 @@ int pdk_cross_apply(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_
     }
     return rc;
 }
-
-}  // namespace
+template int pdk_cross_apply_fn<double>(rlhip_ctx*, int64_t, int64_t, const double*, int64_t, int64_t, const double*, int64_t, PdkFn<double>, int64_t,
+                                        double, const double*, int64_t, double, double*, int64_t);
+template int pdk_cross_apply_fn<float>(rlhip_ctx*, int64_t, int64_t, const float*, int64_t, int64_t, const float*, int64_t, PdkFn<float>, int64_t, float,
+                                       const float*, int64_t, float, float*, int64_t);
+}  // namespace rlhip
 
 extern "C" {
 

@@ -114,6 +114,18 @@ __device__ __forceinline__ T matern_of_s(T s, T c, T third) {
     const T a = c * pdk_sqrt(s);
     return pdk_fma(a, pdk_fma(a, third, T(1)), T(1)) * pdk_exp(-a);
 }
+// ---- the gradient weights of the same kernels: grad_z k(z, x) = w(s) (z - x), w(s) = 2 dk/ds = w(0) u(s), and u is what the
+//      device kernels evaluate; the caller multiplies by w(0) once, after the sums (PdkFn's weight forms, rlhip_internal.h).
+//        squared exponential  w(0) = -1 / l^2        u = exp(scale s): the kernel itself, no function of its own
+//        Matern 3/2           w(0) = -3 / l^2        u = exp(-a)              lin = 0: fma(a, 0, 1) is exactly 1
+//        Matern 5/2           w(0) = -5 / (3 l^2)    u = (1 + a) exp(-a)      lin = 1: 1 + a rounded once
+//      a = c sqrt(s) with matern_of_s's c and its select-clamp; u(0) is exactly 1, and u is smooth in s wherever k is.
+template <typename T>
+__device__ __forceinline__ T pdk_weight_of_s(T s, T c, T lin) {
+    s = s < T(0) ? T(0) : s;
+    const T a = c * pdk_sqrt(s);
+    return pdk_fma(a, lin, T(1)) * pdk_exp(-a);
+}
 
 // ---- the fused two-point-set kernels (rbf.hip rbf_fused_kernel, rbf_var.hip pdk_var_fused_kernel): workgroup shape and the layout of
 //      the tiles they stage in LDS

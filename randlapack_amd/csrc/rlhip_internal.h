@@ -187,6 +187,9 @@ struct rlhip_ctx {
     // the in-place solver, [5] = 72 trmm_right_upper calls, [6] = 73 trmm_left_upper calls
     int64_t tri_path_count[7] = {};
     int var_fused = 0;               // rlhip_pdk_var_set_fused: 1 = rlhip_pdk_cross_var_* takes its fused kernel where the shape allows
+    // the routes of the kernel-gradient apply (rbf_grad.hip), read through rlhip_pdk_grad_path_count: [0] = 74 fused, [1] = 75 composed
+    int64_t grad_path_count[2] = {};
+    int grad_fused = 0;              // rlhip_pdk_grad_set_fused: 1 = rlhip_pdk_cross_grad_* takes its fused kernel where the shape allows
 };
 
 // every host wait of the library goes through here: the epoch lets deferred read-backs know that an earlier wait already covered them
@@ -457,10 +460,13 @@ int dot_dev(rlhip_ctx* c, int64_t n, const T* x, const T* y, T* out_dev);
 // The kernel function of a positive-definite kernel matrix as the device kernels take it (RLHIP_PDK_*): whether it is a Matern
 // kind, and two constants, each computed in double and rounded once to T.  scale = -1 / (2 l^2) for the squared exponential, sqrt(3) / l
 // and sqrt(5) / l for Matern 3/2 and 5/2; third = 1 / 3 for Matern 5/2 and 0 otherwise (matern_of_s, rlhip_device.h).
+// weight = true (pdk_weight_fn alone): the Matern kinds' gradient weight u(s) in place of the kernel, pdk_weight_of_s(s, scale, third) with
+// third = lin; the squared exponential's u is its kernel, so its weight form is its value form.
 template <typename T>
 struct PdkFn {
     bool matern;
     T scale, third;
+    bool weight = false;
 };
 inline bool pdk_kind_ok(int kernel) { return kernel >= RLHIP_PDK_SQEXP && kernel <= RLHIP_PDK_MATERN52; }
 template <typename T>
@@ -470,11 +476,28 @@ PdkFn<T> pdk_fn(int kernel, T bandwidth) {
     if (kernel == RLHIP_PDK_MATERN32) return {true, (T)(1.7320508075688772 / l), T(0)};             // sqrt(3), correctly rounded
     return {true, (T)(2.23606797749979 / l), (T)(1.0 / 3.0)};                                         // sqrt(5), correctly rounded
 }
+// the gradient weight of a kernel function: u(s) as a PdkFn, and in *w0 the factor w(0) = -1 / l^2, -3 / l^2, -5 / (3 l^2)
+template <typename T>
+PdkFn<T> pdk_weight_fn(int kernel, T bandwidth, T* w0) {
+    const double l = (double)bandwidth;
+    if (kernel == RLHIP_PDK_SQEXP) { *w0 = (T)(-1.0 / (l * l)); return {false, (T)(-1.0 / (2.0 * l * l)), T(0), false}; }
+    if (kernel == RLHIP_PDK_MATERN32) { *w0 = (T)(-3.0 / (l * l)); return {true, (T)(1.7320508075688772 / l), T(0), true}; }
+    *w0 = (T)(-5.0 / (3.0 * l * l));
+    return {true, (T)(2.23606797749979 / l), T(1), true};
+}
 // nr[j] = |X(:, j)|^2 for cols points, and K(i, j) <- f((nr_rows[i] + nr_cols[j]) + K(i, j)) on a rows x cols block that holds -2 z_i^T x_j
 // (cols <= 65535), f the kernel function: the two kernels of the norm-expansion submatrix, for the two-point-set routines of rbf.hip
 template <typename T>
 int sqexp_colnorms(rlhip_ctx* c, int64_t rows_x, int64_t cols, const T* X, int64_t ldx, T* nr);
 template <typename T>
 int pdk_epilogue(rlhip_ctx* c, int64_t rows, int64_t cols, const T* nr_rows, const T* nr_cols, PdkFn<T> f, T* K, int64_t ldk);
+
+// ---- rbf.hip
+// rlhip_pdk_cross_apply_* behind its argument checks, for mz, n, nx > 0 and alpha != 0, with the scalar function as a PdkFn: the kernel
+// functions for the public entries, a gradient weight for rbf_grad.hip.  It picks its fused or row-block route and counts it as they do;
+// a weight form is never split over X.
+template <typename T>
+int pdk_cross_apply_fn(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t nx, const T* X, int64_t ldx, PdkFn<T> f, int64_t n,
+                       T alpha, const T* B, int64_t ldb, T beta, T* C, int64_t ldc);
 
 }  // namespace rlhip

@@ -122,7 +122,7 @@ __global__ void sq_colnorms_kernel(int64_t rows_x, int64_t cols, const T* __rest
     nr[j] = s;
 }
 
-template <typename T, bool MATERN>
+template <typename T, bool MATERN, bool WEIGHT = false>
 __global__ void sqexp_epilogue_kernel(int64_t rows, int64_t cols, const T* __restrict__ nr_rows, const T* __restrict__ nr_cols, T scale, T third,
                                       T* __restrict__ K, int64_t ldk) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -130,7 +130,8 @@ __global__ void sqexp_epilogue_kernel(int64_t rows, int64_t cols, const T* __res
     if (i >= rows) return;
     T* p = K + i + j * ldk;
     const T s = (nr_rows[i] + nr_cols[j]) + *p;
-    if constexpr (MATERN) *p = rlhip_dev::matern_of_s(s, scale, third);
+    if constexpr (WEIGHT) *p = rlhip_dev::pdk_weight_of_s(s, scale, third);
+    else if constexpr (MATERN) *p = rlhip_dev::matern_of_s(s, scale, third);
     else *p = dexp(scale * s);
 }
 
@@ -392,7 +393,9 @@ int pdk_columns(rlhip_ctx* c, int64_t rows_x, int64_t n, const T* X, int64_t ldx
 template <typename T>
 int launch_epilogue(rlhip_ctx* c, int64_t rows, int64_t cols, const T* nr_rows, const T* nr_cols, PdkFn<T> f, T* K, int64_t ldk) {
     const dim3 grid(grid1(rows, 256), (unsigned)cols);
-    if (f.matern)
+    if (f.weight)
+        hipLaunchKernelGGL((sqexp_epilogue_kernel<T, true, true>), grid, dim3(256), 0, c->stream, rows, cols, nr_rows, nr_cols, f.scale, f.third, K, ldk);
+    else if (f.matern)
         hipLaunchKernelGGL((sqexp_epilogue_kernel<T, true>), grid, dim3(256), 0, c->stream, rows, cols, nr_rows, nr_cols, f.scale, f.third, K, ldk);
     else
         hipLaunchKernelGGL((sqexp_epilogue_kernel<T, false>), grid, dim3(256), 0, c->stream, rows, cols, nr_rows, nr_cols, f.scale, f.third, K, ldk);

@@ -216,6 +216,24 @@ class Context:
         """routes of rlhip_pdk_cross_var_*: 58 fused, 59 composed (include/rlhip.h rlhip_pdk_var_path_count)"""
         return int(self.lib.rlhip_pdk_var_path_count(self.h, which))
 
+    def grad_path_count(self, which: int) -> int:
+        """routes of rlhip_pdk_cross_grad_*: 74 fused, 75 composed (include/rlhip.h rlhip_pdk_grad_path_count)"""
+        return int(self.lib.rlhip_pdk_grad_path_count(self.h, which))
+
+    def grad_fused(self, on: bool = True):
+        """context manager: rlhip_pdk_cross_grad_* on this context takes its fused kernel where the shape allows (rlhip_pdk_grad_set_fused);
+        the value found is put back"""
+        import contextlib
+
+        @contextlib.contextmanager
+        def _cm():
+            was = int(self.lib.rlhip_pdk_grad_set_fused(self.h, int(bool(on))))
+            try:
+                yield self
+            finally:
+                self.lib.rlhip_pdk_grad_set_fused(self.h, was)
+        return _cm()
+
     def lu_path_count(self, which: int) -> int:
         """routes of the LU layer: a panel on 60 the LDS kernel, 61 the fast step, 62 the general register kernel; 63 getrf calls with an
         outer block wider than a panel, 64 unit_lower_solve_kernel launches; luqrcp_piv on 65 the LDS walk, 66 the serial kernel
@@ -972,6 +990,45 @@ def krr_predict_pdk(ctx: Context, Z, mz, Xp, rows_x, n, kernel, bandwidth, coeff
                                                              coeffs.data_ptr(), max(_ld(coeffs), 1), Y.data_ptr(), max(mz, 1))
     _drv_check(ctx, rc, "krr_predict_pdk")
     return Y
+
+
+def pdk_cross_grad(ctx: Context, Z, X, rows_x, mz, nx, kernel, bandwidth, B, n, alpha=1.0, G=None):
+    """rlhip_pdk_cross_grad_*: G (rows_x x (mz n)), column r mz + i = the gradient at Z(:, i) of alpha K(Z, X) B(:, r); a tensor (n mz, ldg)
+    column-major, laid out like Z per right-hand side.  G given: written in place with its own leading dimension."""
+    torch = _torch()
+    suf, _ = _suf(X)
+    if G is None:
+        G = torch.zeros((n * mz, rows_x), dtype=X.dtype, device=X.device)
+    rc = getattr(ctx.lib, f"rlhip_pdk_cross_grad_{suf}")(ctx.h, rows_x, mz, _ptr(Z), _ld(Z), nx, _ptr(X), _ld(X), kernel, bandwidth, n, alpha, _ptr(B),
+                                                        max(_ldc(B), 1), G.data_ptr(), max(_ldc(G), 1))
+    _lib.check(rc, "pdk_cross_grad")
+    return G
+
+
+def krr_predict_grad_pdk(ctx: Context, Z, mz, Xp, rows_x, n, kernel, bandwidth, coeffs, s):
+    """krr_predict_grad: the gradients of krr_predict_pdk's functions at the points of Z; (s mz, rows_x) column-major, row c mz + i of the
+    tensor = the gradient at Z(:, i) of the function of the c-th regularization"""
+    torch = _torch()
+    suf, _ = _suf(Xp)
+    G = torch.zeros((s * mz, rows_x), dtype=Xp.dtype, device=Xp.device)
+    rc = getattr(ctx.lib, f"rlhip_drv_krr_predict_grad_pdk_{suf}")(ctx.h, rows_x, mz, Z.data_ptr(), _ld(Z), n, Xp.data_ptr(), _ld(Xp), kernel, bandwidth,
+                                                                  s, coeffs.data_ptr(), max(_ldc(coeffs), 1), G.data_ptr(), rows_x)
+    _drv_check(ctx, rc, "krr_predict_grad_pdk")
+    return G
+
+
+def krr_predict_restricted_grad_pdk(ctx: Context, Z, mz, Xp, rows_x, n, kernel, bandwidth, S, alpha, s):
+    """krr_predict_restricted_grad: the gradients of krr_predict_restricted_pdk's functions at the points of Z, laid out as
+    krr_predict_grad_pdk lays them out"""
+    torch = _torch()
+    suf, _ = _suf(Xp)
+    S = np.ascontiguousarray(S, dtype=np.int64)
+    G = torch.zeros((s * mz, rows_x), dtype=Xp.dtype, device=Xp.device)
+    rc = getattr(ctx.lib, f"rlhip_drv_krr_predict_restricted_grad_pdk_{suf}")(ctx.h, rows_x, mz, Z.data_ptr(), _ld(Z), n, Xp.data_ptr(), _ld(Xp), kernel,
+                                                                             bandwidth, int(S.size), S.ctypes.data_as(C.POINTER(C.c_int64)), s,
+                                                                             alpha.data_ptr(), max(_ldc(alpha), 1), G.data_ptr(), rows_x)
+    _drv_check(ctx, rc, "krr_predict_restricted_grad_pdk")
+    return G
 
 
 def pdk_kernel_apply(ctx: Context, X, rows_x, dim, kernel, bandwidth, B, n, alpha=1.0, beta=0.0, C_=None, regs=(), eval_includes_reg=False,
