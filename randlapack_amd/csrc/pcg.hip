@@ -25,8 +25,6 @@ using namespace rlhip_dev;
 
 constexpr int FUSED_MAX = 64;       // widest block the row-per-thread kernels and the one-workgroup solve serve
 
-inline unsigned grid1(int64_t work, int per) { return (unsigned)((work + per - 1) / per); }
-
 __device__ inline double dsqrt(double x) { return sqrt(x); }
 __device__ inline float dsqrt(float x) { return sqrtf(x); }
 

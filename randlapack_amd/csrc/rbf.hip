@@ -265,16 +265,9 @@ int launch_fused_n(rlhip_ctx* c, const RbfArgs<T>& a) {
     return launch_fused<T, KS, 4, MATERN, WEIGHT>(c, a);
 }
 template <typename T, bool MATERN, bool WEIGHT = false>
-int launch_fused_rows(rlhip_ctx* c, const RbfArgs<T>& a) {      // KS = rows_x / 4 rounded up to a power of two (zero rows add exactly 0)
-    if (a.rows_x <= 4) return launch_fused_n<T, 1, MATERN, WEIGHT>(c, a);
-    if (a.rows_x <= 8) return launch_fused_n<T, 2, MATERN, WEIGHT>(c, a);
-    if (a.rows_x <= 16) return launch_fused_n<T, 4, MATERN, WEIGHT>(c, a);
-    if (a.rows_x <= 32) return launch_fused_n<T, 8, MATERN, WEIGHT>(c, a);
-    if (a.rows_x <= 64) return launch_fused_n<T, 16, MATERN, WEIGHT>(c, a);
-    return launch_fused_n<T, 32, MATERN, WEIGHT>(c, a);
+int launch_fused_rows(rlhip_ctx* c, const RbfArgs<T>& a) {
+    return rbf_ks_dispatch(a.rows_x, [&](auto ks) { return launch_fused_n<T, decltype(ks)::value, MATERN, WEIGHT>(c, a); });
 }
-
-inline unsigned grid1(int64_t work, int per) { return (unsigned)((work + per - 1) / per); }
 
 // K (rows_k x cols_k, ldk) = K(Zb, Xb) for rows_k points Zb and cols_k points Xb with their norms: no argument checks, no counter
 template <typename T>
@@ -372,10 +365,8 @@ int pdk_cross_apply_fn(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int
     const int64_t route = c->opt[RLHIP_OPT_RBF_FUSED];
     const bool fused = route != 0 && n <= RLHIP_RBF_FUSED_MAX_N && rows_x <= RLHIP_RBF_FUSED_MAX_ROWS_X;
     ws_scope ws(c);
-    T* nr = ws.alloc<T>((size_t)(mz + nx));                    // the fused route's whole scratch
-    if (!nr) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
-    int rc = rlhip::sqexp_colnorms<T>(c, rows_x, mz, Z, ldz, nr);
-    if (rc == 0) rc = rlhip::sqexp_colnorms<T>(c, rows_x, nx, X, ldx, nr + mz);
+    T* nr;                                                     // the fused route's whole scratch
+    int rc = pdk_pair_norms<T>(c, ws, rows_x, mz, Z, ldz, nx, X, ldx, &nr);
     if (rc) return rc;
     if (fused) {
         c->rbf_path_count[0]++;
@@ -393,9 +384,7 @@ int pdk_cross_apply_fn(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int
         return f.matern ? launch_fused_rows<T, true>(c, a) : launch_fused_rows<T, false>(c, a);
     }
     c->rbf_path_count[1]++;
-    int64_t rb = ((int64_t)1 << 26) / nx;                      // the K block holds at most 2^26 entries (one row when nx > 2^26)
-    rb = rb < 1 ? 1 : (rb >= 256 ? (rb / 256) * 256 : rb);
-    if (rb > mz) rb = mz;
+    const int64_t rb = pdk_row_block(nx, mz);                  // rows of a block of K
     T* Kb = ws.alloc<T>((size_t)(rb * nx));
     if (!Kb) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     for (int64_t r0 = 0; rc == 0 && r0 < mz; r0 += rb) {

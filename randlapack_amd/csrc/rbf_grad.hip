@@ -249,15 +249,9 @@ int launch_grad_n(rlhip_ctx* c, const GradArgs<T>& a) {
     return launch_grad<T, KS, 4, MATERN>(c, a);
 }
 template <typename T, bool MATERN>
-int launch_grad_rows(rlhip_ctx* c, const GradArgs<T>& a) {      // KS = rows_x / 4 rounded up to a power of two (zero rows add exactly 0)
-    if (a.rows_x <= 4) return launch_grad_n<T, 1, MATERN>(c, a);
-    if (a.rows_x <= 8) return launch_grad_n<T, 2, MATERN>(c, a);
-    if (a.rows_x <= 16) return launch_grad_n<T, 4, MATERN>(c, a);
-    if (a.rows_x <= 32) return launch_grad_n<T, 8, MATERN>(c, a);
-    return launch_grad_n<T, 16, MATERN>(c, a);      // n (rows_x + 1) <= 64 leaves rows_x <= 63
+int launch_grad_rows(rlhip_ctx* c, const GradArgs<T>& a) {      // n (rows_x + 1) <= 64 leaves rows_x <= 63: KS stops at 16
+    return rbf_ks_dispatch<16>(a.rows_x, [&](auto ks) { return launch_grad_n<T, decltype(ks)::value, MATERN>(c, a); });
 }
-
-inline unsigned grid1(int64_t work, int per) { return (unsigned)((work + per - 1) / per); }
 
 // the shape rule of the fused route (include/rlhip.h)
 inline bool grad_fused_shape(int64_t rows_x, int64_t n) {
@@ -297,10 +291,8 @@ int pdk_cross_grad(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_t
     // the fused kernel is opt-in: DESIGN 4.30 has the measurements behind the default
     if (c->grad_fused && grad_fused_shape(rows_x, n)) {
         c->grad_path_count[0]++;
-        T* nr = ws.alloc<T>((size_t)(mz + nx));
-        if (!nr) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
-        int rc = rlhip::sqexp_colnorms<T>(c, rows_x, mz, Z, ldz, nr);
-        if (rc == 0) rc = rlhip::sqexp_colnorms<T>(c, rows_x, nx, X, ldx, nr + mz);
+        T* nr;
+        const int rc = rlhip::pdk_pair_norms<T>(c, ws, rows_x, mz, Z, ldz, nx, X, ldx, &nr);
         if (rc) return rc;
         const GradArgs<T> a{rows_x, mz, nx, n, Z, ldz, X, ldx, nr, nr + mz, B, ldb, G, ldg, alpha, w0, f.scale, f.third};
         return f.matern ? launch_grad_rows<T, true>(c, a) : launch_grad_rows<T, false>(c, a);
@@ -311,9 +303,7 @@ int pdk_cross_grad(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_t
     if (!Bp) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     hipLaunchKernelGGL(grad_bprime_kernel<T>, dim3(grid1(nx * ncols, 256)), dim3(256), 0, c->stream, d1, nx, n, X, ldx, B, ldb, Bp);
     RLHIP_LAUNCH_CHECK();
-    int64_t rb = ((int64_t)1 << 26) / ncols;                   // the block of T holds at most 2^26 entries, as rlhip_pdk_cross_var_*'s block of t
-    rb = rb < 1 ? 1 : (rb >= 256 ? (rb / 256) * 256 : rb);
-    if (rb > mz) rb = mz;
+    const int64_t rb = rlhip::pdk_row_block(ncols, mz);        // rows of a block of T
     T* Tm = ws.alloc<T>((size_t)(rb * ncols));
     if (!Tm) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     for (int64_t r0 = 0; r0 < mz; r0 += rb) {

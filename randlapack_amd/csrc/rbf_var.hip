@@ -249,16 +249,9 @@ int launch_var(rlhip_ctx* c, const VarArgs<T>& a) {
     return 0;
 }
 template <typename T, bool MATERN>
-int launch_var_rows(rlhip_ctx* c, const VarArgs<T>& a) {      // KS = rows_x / 4 rounded up to a power of two (zero rows add exactly 0)
-    if (a.rows_x <= 4) return launch_var<T, 1, MATERN>(c, a);
-    if (a.rows_x <= 8) return launch_var<T, 2, MATERN>(c, a);
-    if (a.rows_x <= 16) return launch_var<T, 4, MATERN>(c, a);
-    if (a.rows_x <= 32) return launch_var<T, 8, MATERN>(c, a);
-    if (a.rows_x <= 64) return launch_var<T, 16, MATERN>(c, a);
-    return launch_var<T, 32, MATERN>(c, a);
+int launch_var_rows(rlhip_ctx* c, const VarArgs<T>& a) {
+    return rbf_ks_dispatch(a.rows_x, [&](auto ks) { return launch_var<T, decltype(ks)::value, MATERN>(c, a); });
 }
-
-inline unsigned grid1(int64_t work, int per) { return (unsigned)((work + per - 1) / per); }
 
 inline int cross_apply(rlhip_ctx* c, int64_t rows_x, int64_t mz, const double* Z, int64_t ldz, int64_t nx, const double* X, int64_t ldx, int kernel,
                        double bandwidth, int64_t n, const double* B, int64_t ldb, double* C, int64_t ldc) {
@@ -314,18 +307,14 @@ int pdk_cross_var(rlhip_ctx* c, int64_t rows_x, int64_t mz, const T* Z, int64_t 
     // the fused kernel is opt-in: it measured slower than the product-based route on every shape of DESIGN 4.27
     if (c->var_fused && var_fused_shape(rows_x, k, s)) {
         c->var_path_count[0]++;
-        T* nr = ws.alloc<T>((size_t)(mz + k));
-        if (!nr) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
-        int rc = rlhip::sqexp_colnorms<T>(c, rows_x, mz, Z, ldz, nr);
-        if (rc == 0) rc = rlhip::sqexp_colnorms<T>(c, rows_x, k, Xs, ldx, nr + mz);
+        T* nr;
+        const int rc = rlhip::pdk_pair_norms<T>(c, ws, rows_x, mz, Z, ldz, k, Xs, ldx, &nr);
         if (rc) return rc;
         const VarArgs<T> a{rows_x, mz, k, kp, s, Z, ldz, Xs, ldx, nr, nr + mz, G, ldg, E, V, ldv, f.scale, f.third};
         return f.matern ? launch_var_rows<T, true>(c, a) : launch_var_rows<T, false>(c, a);
     }
     c->var_path_count[1]++;
-    int64_t rb = ((int64_t)1 << 26) / k;                       // the block of t holds at most 2^26 entries, as the cross apply's block of K
-    rb = rb < 1 ? 1 : (rb >= 256 ? (rb / 256) * 256 : rb);
-    if (rb > mz) rb = mz;
+    const int64_t rb = rlhip::pdk_row_block(k, mz);            // rows of a block of t, as the cross apply sizes its block of K
     T* tb = ws.alloc<T>((size_t)(rb * k));
     if (!tb) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     int rc = 0;

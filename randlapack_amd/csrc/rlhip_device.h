@@ -1,6 +1,7 @@
 // Wave- and grid-level device helpers shared by the kernel files of librlhip.so: the one copy of every helper that more than one
 // .hip file needs.  A kernel file pulls them in with `using namespace rlhip_dev;` inside its anonymous namespace.  Helpers that a
-// single file uses stay in that file.  gfx950 only: 64-lane wavefronts.
+// single file uses stay in that file.  gfx950 only: 64-lane wavefronts.  One host-side helper lives here too, beside the IntC it is
+// built on: rbf_ks_dispatch, which picks the KS instantiation of the fused two-point-set kernels.
 #pragma once
 #include "rlhip_internal.h"
 
@@ -127,8 +128,11 @@ __device__ __forceinline__ T pdk_weight_of_s(T s, T c, T lin) {
     return pdk_fma(a, lin, T(1)) * pdk_exp(-a);
 }
 
-// ---- the fused two-point-set kernels (rbf.hip rbf_fused_kernel, rbf_var.hip pdk_var_fused_kernel): workgroup shape and the layout of
-//      the tiles they stage in LDS
+// ---- the fused two-point-set kernels (rbf.hip rbf_fused_kernel, rbf_var.hip pdk_var_fused_kernel, rbf_grad.hip pdk_grad_fused_kernel):
+//      workgroup shape and the layout of the tiles they stage in LDS.  The walk over X itself (the fetch / stash of a tile and the
+//      pipelined sub-tile loop; rbf.hip's header has the scheme) stands in each of the three kernels, and a change to it goes into all
+//      three: as one inlined function of this header it compiled to other register counts, which crossed occupancy steps and cost the
+//      default apply 10 % in fp32 with 64 columns (profiles/rbf_walk_ab.jsonl).
 constexpr int RBF_WG = 256;
 constexpr int RBF_ZP = 64;                  // points of Z per workgroup
 constexpr int RBF_LDS_CAP = 64 * 1024;      // both buffers; no raised dynamic-LDS limit is needed below it
@@ -150,5 +154,18 @@ template <typename T, int KS, int NT> constexpr int rbf_tp() {
 
 // an integer as a type: the argument of a generic lambda that needs it at compile time
 template <int N> struct IntC { static constexpr int value = N; };
+
+// host side: f(IntC<KS>{}) for KS = rows_x / 4 rounded up to a power of two, at most KS_MAX (zero rows add exactly 0)
+template <int KS_MAX = 32, typename F>
+int rbf_ks_dispatch(int64_t rows_x, F&& f) {
+    if (rows_x <= 4) return f(IntC<1>{});
+    if (rows_x <= 8) return f(IntC<2>{});
+    if (rows_x <= 16) return f(IntC<4>{});
+    if (rows_x <= 32) return f(IntC<8>{});
+    if constexpr (KS_MAX >= 32) {
+        if (rows_x > 64) return f(IntC<32>{});
+    }
+    return f(IntC<16>{});
+}
 
 }  // namespace rlhip_dev

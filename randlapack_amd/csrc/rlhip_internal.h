@@ -220,6 +220,8 @@ struct ws_scope {
     template <typename T>
     T* alloc(size_t n) { return ws_alloc<T>(c, n); }   // nullptr when the arena cannot grow
 };
+// workgroups of `per` threads for `work` threads' worth of it
+static inline unsigned grid1(int64_t work, int per) { return (unsigned)((work + per - 1) / per); }
 // device buffer for the tagged-word exchanges between workgroups (QRCP / LU panel kernels); grows, lives with the context.
 // RLHIP_XCHG = 0: ordinary device memory, 1: fine-grained, 2: uncached (default)
 void* rlhip_xchg_buffer(rlhip_ctx* c, size_t bytes);
@@ -491,6 +493,21 @@ template <typename T>
 int sqexp_colnorms(rlhip_ctx* c, int64_t rows_x, int64_t cols, const T* X, int64_t ldx, T* nr);
 template <typename T>
 int pdk_epilogue(rlhip_ctx* c, int64_t rows, int64_t cols, const T* nr_rows, const T* nr_cols, PdkFn<T> f, T* K, int64_t ldk);
+// the norms of two point sets in one block of ws: (*nr)[i] = |Z(:, i)|^2 for i < mz, (*nr)[mz + j] = |X(:, j)|^2 for j < nx
+template <typename T>
+int pdk_pair_norms(rlhip_ctx* c, ws_scope& ws, int64_t rows_x, int64_t mz, const T* Z, int64_t ldz, int64_t nx, const T* X, int64_t ldx, T** nr) {
+    *nr = ws.alloc<T>((size_t)(mz + nx));
+    if (!*nr) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
+    const int rc = sqexp_colnorms<T>(c, rows_x, mz, Z, ldz, *nr);
+    return rc ? rc : sqexp_colnorms<T>(c, rows_x, nx, X, ldx, *nr + mz);
+}
+// rows per block of a product that goes through the scratch arena one row block (rows x cols) at a time: a block holds at most 2^26
+// entries (one row when cols > 2^26), a multiple of 256 rows where that is at least 256, and no more than the mz rows there are
+inline int64_t pdk_row_block(int64_t cols, int64_t mz) {
+    const int64_t rb = ((int64_t)1 << 26) / cols;
+    const int64_t r = rb < 1 ? 1 : (rb >= 256 ? (rb / 256) * 256 : rb);
+    return r > mz ? mz : r;
+}
 
 // ---- rbf.hip
 // rlhip_pdk_cross_apply_* behind its argument checks, for mz, n, nx > 0 and alpha != 0, with the scalar function as a PdkFn: the kernel

@@ -360,8 +360,6 @@ __global__ void gather_cols_kernel(int64_t m, const int64_t* __restrict__ idx, c
     out[r + c * ldo] = A[r + idx[c] * lda];
 }
 
-inline unsigned grid1(int64_t work, int per) { return (unsigned)((work + per - 1) / per); }
-
 // The three routines below serve the rlhip_sqexp_* / rlhip_rbf_apply_* entries (kernel = RLHIP_PDK_SQEXP, sh = 0) and the rlhip_pdk_* entries,
 // whose argument lists have `kernel` in front of the bandwidth: sh = 1 moves the codes of the arguments from there on by one.
 template <typename T>
@@ -463,9 +461,7 @@ int pdk_apply(rlhip_ctx* c, int64_t rows_x, int64_t dim, const T* X, int64_t ldx
     ws_scope ws(c);
     int rc = 0;
     T* nr = ws.alloc<T>((size_t)dim);
-    int64_t rb = ((int64_t)1 << 26) / dim;                 // the K block holds at most 2^26 entries (one row when dim > 2^26)
-    rb = rb < 1 ? 1 : (rb >= 256 ? (rb / 256) * 256 : rb);
-    if (rb > dim) rb = dim;
+    const int64_t rb = rlhip::pdk_row_block(dim, dim);     // rows of a block of K
     T* Kb = ws.alloc<T>((size_t)(rb * dim));
     if (!nr || !Kb) return RLHIP_ERR_HIP(hipErrorOutOfMemory);
     rc = sq_colnorms(c, rows_x, dim, X, ldx, nr);

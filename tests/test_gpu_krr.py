@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 DT = {"f64": np.float64, "f32": np.float32}
 FACTOR = 64.0
 SHAPES = [(1, 1, 1), (17, 63, 3), (65, 67, 17), (200, 1000, 64), (130, 130, 16)]
-ROWS = [1, 3, 4, 5, 16, 33, 128]
+ROWS = [1, 3, 4, 5, 16, 20, 33, 128]
 
 
 def _pts(a, T, ld=None):

@@ -26,7 +26,10 @@ FUSED_MAX_S = 8                                                              # R
 # panel of one column; three panels, five coordinates past a multiple of four; rows_x beyond the fused limit (the composed route); s beyond
 # the sums the fused kernel carries (the composed route, two passes over a row of t).  The fused kernel is opt-in (Context.var_fused); every
 # shape also runs on the composed route, by default and with the cross apply behind it forced onto its own composed route (rbf_fused = 0).
-KERNEL_SHAPES = [(1, 1, 1, 1), (63, 17, 2, 3), (65, 64, 5, 1), (130, 65, 3, 3), (200, 130, 17, 4), (70, 40, 130, 2), (66, 70, 4, FUSED_MAX_S + 3)]
+# The last two: 40 and 100 coordinates on the fused route (its instantiations for 33 .. 64 and 65 .. 128 coordinates); with 100 the fp64
+# kernel stages tiles of 16 centres: five tiles, the last of 6 centres, and two panels.
+KERNEL_SHAPES = [(1, 1, 1, 1), (63, 17, 2, 3), (65, 64, 5, 1), (130, 65, 3, 3), (200, 130, 17, 4), (70, 40, 130, 2), (66, 70, 4, FUSED_MAX_S + 3),
+                 (65, 70, 40, 2), (65, 70, 100, 2)]
 # fit then variance, (n, rows_x, k, b, s) and per n the bandwidths of the three kinds: the four of tests/test_gpu_krr_restricted.py and
 # three with k one past a panel, two panels and a bit, a panel and a half
 FIT_SHAPES = [(130, 2, 16, 16, 1), (300, 3, 24, 8, 3), (515, 5, 40, 16, 4), (48, 2, 48, 8, 2), (400, 3, 65, 16, 3), (640, 5, 130, 32, 3),
@@ -152,7 +155,7 @@ def test_kernel_matches_model(ctx, shape, kind, per_column, route, prec):
 
 
 def test_the_shapes_cover_both_routes(ctx):
-    assert [_expect_route(ctx, s, "fused") for s in KERNEL_SHAPES] == [58, 58, 58, 58, 58, 59, 59]
+    assert [_expect_route(ctx, s, "fused") for s in KERNEL_SHAPES] == [58, 58, 58, 58, 58, 59, 59, 58, 58]
     assert [_expect_route(ctx, s, "default") for s in KERNEL_SHAPES] == [59] * len(KERNEL_SHAPES)      # the fused kernel is opt-in
     assert ctx.lib.rlhip_pdk_var_set_fused(ctx.h, 1) == 0 and ctx.lib.rlhip_pdk_var_set_fused(ctx.h, 0) == 1      # returns the value found
     assert ctx.lib.rlhip_pdk_var_set_fused(None, 1) == -1

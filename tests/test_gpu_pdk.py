@@ -25,7 +25,7 @@ FACTOR = 64.0
 C_E = 16.0
 MATERN = [pk.MATERN32, pk.MATERN52]
 SHAPES = [(1, 1, 1), (17, 63, 3), (65, 67, 17), (130, 130, 16)]
-ROWS = [1, 4, 5, 33, 128]
+ROWS = [1, 4, 5, 20, 33, 128]
 
 
 def _pts(a, T, ld=None):

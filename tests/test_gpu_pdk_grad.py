@@ -22,10 +22,10 @@ DT = {"f64": np.float64, "f32": np.float32}
 FUSED_MAX_COLS = 64                                                          # RLHIP_PDK_GRAD_FUSED_MAX_COLS
 # (mz, nx, rows_x, n): the smallest case; nothing a multiple of anything; a second Z tile of one point and exactly one X tile; an X tile of
 # one point; coordinates one past a multiple of four; n (rows_x + 1) = 64 exactly; 68 columns, past one cross apply's width; 65 columns,
-# one past the fused kernel's limit; rows_x past the fused limit
+# one past the fused kernel's limit; rows_x past the fused limit; 40 coordinates on the fused route (its instantiation for 33 .. 63)
 SHAPES = [(1, 1, 1, 1), (63, 17, 2, 3), (65, 64, 5, 1), (130, 65, 3, 3), (200, 130, 17, 1), (66, 70, 15, 4), (70, 40, 16, 4), (66, 70, 12, 5),
-          (40, 150, 130, 1)]
-FUSED_SHAPES = [True, True, True, True, True, True, False, False, False]
+          (40, 150, 130, 1), (65, 70, 40, 1)]
+FUSED_SHAPES = [True, True, True, True, True, True, False, False, False, True]
 ROUTES = ["fused", "default", "rbf_fused=0"]
 ALPHA = 0.75
 

@@ -23,7 +23,7 @@ DT = {"f64": np.float64, "f32": np.float32}
 FACTOR = 64.0
 KINDS = [pk.SQEXP, pk.MATERN52]
 SHAPES = [(1, 1024, 1), (70, 1100, 3), (17, 4113, 17), (200, 2500, 64), (130, 1300, 16)]
-ROWS = [1, 5, 16, 33, 128]
+ROWS = [1, 5, 16, 20, 33, 128]
 
 
 def _pts(a, T, ld=None):
