@@ -13,6 +13,9 @@
 //   - resid_vec must hold iter_lim + 1 entries: the reference writes resid_vec[iter] after the loop (:127), one past its documented
 //     length (:28) when the limit is reached;
 //   - a trailing `int64_t* iters` (optional) returns the number of iterations run.
+// pcg_saddle_block (no counterpart in the reference): the same loop for s right-hand sides kept in lockstep over an operator with
+// the members matmat and normal_matmat (linops::DenseLinOp): one normal product and two products with M per iteration for all columns,
+// per-column scalars and stop flags on the device (rlhip_pcg_saddle_block_step_*), one host read of the s flags per iteration.
 //
 // pcg:
 // Everything n x s and s x s lives in device memory on G.q; the loop is the reference's, statement by statement (line numbers at the right),
@@ -30,6 +33,7 @@
 //     Any other callable is called as in the reference, after one more read per solve;
 //   - a trailing `int64_t* iters` (optional) returns k, the number of iterations started.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <iostream>
@@ -56,6 +60,13 @@ inline int step_d(blas::Queue& q, int64_t n, const double* r, const double* s, c
 inline int step_d(blas::Queue& q, int64_t n, const float* r, const float* s, const float* d1o, float* d1n, float* d) { return rlhip_pcg_saddle_step_d_f32(q.ctx(), n, r, s, d1o, d1n, d); }
 inline int axpby(blas::Queue& q, int64_t n, double a, const double* x, double b, double* y) { return rlhip_axpby_f64(q.ctx(), n, a, x, b, y); }
 inline int axpby(blas::Queue& q, int64_t n, float a, const float* x, float b, float* y) { return rlhip_axpby_f32(q.ctx(), n, a, x, b, y); }
+// the same three steps on n x s blocks in lockstep (rlhip_pcg_saddle_block_step_*)
+inline int block_step_xr(blas::Queue& q, int64_t n, int64_t s, const double* D, int64_t ldd, const double* Q, int64_t ldq, const double* dq, const double* d1, int64_t ldh, double* X, int64_t ldx, double* R, int64_t ldr, const int* act) { return rlhip_pcg_saddle_block_step_xr_f64(q.ctx(), n, s, D, ldd, Q, ldq, dq, d1, ldh, X, ldx, R, ldr, act); }
+inline int block_step_xr(blas::Queue& q, int64_t n, int64_t s, const float* D, int64_t ldd, const float* Q, int64_t ldq, const float* dq, const float* d1, int64_t ldh, float* X, int64_t ldx, float* R, int64_t ldr, const int* act) { return rlhip_pcg_saddle_block_step_xr_f32(q.ctx(), n, s, D, ldd, Q, ldq, dq, d1, ldh, X, ldx, R, ldr, act); }
+inline int block_step_refresh(blas::Queue& q, int64_t n, int64_t s, const double* B1, int64_t ldb1, const double* QX, int64_t ldqx, double delta, const double* X, int64_t ldx, double* R, int64_t ldr, const int* act) { return rlhip_pcg_saddle_block_step_refresh_f64(q.ctx(), n, s, B1, ldb1, QX, ldqx, delta, X, ldx, R, ldr, act); }
+inline int block_step_refresh(blas::Queue& q, int64_t n, int64_t s, const float* B1, int64_t ldb1, const float* QX, int64_t ldqx, float delta, const float* X, int64_t ldx, float* R, int64_t ldr, const int* act) { return rlhip_pcg_saddle_block_step_refresh_f32(q.ctx(), n, s, B1, ldb1, QX, ldqx, delta, X, ldx, R, ldr, act); }
+inline int block_step_d(blas::Queue& q, int64_t n, int64_t s, const double* R, int64_t ldr, const double* S, int64_t lds, const double* d1o, double* d1n, int64_t ldh, double* D, int64_t ldd, double tol, double* rel, int* act) { return rlhip_pcg_saddle_block_step_d_f64(q.ctx(), n, s, R, ldr, S, lds, d1o, d1n, ldh, D, ldd, tol, rel, act); }
+inline int block_step_d(blas::Queue& q, int64_t n, int64_t s, const float* R, int64_t ldr, const float* S, int64_t lds, const float* d1o, float* d1n, int64_t ldh, float* D, int64_t ldd, float tol, float* rel, int* act) { return rlhip_pcg_saddle_block_step_d_f32(q.ctx(), n, s, R, ldr, S, lds, d1o, d1n, ldh, D, ldd, tol, rel, act); }
 
 }  // namespace _saddle_impl
 
@@ -142,6 +153,111 @@ void pcg_saddle(int64_t m, int64_t n, const T* A, int64_t lda, const T* b, const
     randlapack_require(m >= 1 && n >= 1 && k >= 1) << "pcg_saddle needs m=" << m << ", n=" << n << ", k=" << k << " >= 1";
     linops::DenseLinOp<T> op(m, n, A, lda, Layout::ColMajor, q);
     pcg_saddle(op, b, c, delta, iter_lim, resid_vec, tol, k, M, ldm, x0, x, y, iters);
+}
+
+/// pcg_saddle for s right-hand sides in lockstep: column j runs exactly the recurrence of pcg_saddle on (b_j, c_j, x0_j) --
+/// the residual refresh on iter % 25 == 1 and the stop test delta_1j > (delta_1j^0 tol) tol included -- while all columns share each
+/// iteration's one normal product (A.normal_matmat: A is read once per chunk of columns on its one-pass route) and its two products with M.
+/// B: m x s (ldb); C: n x s (ldc; NULL: zero); resid: (iter_lim + 1) x s (ldr >= iter_lim + 1); M: n x k (ldm); X0: n x s (ldx0; NULL:
+/// zero); X: n x s (ldx); Y: m x s (ldy) -- all DEVICE, column-major.  iters: HOST, s entries, may be NULL.
+/// The loop runs while iter < iter_lim and some column is active.  A column that has met its stop test is frozen: its x_j, r_j and d_j no
+/// longer change, iters[j] is the number of iterations it ran, resid[0 .. iters[j], j] are written and the entries below them are left
+/// as they were.  A column whose delta_1j^0 is zero (a zero right-hand side) or NaN never starts: x_j = x0_j, iters[j] = 0.  At the end
+/// Y = B - A X for every column.  alpha_j, beta_j, delta_1j, d_j' q_j and rel_sq_tol_j never leave the device; the one host read of an
+/// iteration is that of the s flags active_j.
+/// A is anything with n_rows, n_cols, q and the two members matmat(trans, s, alpha, X, ldx, beta, Y, ldy) and
+/// normal_matmat(s, D, ldd, delta, Q, ldq, T, ldt, dq): linops::DenseLinOp (rl_linops.hh).
+template <typename T, typename LinOp>
+void pcg_saddle_block(LinOp& A, int64_t s, const T* B, int64_t ldb, const T* C, int64_t ldc, T delta, int64_t iter_lim, T* resid, int64_t ldr, T tol,
+                      int64_t k, const T* M, int64_t ldm, const T* X0, int64_t ldx0, T* X, int64_t ldx, T* Y, int64_t ldy, int64_t* iters = nullptr) {
+    namespace si = _saddle_impl;
+    const int64_t m = A.n_rows, n = A.n_cols;
+    blas::Queue& q = A.q;
+    const auto gen = lapack::MatrixType::General;
+    const auto layout = Layout::ColMajor;
+    randlapack_require(m >= 1 && n >= 1 && k >= 1) << "pcg_saddle_block needs m=" << m << ", n=" << n << ", k=" << k << " >= 1";
+    randlapack_require(s >= 0 && s <= 65535) << "s=" << s << " must lie in [0, 65535]";
+    randlapack_require(iter_lim >= 0) << "iter_lim=" << iter_lim << " must be >= 0";
+    randlapack_require(ldb >= m && ldy >= m && ldx >= n && ldm >= n && (!C || ldc >= n) && (!X0 || ldx0 >= n))
+        << "pcg_saddle_block: a leading dimension is below its row count";
+    randlapack_require(ldr >= iter_lim + 1) << "ldr=" << ldr << " must be >= iter_lim + 1 = " << iter_lim + 1;
+    if (s == 0) return;
+    std::vector<int64_t> its((size_t)s, 0);
+    if (iters) std::copy(its.begin(), its.end(), iters);
+
+    blas::Scratch ws(q);
+    T* allwork = ws.alloc<T>(5 * n * s + k * s + 2 * s);
+    T* out_at1 = allwork;                        // n x s: the normal product
+    T* R = out_at1 + n * s;
+    T* D = R + n * s;
+    T* B1 = D + n * s;
+    T* out_m1 = B1 + n * s;
+    T* out_mt1 = out_m1 + n * s;                 // k x s
+    T* dq = out_mt1 + k * s;                     // d_j' q_j of the current iteration
+    T* rel_sq_tol = dq + s;
+    int* active = ws.alloc<int>(s);
+    std::vector<int> act((size_t)s, 0);
+
+    // B1 = A'B - C
+    if (C) {
+        lapack::lacpy(gen, n, s, C, ldc, B1, n, q);
+        A.matmat(Op::Trans, s, (T)1.0, B, ldb, (T)-1.0, B1, n);
+    } else {
+        A.matmat(Op::Trans, s, (T)1.0, B, ldb, (T)0.0, B1, n);
+    }
+    if (X0) lapack::lacpy(gen, n, s, X0, ldx0, X, ldx, q);
+    else lapack::laset(gen, n, s, (T)0.0, (T)0.0, X, ldx, q);
+    // R = B1 - (A'(A X0) + delta X0)
+    blas::device_copy_vector(n * s, B1, R, q);
+    A.normal_matmat(s, X, ldx, delta, out_at1, n, (T*)nullptr, 0, (T*)nullptr);
+    blas::check(si::axpby(q, n * s, (T)-1.0, out_at1, (T)1.0, R), "axpby");
+    // D = M (M' R)
+    blas::gemm(layout, Op::Trans, Op::NoTrans, k, s, n, (T)1.0, M, ldm, R, n, (T)0.0, out_mt1, k, q);
+    blas::gemm(layout, Op::NoTrans, Op::NoTrans, n, s, k, (T)1.0, M, ldm, out_mt1, k, (T)0.0, D, n, q);
+    // resid[0, j] = d_j' r_j, rel_sq_tol_j and active_j
+    blas::check(si::block_step_d(q, n, s, R, n, D, n, (const T*)nullptr, resid, ldr, (T*)nullptr, n, tol, rel_sq_tol, active), "pcg_saddle_block_step_d");
+    blas::copy_to_host(s, active, act.data(), q);
+
+    int64_t iter = 0;
+    auto any_active = [&] {
+        for (int a : act)
+            if (a) return true;
+        return false;
+    };
+    while (iter < iter_lim && any_active()) {
+        for (int64_t j = 0; j < s; ++j) its[j] += act[j] ? 1 : 0;
+        // Q = A'(A D) + delta D, and d_j' q_j
+        A.normal_matmat(s, D, n, delta, out_at1, n, (T*)nullptr, 0, dq);
+        const bool refresh = iter % 25 == 1;
+        blas::check(si::block_step_xr(q, n, s, D, n, refresh ? (const T*)nullptr : out_at1, n, dq, resid + iter, ldr, X, ldx, R, n, active),
+                    "pcg_saddle_block_step_xr");
+        if (refresh) {
+            A.normal_matmat(s, X, ldx, (T)0.0, out_at1, n, (T*)nullptr, 0, (T*)nullptr);
+            blas::check(si::block_step_refresh(q, n, s, B1, n, out_at1, n, delta, X, ldx, R, n, active), "pcg_saddle_block_step_refresh");
+        }
+        // S = M (M' R)
+        blas::gemm(layout, Op::Trans, Op::NoTrans, k, s, n, (T)1.0, M, ldm, R, n, (T)0.0, out_mt1, k, q);
+        blas::gemm(layout, Op::NoTrans, Op::NoTrans, n, s, k, (T)1.0, M, ldm, out_mt1, k, (T)0.0, out_m1, n, q);
+        blas::check(si::block_step_d(q, n, s, R, n, out_m1, n, resid + iter, resid + iter + 1, ldr, D, n, tol, rel_sq_tol, active), "pcg_saddle_block_step_d");
+        ++iter;
+        blas::copy_to_host(s, active, act.data(), q);                            // the iteration's one host read
+    }
+    if (iters) std::copy(its.begin(), its.end(), iters);
+
+    // Y = B - A X
+    lapack::lacpy(gen, m, s, B, ldb, Y, ldy, q);
+    A.matmat(Op::NoTrans, s, (T)-1.0, X, ldx, (T)1.0, Y, ldy);
+    q.sync();                                    // (the work space goes back to the arena)
+}
+
+/// The same for a dense column-major A (m x n, lda, DEVICE).
+template <typename T>
+void pcg_saddle_block(int64_t m, int64_t n, const T* A, int64_t lda, int64_t s, const T* B, int64_t ldb, const T* C, int64_t ldc, T delta, int64_t iter_lim,
+                      T* resid, int64_t ldr, T tol, int64_t k, const T* M, int64_t ldm, const T* X0, int64_t ldx0, T* X, int64_t ldx, T* Y, int64_t ldy,
+                      blas::Queue& q = blas::default_queue(), int64_t* iters = nullptr) {
+    randlapack_require(m >= 1 && n >= 1 && k >= 1) << "pcg_saddle_block needs m=" << m << ", n=" << n << ", k=" << k << " >= 1";
+    linops::DenseLinOp<T> op(m, n, A, lda, Layout::ColMajor, q);
+    pcg_saddle_block(op, s, B, ldb, C, ldc, delta, iter_lim, resid, ldr, tol, k, M, ldm, X0, ldx0, X, ldx, Y, ldy, iters);
 }
 
 /// The Frobenius norm of a DEVICE block, every value kept (rl_determiter.hh:139-151).  pcg recognises this type and fills `history` from the

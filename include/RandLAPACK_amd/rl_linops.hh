@@ -7,7 +7,8 @@
 // sketching operator in place of B (Side::Right: C = alpha S op(A) + beta C -- how CQRRT_linops sketches, rl_cqrrt_linops.hh:200,207).
 // ABRIK (rl_abrik.hh:311,364,494) and the linop QR drivers (rl_qr_linops.hh) are templated over it.  All B / C are DEVICE pointers
 // and every operator carries the queue it runs on (member `q`).  DenseLinOp and SparseLinOp also have the two matrix-VECTOR members
-// pcg_saddle runs on (rl_determiter.hh): matvec (y = alpha op(A) x + beta y) and normal_matvec (q = A^T (A d) + delta d).
+// pcg_saddle runs on (rl_determiter.hh): matvec (y = alpha op(A) x + beta y) and normal_matvec (q = A^T (A d) + delta d).  DenseLinOp has
+// their block forms matmat and normal_matmat as well, which pcg_saddle_block runs on (several right-hand sides).
 //
 //   DenseLinOp        column-major device matrix; MFMA GEMM.  `row_sharded`: one row block per rank, A^T X and S A all-reduced.
 //   SparseLinOp       device CSR (+ the CSR of the transpose, built on first use); gather SpMM, csrc/sparse.hip.  Also built from CSC
@@ -88,6 +89,14 @@ inline void normal_matvec(int64_t m, int64_t n, const double* A, int64_t lda, co
 }
 inline void normal_matvec(int64_t m, int64_t n, const float* A, int64_t lda, const float* d, float delta, float* out, float* t, float* dq, blas::Queue& q) {
     blas::check(rlhip_normal_matvec_f32(q.ctx(), m, n, A, lda, d, delta, out, t, dq, 0), "normal_matvec");
+}
+inline void normal_matmat(int64_t m, int64_t n, int64_t s, const double* A, int64_t lda, const double* D, int64_t ldd, double delta, double* Q, int64_t ldq,
+                          double* T, int64_t ldt, double* dq, blas::Queue& q) {
+    blas::check(rlhip_normal_matmat_f64(q.ctx(), m, n, s, A, lda, D, ldd, delta, Q, ldq, T, ldt, dq, 0), "normal_matmat");
+}
+inline void normal_matmat(int64_t m, int64_t n, int64_t s, const float* A, int64_t lda, const float* D, int64_t ldd, float delta, float* Q, int64_t ldq,
+                          float* T, int64_t ldt, float* dq, blas::Queue& q) {
+    blas::check(rlhip_normal_matmat_f32(q.ctx(), m, n, s, A, lda, D, ldd, delta, Q, ldq, T, ldt, dq, 0), "normal_matmat");
 }
 inline void csr_spmv(int64_t nrows, int64_t ncols, int64_t nnz, const int64_t* rp, const int64_t* ci, const double* v, double al, const double* x, double be,
                      double* y, blas::Queue& q) {
@@ -195,6 +204,18 @@ struct DenseLinOp {
     void normal_matvec(const T* d, T delta, T* out, T* t, T* dq) {
         randlapack_require(!(row_sharded && q.world() > 1)) << "normal_matvec is not defined for a row-sharded operator";
         detail::normal_matvec(n_rows, n_cols, A_buff, lda, d, delta, out, t, dq, q);
+    }
+    /// The same two on blocks of s columns, the calls pcg_saddle_block makes: Y = alpha op(A) X + beta Y (blas::gemm) and
+    /// Q (n_cols x s) = A^T (A D) + delta D with T = A D (n_rows x s) and dq[j] = D_j^T Q_j optional (rlhip_normal_matmat_*: A read once per
+    /// chunk of columns on its one-pass route).  Not defined for a row-sharded operator either.
+    void matmat(Op trans, int64_t s, T alpha, const T* X, int64_t ldx, T beta, T* Y, int64_t ldy) {
+        randlapack_require(!(row_sharded && q.world() > 1)) << "matmat is not defined for a row-sharded operator";
+        const bool nt = trans == Op::NoTrans;
+        blas::gemm(Layout::ColMajor, trans, Op::NoTrans, nt ? n_rows : n_cols, s, nt ? n_cols : n_rows, alpha, A_buff, lda, X, ldx, beta, Y, ldy, q);
+    }
+    void normal_matmat(int64_t s, const T* D, int64_t ldd, T delta, T* Q, int64_t ldq, T* Tm, int64_t ldt, T* dq) {
+        randlapack_require(!(row_sharded && q.world() > 1)) << "normal_matmat is not defined for a row-sharded operator";
+        detail::normal_matmat(n_rows, n_cols, s, A_buff, lda, D, ldd, delta, Q, ldq, Tm, ldt, dq, q);
     }
 
     // ---- block views (rl_dense_linop.hh:295-330): non-owning, same storage, same queue

@@ -1,9 +1,11 @@
 // Sketch-and-precondition least squares on the device: sap_lstsq chains rpc_data_svd_saso, make_right_orthogonalizer and pcg_saddle.
 // This is the one function of the solver layer WITHOUT a counterpart in the reference, whose tests chain the three by hand
-// (test/comps/test_determiter.cc, test_preconditioners.cc and the pcgls helper built on them).
+// (test/comps/test_determiter.cc, test_preconditioners.cc and the pcgls helper built on them).  The overload with s right-hand sides builds
+// the preconditioner once and runs pcg_saddle_block: s conjugate-gradient iterations in lockstep on one normal product.
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <vector>
 #include "rl_exceptions.hh"
 #include "rl_blaspp.hh"
 #include "rl_randblas.hh"
@@ -40,6 +42,38 @@ SapLstsqResult sap_lstsq(int64_t m, int64_t n, const T* A, int64_t lda, const T*
     randlapack_require(out.rank >= 1) << "sap_lstsq: the sketch of A has numerical rank 0";
     blas::device_memset(x0, 0, n, q);
     pcg_saddle(m, n, A, lda, b, c, delta, iter_lim, resid, tol, out.rank, V_sk, n, x0, x, y, q, &out.iters);
+    return out;
+}
+
+struct SapLstsqBlockResult {
+    int64_t rank = 0;              // columns of the orthogonalizer M
+    std::vector<int64_t> iters;    // pcg_saddle_block iterations each column ran
+};
+
+/// The same for s right-hand sides: B, Y: m x s (ldb, ldy); C: n x s (ldc; NULL: zero); X: n x s (ldx); resid (DEVICE,
+/// (iter_lim + 1) x s with stride iter_lim + 1; may be NULL) receives the residual histories.  ONE rpc_data_svd_saso and one
+/// make_right_orthogonalizer serve all columns -- `state` is advanced exactly as the single-column call advances it -- then
+/// pcg_saddle_block runs from X0 = 0: one normal product per iteration for all columns.
+template <typename T, typename RNG>
+SapLstsqBlockResult sap_lstsq(int64_t m, int64_t n, const T* A, int64_t lda, int64_t s, const T* B, int64_t ldb, const T* C, int64_t ldc, T delta,
+                              T d_factor, int64_t nnz, T tol, int64_t iter_lim, T* X, int64_t ldx, T* Y, int64_t ldy, RandBLAS::RNGState<RNG>& state,
+                              blas::Queue& q = blas::default_queue(), T* resid = nullptr) {
+    randlapack_require(m >= n && n >= 1) << "sap_lstsq needs m=" << m << " >= n=" << n << " >= 1";
+    randlapack_require(s >= 0) << "s=" << s << " must be >= 0";
+    randlapack_require(d_factor >= (T)1.0) << "d_factor=" << d_factor << " must be >= 1";
+    randlapack_require(iter_lim >= 0) << "iter_lim=" << iter_lim << " must be >= 0";
+    int64_t d = (int64_t)std::ceil((double)d_factor * (double)n);
+    blas::Scratch ws(q);
+    T* V_sk = ws.alloc<T>(d * n);
+    T* sigma_sk = ws.alloc<T>(n);
+    T* res = resid ? resid : ws.alloc<T>((iter_lim + 1) * (s > 0 ? s : 1));
+    state = rpc_data_svd_saso(Layout::ColMajor, m, n, d, nnz, A, lda, V_sk, sigma_sk, state, q);
+    SapLstsqBlockResult out;
+    out.rank = make_right_orthogonalizer(Layout::ColMajor, n, V_sk, sigma_sk, delta, n, q);
+    randlapack_require(out.rank >= 1) << "sap_lstsq: the sketch of A has numerical rank 0";
+    out.iters.assign((size_t)s, 0);
+    pcg_saddle_block(m, n, A, lda, s, B, ldb, C, ldc, delta, iter_lim, res, iter_lim + 1, tol, out.rank, (const T*)V_sk, n, (const T*)nullptr, n, X, ldx, Y,
+                     ldy, q, out.iters.data());
     return out;
 }
 

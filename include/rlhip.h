@@ -664,6 +664,77 @@ int rlhip_pcg_saddle_step_d_f32(rlhip_ctx* ctx, int64_t n, const float* r, const
  * well), 48 rlhip_gemv 'N', 49 rlhip_gemv 'T' (calls that launch nothing are not counted).  -1 for any other index. */
 int64_t rlhip_lsq_path_count(rlhip_ctx* ctx, int which);
 
+/* ---- least squares with several right-hand sides (lsq_block.hip): the hot path of RandLAPACK::pcg_saddle_block (rl_determiter.hh;
+ *      DESIGN 4.31).  Column-major DEVICE operands with leading dimensions; the rules of the layer above hold (no workgroup waits for
+ *      another, no floating-point atomic, static slabs, partials in the scratch arena and a final pass in a fixed order), and on top of them
+ *      COLUMN INDEPENDENCE: column j of every output is a function of A, delta and column j of the inputs alone; for given sizes, max_wg and
+ *      route its bits do not depend on what the other columns hold.  Column j of a call with s > 1 need not have rlhip_normal_matvec's bits. ---- */
+/* rlhip_normal_matmat_*: Q (n x s, ldq) = A^T (A D) + delta D for D n x s (ldd).  Optional outputs, each may be NULL: T = A D (m x s, ldt)
+ * and dq_dev[j] = D(:, j)^T Q(:, j) (s values, each by one workgroup in the order of rlhip_normal_matvec's d^T q).
+ * One-pass route, n <= RLHIP_NORMAL_MATMAT_FUSED_MAX_N: the slab walk of the fused rlhip_normal_matvec (G = min(max_wg, slabs) workgroups of
+ * 1024 threads, max_wg <= 0: one per CU; workgroup b walks the R-row slabs b, b + G, ...), the staged slab S used for a chunk of sc columns
+ * at once: T_slab (R x sc) = S D, then the workgroup's partial Q (n x sc) += S^T T_slab, while the next slab is on its way into registers.
+ * A is read from memory once per chunk; s columns take ceil(s / sc) passes.  A slab holds at most 64 KiB (R the largest power of two between
+ * 16 and 256 with R n sizeof(T) <= 64 KiB) so that D, the shares of T_slab and T_slab fit beside it; sc is at most
+ * RLHIP_NORMAL_MATMAT_FUSED_SC_F64 / _F32.  Composed route (every other shape): T = A D and Q = A^T T through rlhip_gemm_*
+ * (T in scratch when the caller passes NULL), then Q += delta D; two passes over A.
+ * The route: unasked, the one-pass route serves the shapes where it measured faster than both the composed route and s calls of
+ * rlhip_normal_matvec: 2 <= s <= 8 with 33 <= n <= 256 in fp64, 129 <= n <= 256 in fp32 (rlhip_normal_matmat_default);
+ * rlhip_normal_matmat_set_route(ctx, 1) takes it wherever rlhip_normal_matmat_fused(...) != 0, 0 never, -1 restores the default.
+ * m == 0: Q = delta D.  n == 0 or s == 0: returns 0 and writes nothing.  Rows m .. lda - 1 of A are never read; nothing is written beyond
+ * column s - 1 or beyond row n - 1 (Q), m - 1 (T) of an output.
+ * Argument codes, checked before anything is enqueued: -1 ctx NULL, -2 m < 0, -3 n < 0, -4 s < 0, -5 A NULL (m, n, s > 0), -6 lda < max(1, m),
+ * -7 D NULL (n, s > 0), -8 ldd < max(1, n), -10 Q NULL (n, s > 0), -11 ldq < max(1, n), -13 ldt < max(1, m) with T given. */
+#define RLHIP_NORMAL_MATMAT_FUSED_MAX_N 512
+#define RLHIP_NORMAL_MATMAT_FUSED_SC_F64 4
+#define RLHIP_NORMAL_MATMAT_FUSED_SC_F32 4
+int rlhip_normal_matmat_f64(rlhip_ctx* ctx, int64_t m, int64_t n, int64_t s, const double* A, int64_t lda, const double* D, int64_t ldd, double delta,
+                            double* Q, int64_t ldq, double* T, int64_t ldt, double* dq_dev, int64_t max_wg);
+int rlhip_normal_matmat_f32(rlhip_ctx* ctx, int64_t m, int64_t n, int64_t s, const float* A, int64_t lda, const float* D, int64_t ldd, float delta,
+                            float* Q, int64_t ldq, float* T, int64_t ldt, float* dq_dev, int64_t max_wg);
+/* The chunk width the one-pass route uses for n columns of A, s right-hand sides and elements of elem_bytes (8 or 4) bytes:
+ * min(s, RLHIP_NORMAL_MATMAT_FUSED_SC_*) for 1 <= n <= RLHIP_NORMAL_MATMAT_FUSED_MAX_N and s >= 1, else 0.  A function of the shape alone. */
+int rlhip_normal_matmat_fused(int64_t n, int64_t s, int elem_bytes);
+/* 1 where rlhip_normal_matmat_* takes its one-pass route unasked (the measured ranges above), else 0.  A function of the shape alone. */
+int rlhip_normal_matmat_default(int64_t n, int64_t s, int elem_bytes);
+/* route: -1 the default, 0 always the composed route, > 0 the one-pass route wherever rlhip_normal_matmat_fused(...) != 0.  Returns the
+ * value found (-1, 0 or 1), -1 for a NULL context. */
+int rlhip_normal_matmat_set_route(rlhip_ctx* ctx, int route);
+/* The three vector steps of rlhip_pcg_saddle_step_* over n x s blocks in lockstep.  Per-column scalars stay on the device: dq_dev (s),
+ * rel_sq_tol_dev (s), the flags active_dev (s ints) and the residual histories, one column of (at least) iter_lim + 1 entries each with
+ * stride ldh: the loop passes resid + iter as delta1_dev / delta1_old_dev and resid + iter + 1 as delta1_new_dev, so column j's scalar is
+ * at [j * ldh].  A column whose flag is 0 is not touched by any step.
+ * step_xr: alpha_j = delta1_j / dq_j, X_j += alpha_j D_j, R_j -= alpha_j Q_j (Q == NULL leaves R alone).  Codes: -1 ctx, -2 n < 0, -3 s < 0
+ *   or > 65535, -4 D, -5 ldd, -7 ldq (Q given), -8 dq_dev, -9 delta1_dev, -10 ldh < 1, -11 X, -12 ldx, -13 R NULL with Q given, -14 ldr
+ *   (Q given), -15 active_dev.
+ * step_refresh: R_j = (B1_j - QX_j) - delta X_j, the last term only when delta > 0.  Codes: -1 ctx, -2 n, -3 s, -4 B1, -5 ldb1, -6 QX,
+ *   -7 ldqx, -9 X, -10 ldx, -11 R, -12 ldr, -13 active_dev.
+ * step_d: one workgroup per column: delta1_new_j = R_j^T S_j (fixed order), written to the column's history; beta_j = that / delta1_old_j,
+ *   D_j = beta_j D_j + S_j; active_j is cleared when delta1_new_j > rel_sq_tol_j is false (so a NaN clears it).  delta1_old_dev == NULL is
+ *   the first call: the dot alone for EVERY column, rel_sq_tol_j = (delta1_j tol) tol is formed and active_j set from the same test whatever
+ *   it held.  Codes: -1 ctx, -2 n, -3 s, -4 R, -5 ldr, -6 S, -7 lds, -9 delta1_new_dev, -10 ldh < 1, -11 D NULL, -12 ldd (both with
+ *   delta1_old_dev given), -14 rel_sq_tol_dev, -15 active_dev.
+ * The pointer codes only when n > 0 and s > 0; n == 0 or s == 0: each returns 0 and enqueues nothing. */
+int rlhip_pcg_saddle_block_step_xr_f64(rlhip_ctx* ctx, int64_t n, int64_t s, const double* D, int64_t ldd, const double* Q, int64_t ldq,
+                                       const double* dq_dev, const double* delta1_dev, int64_t ldh, double* X, int64_t ldx, double* R, int64_t ldr,
+                                       const int* active_dev);
+int rlhip_pcg_saddle_block_step_xr_f32(rlhip_ctx* ctx, int64_t n, int64_t s, const float* D, int64_t ldd, const float* Q, int64_t ldq,
+                                       const float* dq_dev, const float* delta1_dev, int64_t ldh, float* X, int64_t ldx, float* R, int64_t ldr,
+                                       const int* active_dev);
+int rlhip_pcg_saddle_block_step_refresh_f64(rlhip_ctx* ctx, int64_t n, int64_t s, const double* B1, int64_t ldb1, const double* QX, int64_t ldqx,
+                                            double delta, const double* X, int64_t ldx, double* R, int64_t ldr, const int* active_dev);
+int rlhip_pcg_saddle_block_step_refresh_f32(rlhip_ctx* ctx, int64_t n, int64_t s, const float* B1, int64_t ldb1, const float* QX, int64_t ldqx,
+                                            float delta, const float* X, int64_t ldx, float* R, int64_t ldr, const int* active_dev);
+int rlhip_pcg_saddle_block_step_d_f64(rlhip_ctx* ctx, int64_t n, int64_t s, const double* R, int64_t ldr, const double* S, int64_t lds,
+                                      const double* delta1_old_dev, double* delta1_new_dev, int64_t ldh, double* D, int64_t ldd, double tol,
+                                      double* rel_sq_tol_dev, int* active_dev);
+int rlhip_pcg_saddle_block_step_d_f32(rlhip_ctx* ctx, int64_t n, int64_t s, const float* R, int64_t ldr, const float* S, int64_t lds,
+                                      const float* delta1_old_dev, float* delta1_new_dev, int64_t ldh, float* D, int64_t ldd, float tol,
+                                      float* rel_sq_tol_dev, int* active_dev);
+/* The routes of this layer: 76 rlhip_normal_matmat calls on the one-pass route, 77 on the composed route (calls that reach neither are not
+ * counted), 78 iterations of the block solver (step_d calls with delta1_old_dev given).  -1 for any other index and for a NULL context. */
+int64_t rlhip_lsq_block_path_count(rlhip_ctx* ctx, int which);
+
 /* ---- sparse matrix-vector layer (spmv.hip): the hot path of pcg_saddle on a linops::SparseLinOp.  CSR with int64 indices,
  *      all arrays DEVICE, everything asynchronous, no host read: nnz (= rowptr[nrows]) is an ARGUMENT.  The rules are those of the dense
  *      layer above: no workgroup waits for another, no floating-point atomic, results bitwise reproducible and independent of the grid and

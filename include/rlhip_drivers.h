@@ -424,6 +424,27 @@ int rlhip_drv_sap_lstsq_f64(rlhip_ctx* ctx, int64_t m, int64_t n, const double* 
 int rlhip_drv_sap_lstsq_f32(rlhip_ctx* ctx, int64_t m, int64_t n, const float* A, int64_t lda, const float* b, const float* c, float delta,
                             float d_factor, int64_t nnz, float tol, int64_t iter_lim, float* x, float* y, float* resid_vec, uint32_t state[6],
                             int64_t* rank, int64_t* iters);
+/* pcg_saddle_block and the sap_lstsq overload with s right-hand sides (include/RandLAPACK_amd/rl_determiter.hh, rl_lstsq.hh; no
+ * reference counterpart): column j runs pcg_saddle's recurrence on (B_j, C_j, X0_j) while all columns share each iteration's one normal product
+ * (rlhip_normal_matmat_*).  B, Y: m x s (ldb, ldy); C: n x s (ldc; NULL: zero); X0: n x s (ldx0; NULL: zero); X: n x s (ldx); resid:
+ * (iter_lim + 1) x s with stride ldr >= iter_lim + 1 (sap_lstsq_block: stride iter_lim + 1, may be NULL) -- all DEVICE.  iters (HOST, s entries,
+ * may be NULL): iterations each column ran; resid[0 .. iters[j], j] are written, the entries below them are left as they were.  s == 0
+ * returns 0 and writes nothing (sap_lstsq_block still advances state[6]).  sap_lstsq_block builds ONE preconditioner for all columns and
+ * advances state[6] as rlhip_drv_sap_lstsq_* does.  -100 with rlhip_last_error() on a refused argument, a row-sharded context included. */
+int rlhip_drv_pcg_saddle_block_f64(rlhip_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda, int64_t s, const double* B, int64_t ldb,
+                                   const double* C, int64_t ldc, double delta, int64_t iter_lim, double* resid, int64_t ldr, double tol, int64_t k,
+                                   const double* M, int64_t ldm, const double* X0, int64_t ldx0, double* X, int64_t ldx, double* Y, int64_t ldy,
+                                   int64_t* iters);
+int rlhip_drv_pcg_saddle_block_f32(rlhip_ctx* ctx, int64_t m, int64_t n, const float* A, int64_t lda, int64_t s, const float* B, int64_t ldb,
+                                   const float* C, int64_t ldc, float delta, int64_t iter_lim, float* resid, int64_t ldr, float tol, int64_t k,
+                                   const float* M, int64_t ldm, const float* X0, int64_t ldx0, float* X, int64_t ldx, float* Y, int64_t ldy,
+                                   int64_t* iters);
+int rlhip_drv_sap_lstsq_block_f64(rlhip_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda, int64_t s, const double* B, int64_t ldb,
+                                  const double* C, int64_t ldc, double delta, double d_factor, int64_t nnz, double tol, int64_t iter_lim, double* X,
+                                  int64_t ldx, double* Y, int64_t ldy, double* resid, uint32_t state[6], int64_t* rank, int64_t* iters);
+int rlhip_drv_sap_lstsq_block_f32(rlhip_ctx* ctx, int64_t m, int64_t n, const float* A, int64_t lda, int64_t s, const float* B, int64_t ldb,
+                                  const float* C, int64_t ldc, float delta, float d_factor, int64_t nnz, float tol, int64_t iter_lim, float* X,
+                                  int64_t ldx, float* Y, int64_t ldy, float* resid, uint32_t state[6], int64_t* rank, int64_t* iters);
 /* The three entries above over an operator descriptor (rlhip_linop_desc, above) in place of (A, lda); m = left->rows, n = left->cols.  Kind 0
  * runs the dense entry; kinds 1, 2, 3 (CSR, CSC, COO) a linops::SparseLinOp: the sketch is the operator's scatter over its nonzeros, every product
  * of the iteration a sparse matrix-vector product (rlhip_csr_spmv_*, rlhip_csr_normal_matvec_*), and A is never densified.  The sign operator, and

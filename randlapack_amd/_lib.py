@@ -312,6 +312,22 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the regularization path
                                                               c_vp, c_i64, i64p, _dp, _dp, _dp, i64p, _dp]),
     })
 
+# least squares with several right-hand sides (lsq_block.hip, rl_determiter.hh pcg_saddle_block, rl_lstsq.hh)
+SIGNATURES["rlhip_normal_matmat_fused"] = (c_int, [c_i64, c_i64, c_int])
+SIGNATURES["rlhip_normal_matmat_default"] = (c_int, [c_i64, c_i64, c_int])
+SIGNATURES["rlhip_normal_matmat_set_route"] = (c_int, [c_vp, c_int])
+SIGNATURES["rlhip_lsq_block_path_count"] = (c_i64, [c_vp, c_int])
+for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):
+    SIGNATURES.update({
+        f"rlhip_normal_matmat_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, _T, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64]),
+        f"rlhip_pcg_saddle_block_step_xr_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+        f"rlhip_pcg_saddle_block_step_refresh_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, _T, c_vp, c_i64, c_vp, c_i64, c_vp]),
+        f"rlhip_pcg_saddle_block_step_d_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, _T, c_vp, c_vp]),
+        f"rlhip_drv_pcg_saddle_block_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, _T, c_i64, c_vp, c_i64, _T, c_i64,
+                                                      c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, i64p]),
+        f"rlhip_drv_sap_lstsq_block_{_suf}": (c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, _T, _T, c_i64, _T, c_i64, c_vp,
+                                                     c_i64, c_vp, c_i64, c_vp, u32p, i64p, i64p]),
+    })
 SIGNATURES["rlhip_pdk_var_fused"] = (c_int, [c_i64, c_i64, c_i64])      # the shape rule of the fused variance kernel
 SIGNATURES["rlhip_pdk_var_path_count"] = (c_i64, [c_vp, c_int])
 SIGNATURES["rlhip_pdk_var_set_fused"] = (c_int, [c_vp, c_int])

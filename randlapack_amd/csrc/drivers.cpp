@@ -1228,6 +1228,43 @@ int drv_sap_lstsq(rlhip_ctx* ctx, int64_t m, int64_t n, const T* A, int64_t lda,
         return 0;
     });
 }
+// s right-hand sides.  A context with more than one rank holds a row block of A: refused, as the operator forms below refuse it.
+template <typename T>
+int drv_pcg_saddle_block(rlhip_ctx* ctx, int64_t m, int64_t n, const T* A, int64_t lda, int64_t s, const T* B, int64_t ldb, const T* C, int64_t ldc, T delta,
+                         int64_t iter_lim, T* resid, int64_t ldr, T tol, int64_t k, const T* M, int64_t ldm, const T* X0, int64_t ldx0, T* X, int64_t ldx, T* Y,
+                         int64_t ldy, int64_t* iters) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (s < 0) throw RandLAPACK::Error("pcg_saddle_block: s must be >= 0");
+        if (!A || !M || (s > 0 && (!B || !resid || !X || !Y))) throw RandLAPACK::Error("pcg_saddle_block: A, B, resid, M, X and Y must not be null");
+        if (lda < m || ldm < n) throw RandLAPACK::Error("pcg_saddle_block: lda must be >= m and ldm >= n");
+        if (!(tol > (T)0) || !(delta >= (T)0)) throw RandLAPACK::Error("pcg_saddle_block: tol must be > 0 and delta >= 0");
+        if (m < 1 || n < 1 || k < 1) throw RandLAPACK::Error("pcg_saddle_block: m, n and k must be >= 1");
+        lo::DenseLinOp<T> op(m, n, A, lda, RandLAPACK::Layout::ColMajor, q);
+        op.row_sharded = q.world() > 1;
+        RandLAPACK::pcg_saddle_block(op, s, B, ldb, C, ldc, delta, iter_lim, resid, ldr, tol, k, M, ldm, X0, ldx0, X, ldx, Y, ldy, iters);
+        return 0;
+    });
+}
+template <typename T>
+int drv_sap_lstsq_block(rlhip_ctx* ctx, int64_t m, int64_t n, const T* A, int64_t lda, int64_t s, const T* B, int64_t ldb, const T* C, int64_t ldc, T delta,
+                        T d_factor, int64_t nnz, T tol, int64_t iter_lim, T* X, int64_t ldx, T* Y, int64_t ldy, T* resid, uint32_t state[6], int64_t* rank,
+                        int64_t* iters) {
+    return guarded([&] {
+        blas::Queue q(ctx);
+        if (s < 0) throw RandLAPACK::Error("sap_lstsq: s must be >= 0");
+        if (!A || !state || (s > 0 && (!B || !X || !Y))) throw RandLAPACK::Error("sap_lstsq: A, B, X, Y and state must not be null");
+        if (lda < m) throw RandLAPACK::Error("sap_lstsq: lda must be >= m");
+        if (!(tol > (T)0) || !(delta >= (T)0) || nnz < 1) throw RandLAPACK::Error("sap_lstsq: tol must be > 0, delta >= 0 and nnz >= 1");
+        if (q.world() > 1) throw RandLAPACK::Error("sap_lstsq with several right-hand sides is not defined for a row-sharded operator");
+        State st = load_state(state);
+        const auto r = RandLAPACK::sap_lstsq(m, n, A, lda, s, B, ldb, C, ldc, delta, d_factor, nnz, tol, iter_lim, X, ldx, Y, ldy, st, q, resid);
+        store_state(st, state);
+        if (rank) *rank = r.rank;
+        if (iters) std::copy(r.iters.begin(), r.iters.end(), iters);
+        return 0;
+    });
+}
 
 // the same three over an operator descriptor: kind 0 runs the dense entry above, kinds 1, 2, 3 a linops::SparseLinOp; a composite is refused
 inline void check_lsq_operator(const rlhip_linop_desc* left, const rlhip_linop_desc* right, const char* who) {
@@ -1326,6 +1363,21 @@ extern "C" {
                                         int64_t* rank, int64_t* iters) {                                                                          \
         return drv_sap_lstsq_linop<T>(ctx, left, right, b, c, delta, d_factor, nnz, tol, iter_lim, x, y, resid_vec, state, rank, iters);          \
     }
+#define RLHIP_DEFINE_LSQ_BLOCK_DRIVERS(SUF, T)                                                                                                    \
+    int rlhip_drv_pcg_saddle_block_##SUF(rlhip_ctx* ctx, int64_t m, int64_t n, const T* A, int64_t lda, int64_t s, const T* B, int64_t ldb,       \
+                                         const T* C, int64_t ldc, T delta, int64_t iter_lim, T* resid, int64_t ldr, T tol, int64_t k, const T* M, \
+                                         int64_t ldm, const T* X0, int64_t ldx0, T* X, int64_t ldx, T* Y, int64_t ldy, int64_t* iters) {          \
+        return drv_pcg_saddle_block<T>(ctx, m, n, A, lda, s, B, ldb, C, ldc, delta, iter_lim, resid, ldr, tol, k, M, ldm, X0, ldx0, X, ldx, Y,    \
+                                       ldy, iters);                                                                                               \
+    }                                                                                                                                             \
+    int rlhip_drv_sap_lstsq_block_##SUF(rlhip_ctx* ctx, int64_t m, int64_t n, const T* A, int64_t lda, int64_t s, const T* B, int64_t ldb,        \
+                                        const T* C, int64_t ldc, T delta, T d_factor, int64_t nnz, T tol, int64_t iter_lim, T* X, int64_t ldx,    \
+                                        T* Y, int64_t ldy, T* resid, uint32_t state[6], int64_t* rank, int64_t* iters) {                          \
+        return drv_sap_lstsq_block<T>(ctx, m, n, A, lda, s, B, ldb, C, ldc, delta, d_factor, nnz, tol, iter_lim, X, ldx, Y, ldy, resid, state,    \
+                                      rank, iters);                                                                                               \
+    }
+RLHIP_DEFINE_LSQ_BLOCK_DRIVERS(f64, double)
+RLHIP_DEFINE_LSQ_BLOCK_DRIVERS(f32, float)
 RLHIP_DEFINE_LSQ_DRIVERS(f64, double)
 RLHIP_DEFINE_LSQ_DRIVERS(f32, float)
 }  // extern "C"

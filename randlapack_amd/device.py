@@ -198,6 +198,25 @@ class Context:
         """routes of the matrix-vector layer: 46 fused normal matvec, 47 composed, 48 gemv 'N', 49 gemv 'T' (include/rlhip.h rlhip_lsq_path_count)"""
         return int(self.lib.rlhip_lsq_path_count(self.h, which))
 
+    def lsq_block_path_count(self, which: int) -> int:
+        """routes of the block least-squares layer: 76 one-pass normal matmat, 77 composed, 78 pcg_saddle_block iterations (include/rlhip.h
+        rlhip_lsq_block_path_count)"""
+        return int(self.lib.rlhip_lsq_block_path_count(self.h, which))
+
+    def normal_matmat_route(self, route: int = 1):
+        """context manager: the route of rlhip_normal_matmat_* on this context (rlhip_normal_matmat_set_route): 1 the one-pass kernel where
+        the shape allows, 0 always the composed route, -1 the default; the value found is put back"""
+        import contextlib
+
+        @contextlib.contextmanager
+        def _cm():
+            was = int(self.lib.rlhip_normal_matmat_set_route(self.h, int(route)))
+            try:
+                yield self
+            finally:
+                self.lib.rlhip_normal_matmat_set_route(self.h, was)
+        return _cm()
+
     def spmv_path_count(self, which: int) -> int:
         """routes of the sparse matrix-vector layer: 50 / 51 / 52 a product with 4 / 16 / 64 lanes per row, 53 the split long-row route,
         54 csr_normal_matvec calls (include/rlhip.h rlhip_spmv_path_count)"""
@@ -1555,6 +1574,69 @@ def sap_lstsq(ctx: Context, A, m, n, b, c, delta, d_factor, nnz, tol, iter_lim, 
     _drv_check(ctx, rc, "sap_lstsq")
     it = int(iters.value)
     return dict(x=x, y=y, rank=int(rank.value), iters=it, resid=resid[: it + 1].cpu().numpy(), next_ctr=tuple(int(v) for v in st[:4]))
+
+
+# ---- several right-hand sides (lsq_block.hip, rl_determiter.hh pcg_saddle_block, rl_lstsq.hh).  A block of s vectors is a
+#      column-major tensor (s, ld) like a matrix.
+def normal_matmat_fused(n, s, elem_bytes):
+    """the chunk width rlhip_normal_matmat_*'s one-pass route uses for this shape, 0 outside its limits (no device needed)"""
+    return int(_lib.load().rlhip_normal_matmat_fused(n, s, elem_bytes))
+
+
+def normal_matmat_default(n, s, elem_bytes):
+    """1 where rlhip_normal_matmat_* takes its one-pass route unasked (the ranges in which it measured faster), else 0 (no device needed)"""
+    return int(_lib.load().rlhip_normal_matmat_default(n, s, elem_bytes))
+
+
+def normal_matmat(ctx: Context, m, n, s, A, D, delta, Q, T=None, want_dq=False, max_wg=0, lda=None, ldd=None, ldq=None, ldt=None):
+    """Q = A^T (A D) + delta D on s columns (rlhip_normal_matmat_*); T (optional, m x s) receives A D.  Returns the s values d_j^T q_j as a
+    device tensor when want_dq, else None."""
+    torch = _torch()
+    suf, _ = _suf(Q)
+    dq = torch.zeros(max(s, 1), dtype=Q.dtype, device=Q.device) if want_dq else None
+    rc = getattr(ctx.lib, f"rlhip_normal_matmat_{suf}")(ctx.h, m, n, s, _ptr(A), _ldc(A) if lda is None else lda, _ptr(D), _ldc(D) if ldd is None else ldd,
+                                                       delta, _ptr(Q), _ldc(Q) if ldq is None else ldq, _ptr(T),
+                                                       (_ldc(T) if T is not None else max(m, 1)) if ldt is None else ldt, _ptr(dq), max_wg)
+    _lib.check(rc, "normal_matmat")
+    return None if dq is None else dq[:s]
+
+
+def pcg_saddle_block(ctx: Context, A, m, n, s, B, Cm, delta, iter_lim, tol, M, k, X0=None, lda=None, ldm=None, resid=None):
+    """pcg_saddle_block on DEVICE operands: B (s, ldb), Cm (s, ldc) or None, X0 (s, ldx0) or None.  resid (optional): a device tensor
+    (s, iter_lim + 1) that receives the residual histories (entries a column does not reach are left as they are).
+    Returns dict(x (s, n), y (s, m), iters (list), resid (numpy (s, iter_lim + 1)))."""
+    torch = _torch()
+    suf, _ = _suf(A)
+    X = torch.zeros((max(s, 1), n), dtype=A.dtype, device=A.device)
+    Y = torch.zeros((max(s, 1), m), dtype=A.dtype, device=A.device)
+    if resid is None:
+        resid = torch.full((max(s, 1), iter_lim + 1), float("nan"), dtype=A.dtype, device=A.device)
+    iters = (C.c_int64 * max(s, 1))()
+    rc = getattr(ctx.lib, f"rlhip_drv_pcg_saddle_block_{suf}")(ctx.h, m, n, A.data_ptr(), _ldc(A) if lda is None else lda, s, _ptr(B),
+                                                              _ldc(B) if B is not None else m, _ptr(Cm), _ldc(Cm) if Cm is not None else n, delta, iter_lim, resid.data_ptr(), _ldc(resid), tol, k,
+                                                              M.data_ptr(), _ldc(M) if ldm is None else ldm, _ptr(X0), _ldc(X0) if X0 is not None else n,
+                                                              X.data_ptr(), n, Y.data_ptr(), m, iters)
+    _drv_check(ctx, rc, "pcg_saddle_block")
+    return dict(x=X[:s], y=Y[:s], iters=[int(v) for v in iters[:s]], resid=resid[:s].cpu().numpy())
+
+
+def sap_lstsq_block(ctx: Context, A, m, n, s, B, Cm, delta, d_factor, nnz, tol, iter_lim, ctr=(0, 0, 0, 0), key=(0, 0), lda=None):
+    """sap_lstsq with s right-hand sides: one preconditioner, pcg_saddle_block from X0 = 0.  B (s, ldb), Cm (s, ldc) or None.
+    Returns dict(x (s, n), y (s, m), rank, iters (list), resid (numpy (s, iter_lim + 1), NaN where a column did not reach), next_ctr)."""
+    torch = _torch()
+    suf, _ = _suf(A)
+    X = torch.zeros((max(s, 1), n), dtype=A.dtype, device=A.device)
+    Y = torch.zeros((max(s, 1), m), dtype=A.dtype, device=A.device)
+    resid = torch.full((max(s, 1), iter_lim + 1), float("nan"), dtype=A.dtype, device=A.device)
+    st = _state_arr(ctr, key)
+    rank = C.c_int64(0)
+    iters = (C.c_int64 * max(s, 1))()
+    rc = getattr(ctx.lib, f"rlhip_drv_sap_lstsq_block_{suf}")(ctx.h, m, n, A.data_ptr(), _ldc(A) if lda is None else lda, s, _ptr(B),
+                                                             _ldc(B) if B is not None else m, _ptr(Cm), _ldc(Cm) if Cm is not None else n, delta, d_factor,
+                                                             nnz, tol, iter_lim, X.data_ptr(), n, Y.data_ptr(), m, resid.data_ptr(), st, C.byref(rank), iters)
+    _drv_check(ctx, rc, "sap_lstsq_block")
+    return dict(x=X[:s], y=Y[:s], rank=int(rank.value), iters=[int(v) for v in iters[:s]], resid=resid[:s].cpu().numpy(),
+                next_ctr=tuple(int(v) for v in st[:4]))
 
 
 # ---- the sparse matrix-vector layer (spmv.hip) and least squares over an operator (DenseOperator, CsrOperator, CscOperator, CooOperator)
