@@ -664,7 +664,7 @@ int rlhip_pcg_saddle_step_d_f32(rlhip_ctx* ctx, int64_t n, const float* r, const
  * well), 48 rlhip_gemv 'N', 49 rlhip_gemv 'T' (calls that launch nothing are not counted).  -1 for any other index. */
 int64_t rlhip_lsq_path_count(rlhip_ctx* ctx, int which);
 
-/* ---- least squares with several right-hand sides (lsq_block.hip): the hot path of RandLAPACK::pcg_saddle_block (rl_determiter.hh;
+/* ---- least squares with several right-hand sides (lsq.hip): the hot path of RandLAPACK::pcg_saddle_block (rl_determiter.hh;
  *      DESIGN 4.31).  Column-major DEVICE operands with leading dimensions; the rules of the layer above hold (no workgroup waits for
  *      another, no floating-point atomic, static slabs, partials in the scratch arena and a final pass in a fixed order), and on top of them
  *      COLUMN INDEPENDENCE: column j of every output is a function of A, delta and column j of the inputs alone; for given sizes, max_wg and

@@ -312,7 +312,7 @@ for _suf, _T in (("f64", c_dbl), ("f32", c_flt)):      # the regularization path
                                                               c_vp, c_i64, i64p, _dp, _dp, _dp, i64p, _dp]),
     })
 
-# least squares with several right-hand sides (lsq_block.hip, rl_determiter.hh pcg_saddle_block, rl_lstsq.hh)
+# least squares with several right-hand sides (lsq.hip, rl_determiter.hh pcg_saddle_block, rl_lstsq.hh)
 SIGNATURES["rlhip_normal_matmat_fused"] = (c_int, [c_i64, c_i64, c_int])
 SIGNATURES["rlhip_normal_matmat_default"] = (c_int, [c_i64, c_i64, c_int])
 SIGNATURES["rlhip_normal_matmat_set_route"] = (c_int, [c_vp, c_int])

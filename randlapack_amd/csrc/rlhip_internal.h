@@ -190,7 +190,7 @@ struct rlhip_ctx {
     // the routes of the kernel-gradient apply (rbf_grad.hip), read through rlhip_pdk_grad_path_count: [0] = 74 fused, [1] = 75 composed
     int64_t grad_path_count[2] = {};
     int grad_fused = 0;              // rlhip_pdk_grad_set_fused: 1 = rlhip_pdk_cross_grad_* takes its fused kernel where the shape allows
-    // the routes of the block least-squares layer (lsq_block.hip), read through rlhip_lsq_block_path_count: [0] = 76 one-pass normal matmat,
+    // the routes of the block least-squares layer (lsq.hip), read through rlhip_lsq_block_path_count: [0] = 76 one-pass normal matmat,
     // [1] = 77 composed normal matmat, [2] = 78 iterations of pcg_saddle_block (block step_d calls that update d)
     int64_t lsq_block_path_count[3] = {};
     int matmat_route = -1;           // rlhip_normal_matmat_set_route: -1 the default, 0 always composed, 1 one-pass wherever the shape allows

@@ -1576,7 +1576,7 @@ def sap_lstsq(ctx: Context, A, m, n, b, c, delta, d_factor, nnz, tol, iter_lim, 
     return dict(x=x, y=y, rank=int(rank.value), iters=it, resid=resid[: it + 1].cpu().numpy(), next_ctr=tuple(int(v) for v in st[:4]))
 
 
-# ---- several right-hand sides (lsq_block.hip, rl_determiter.hh pcg_saddle_block, rl_lstsq.hh).  A block of s vectors is a
+# ---- several right-hand sides (lsq.hip, rl_determiter.hh pcg_saddle_block, rl_lstsq.hh).  A block of s vectors is a
 #      column-major tensor (s, ld) like a matrix.
 def normal_matmat_fused(n, s, elem_bytes):
     """the chunk width rlhip_normal_matmat_*'s one-pass route uses for this shape, 0 outside its limits (no device needed)"""

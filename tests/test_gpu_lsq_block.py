@@ -1,4 +1,4 @@
-"""Least squares with several right-hand sides on the device (randlapack_amd/csrc/lsq_block.hip, include/RandLAPACK_amd/rl_determiter.hh
+"""Least squares with several right-hand sides on the device (randlapack_amd/csrc/lsq.hip, include/RandLAPACK_amd/rl_determiter.hh
 pcg_saddle_block, rl_lstsq.hh) in fp64 and fp32: the normal product exactly on small integers on both routes, column
 independence bit for bit, the two routes against each other, the block solver step by step against the model (tests/_lsq_block_model.py: the
 single-column model column by column), convergence and freezing with the model as the yardstick, sap_lstsq with s right-hand sides against s
@@ -443,6 +443,85 @@ def test_argument_codes(ctx, prec):
     assert sd(*args(old=None, new=p(hist), D=None, tol=1.0)) == 0 and _np(act).tolist() == [0, 0] and _np(rel).tolist() == [8.0, 32.0]
     R[1, 0] = NAN
     assert sd(*args(old=None, new=p(hist), D=None, tol=0.5)) == 0 and _np(act).tolist() == [1, 0] and np.isnan(_np(hist)[1, 0])
+
+
+@pytest.mark.parametrize("prec", ["f64", "f32"])
+@pytest.mark.parametrize("n_kind,stalled", [(1, False), (256, False), (257, False), ("wrap", False), (257, True)])
+def test_single_steps_are_block_steps_with_one_column(ctx, n_kind, stalled, prec):
+    """rlhip_pcg_saddle_step_{d, xr, refresh}_* against rlhip_pcg_saddle_block_step_*_* with s = 1 on copies of the same random inputs: step_d
+    (first call), step_xr with q, step_xr without q, step_refresh, step_d (update).  Every output -- x, r, d, delta1 -- must agree bit for
+    bit, the sentinels behind every vector must survive, and the single calls must not move counter 78 (the block update call moves it by
+    one).  n = 256 and 257 lie on either side of the stride of the dot product, n = 256 num_cu + 3 makes step_xr's grid-stride loop wrap.
+    stalled: s = 0, so the first step_d finds delta1 = 0 and the block call clears its flag (0 > 0 is false).  The single entry points have
+    no flag -- the ONE intended difference: the block calls then leave x, r, d and the next delta1 alone while the single calls still write
+    them."""
+    import torch
+
+    T = DT[prec]
+    lib, h = ctx.lib, ctx.h
+    n = 256 * torch.cuda.get_device_properties(0).multi_processor_count + 3 if n_kind == "wrap" else n_kind
+    PAD, delta, tol = 4, 0.375, 1e-3
+    rng = np.random.default_rng(7000 + n)
+
+    def buf(v):
+        return torch.from_numpy(np.concatenate([np.asarray(v, dtype=T), np.full(PAD, SENT, dtype=T)])).to("cuda:0")
+
+    names = ("x", "r", "d", "q", "qx", "b1")
+    host = {k: rng.standard_normal(n) for k in names}
+    host["s"] = np.zeros(n) if stalled else host["r"] * (0.5 + rng.random(n))    # r^T s > 0 unless stalled
+    one = {k: buf(v) for k, v in host.items()}                                   # the single calls' vectors
+    blk = {k: t.clone() for k, t in one.items()}                                 # the block calls'
+    first = {k: t.clone() for k, t in one.items()}                               # as they went in
+    scal = lambda v: torch.tensor(v, dtype=one["x"].dtype, device="cuda:0")
+    dq = scal([1.5 + rng.random()])
+    hist1, histb = scal([SENT, SENT, SENT]), scal([SENT, SENT, SENT])            # delta1 of the first call, of the update, a sentinel
+    rel, act = scal([SENT, SENT]), torch.tensor([7, 7], dtype=torch.int32, device="cuda:0")
+    p, eb, ld = (lambda t: t.data_ptr()), one["x"].element_size(), n + PAD
+    fn = lambda name: getattr(lib, f"rlhip_pcg_saddle_{name}_{prec}")
+    before = _counts(ctx)
+
+    # step_d, the first call
+    assert fn("step_d")(h, n, p(one["r"]), p(one["s"]), None, p(hist1), None) == 0
+    assert fn("block_step_d")(h, n, 1, p(blk["r"]), ld, p(blk["s"]), ld, None, p(histb), 2, None, ld, tol, p(rel), p(act)) == 0
+    assert torch.equal(hist1, histb) and _np(hist1)[1:].tolist() == [SENT, SENT]
+    d1 = _np(hist1)[0]
+    print(f"n = {n} {prec}: delta1 = {d1!r}")
+    assert _np(rel).tolist() == [T(T(d1 * T(tol)) * T(tol)), SENT] and _np(act).tolist() == [0 if stalled else 1, 7]
+    assert (d1 == 0) if stalled else (d1 > 0)
+    # step_xr with q, then without
+    assert fn("step_xr")(h, n, p(one["d"]), p(one["q"]), p(dq), p(hist1), p(one["x"]), p(one["r"])) == 0
+    assert fn("block_step_xr")(h, n, 1, p(blk["d"]), ld, p(blk["q"]), ld, p(dq), p(histb), 2, p(blk["x"]), ld, p(blk["r"]), ld, p(act)) == 0
+    if not stalled:
+        assert torch.equal(one["x"], blk["x"]) and torch.equal(one["r"], blk["r"])
+        assert not torch.equal(one["x"], first["x"]) and not torch.equal(one["r"], first["r"])
+        after_q = one["r"].clone()
+    assert fn("step_xr")(h, n, p(one["d"]), None, p(dq), p(hist1), p(one["x"]), None) == 0
+    assert fn("block_step_xr")(h, n, 1, p(blk["d"]), ld, None, ld, p(dq), p(histb), 2, p(blk["x"]), ld, None, ld, p(act)) == 0
+    if not stalled:
+        assert torch.equal(one["x"], blk["x"]) and torch.equal(one["r"], after_q) and torch.equal(blk["r"], after_q)
+    # step_refresh
+    assert fn("step_refresh")(h, n, p(one["b1"]), p(one["qx"]), delta, p(one["x"]), p(one["r"])) == 0
+    assert fn("block_step_refresh")(h, n, 1, p(blk["b1"]), ld, p(blk["qx"]), ld, delta, p(blk["x"]), ld, p(blk["r"]), ld, p(act)) == 0
+    if not stalled:
+        assert torch.equal(one["r"], blk["r"]) and not torch.equal(one["r"], after_q)
+    assert _counts(ctx) == before
+    # step_d, the update
+    assert fn("step_d")(h, n, p(one["r"]), p(one["s"]), p(hist1), p(hist1) + eb, p(one["d"])) == 0
+    assert _counts(ctx) == before                                                # no single call is an iteration of the block solver
+    assert fn("block_step_d")(h, n, 1, p(blk["r"]), ld, p(blk["s"]), ld, p(histb), p(histb) + eb, 2, p(blk["d"]), ld, tol, p(rel), p(act)) == 0
+    assert [a - b for a, b in zip(_counts(ctx), before)] == [0, 0, 1]            # counted on the host, whatever the flag holds
+    if not stalled:
+        assert torch.equal(hist1, histb) and torch.equal(one["d"], blk["d"]) and not torch.equal(one["d"], first["d"])
+        assert _np(hist1)[1] != SENT and _np(hist1)[2] == SENT
+    else:
+        # the block column was left alone by every call after the first; the single calls wrote r (refresh) and delta1 (update)
+        assert all(torch.equal(blk[k], first[k]) for k in names) and _np(histb).tolist() == [0.0, SENT, SENT] and _np(act).tolist() == [0, 7]
+        assert not torch.equal(one["r"], first["r"]) and _np(hist1)[:2].tolist() == [0.0, 0.0] and _np(hist1)[2] == SENT
+    # nothing was written behind a vector, no input was written
+    for k in names + ("s",):
+        assert np.all(_np(one[k])[n:] == SENT) and np.all(_np(blk[k])[n:] == SENT), k
+    for k in ("q", "qx", "b1", "s"):
+        assert torch.equal(one[k], first[k]) and torch.equal(blk[k], first[k]), k
 
 
 @pytest.mark.parametrize("prec", ["f64", "f32"])
